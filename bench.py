@@ -2,7 +2,17 @@
 """Benchmark: audio samples/s (22.05 kHz) + real-time factor of the m2-tts
 mel-synthesis + vocoder path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: set-up,
+``--settle-ms`` of untimed load, W warm-up steps, exactly K timed steps, then
+one JSON line (``value``, ``ms_per_step`` = the milliseconds one timed step
+took, ...).  ``--dump-outputs DIR`` also writes the arrays the K-th timed step
+returned to its caller as ``DIR/<name>.npy`` (float32; at most 64 MB in all,
+a fixed seeded sample of a larger array): the inputs are seeded, so two
+builds can be compared output for output.  ``--full`` adds everything else
+the benchmark measures (below); the headline of a ``--full`` run also
+carries the HIP-event roofline sampling inside its timed steps.
 
 One process per GPU, RCCL (torch.distributed "nccl") between them.  With
 ``--gpus N > 1`` and no WORLD_SIZE in the environment, this process starts N
@@ -29,9 +39,11 @@ Workloads (BASELINE.json configs):
                streamed in 256-frame chunks (3-frame halo)
   s2_vocoder   stage2 SimpleVocoder at the per-GPU shape of configs[3] on 8
                GPUs: B=8, T=500 (per-kernel roofline table)
-The default run measures ``vocoder`` as the headline ``value`` and adds the
-other workloads, the exact-f32 vocoder, and (rank 0, N=1) the CPU oracle as
-sub-objects of the same JSON line.
+The default run measures ``vocoder`` as the headline ``value``.  With
+``--full`` the headline gets its per-kernel table and roofline, and the other
+workloads, the report-policy and exact-f32 vocoder lines, and (rank 0, N=1)
+the CPU oracle are added as sub-objects of the same JSON line
+(``--no-extras`` / ``--no-cpu-baseline`` drop those again).
 """
 from __future__ import annotations
 
@@ -350,6 +362,30 @@ def samples_per(B: int, T: int) -> int:
     return B * 64 * T
 
 
+DUMP_BUDGET = 60 * 10 ** 6   # bytes --dump-outputs writes at most in all (under 64 MB by either count)
+DUMP_SEED = 0
+
+
+def dump_outputs(dirpath: str, named):
+    """Write each (name, tensor) as dirpath/name.npy in float32 (float64 stays
+    float64).  The arrays share DUMP_BUDGET equally; one over its share is
+    written as a 1-D sample of its flattened elements at sorted indices drawn
+    once from a generator seeded with DUMP_SEED, so two runs of the same
+    shape keep the same elements."""
+    import numpy as np
+    os.makedirs(dirpath, exist_ok=True)
+    share = (DUMP_BUDGET - (1 << 16)) // max(1, len(named))  # the .npy headers fit in the slack
+    for name, t in named:
+        a = t.detach().cpu()
+        if a.dtype != torch.float64:
+            a = a.float()
+        if a.numel() * a.element_size() > share:
+            g = torch.Generator().manual_seed(DUMP_SEED)
+            idx = torch.randint(0, a.numel(), (share // a.element_size(),), generator=g).sort().values
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirpath, name + ".npy"), a.contiguous().numpy())
+
+
 # ---------------------------------------------------------------------------- launcher
 def _free_port() -> int:
     s = socket.socket()
@@ -385,8 +421,13 @@ def parse_args(argv=None):
     ap.add_argument("--phonemes", type=int, default=100)
     ap.add_argument("--s2-shape", default="8x500", help="BxT of the s2_vocoder workload")
     ap.add_argument("--cpu-runs", type=int, default=7, help="CPU baseline: measurements per workload (median of the clean ones)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="headline line only")
+    ap.add_argument("--full", action="store_true",
+                    help="also: the headline's per-kernel table and roofline, the other workloads and vocoder "
+                         "paths, the sharded lines' parity checks, and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the lines beside the headline")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL (default); gloo only to rehearse N ranks sharing one GPU")
     ap.add_argument("--dry-run", action="store_true",
@@ -423,6 +464,7 @@ class Ctx:
         self.nk = self.lib.m2_profile_kernel_count()
         self.models = {}
         self.backend = "RCCL"
+        self.last = None  # what the last step of a timed(..., keep=True) region returned
 
     def model(self, stage: str):
         if stage not in self.models:
@@ -463,11 +505,14 @@ class Ctx:
             torch.cuda.synchronize(self.dev)
         return (time.perf_counter() - t0) * 1e3
 
-    def timed(self, fn, steps: int, warmup: int, hm=None, kernel_mask: int = 0, stride: int = 1):
+    def timed(self, fn, steps: int, warmup: int, hm=None, kernel_mask: int = 0, stride: int = 1,
+              keep: bool = False):
         """Run `steps` of fn between barriers + syncs (max over ranks); with
         kernel_mask, fence-free HIP events on the launch stream inside
-        m2_vocoder around the selected vocoder kernels of every stride-th call."""
+        m2_vocoder around the selected vocoder kernels of every stride-th call.
+        keep: leave what the last of the steps returned in self.last."""
         lib, chk = self.lib, self._lib.check
+        keep = keep and steps > 0
         for _ in range(warmup):
             fn()
         if kernel_mask:
@@ -477,8 +522,10 @@ class Ctx:
         torch.cuda.synchronize(self.dev)
         self.barrier()
         t0 = time.perf_counter()
-        for _ in range(steps):
+        for _ in range(steps - 1 if keep else steps):
             fn()
+        if keep:
+            self.last = fn()
         torch.cuda.synchronize(self.dev)
         self.barrier()
         el = time.perf_counter() - t0
@@ -523,10 +570,12 @@ def traffic_for(kernel_name: str):
     return v, d.get("_source", "profiles/traffic.json")
 
 
-def vocoder_line(cx: Ctx, stage: str, B: int, T: int, args, settle_ms: float, seed: int, f32: bool = False):
-    """SimpleVocoder throughput on mel [B, M, T] per rank (weak scaling), the
-    per-kernel HIP-event table, and the dominant kernel's roofline sampled
-    live inside the timed region."""
+def vocoder_line(cx: Ctx, stage: str, B: int, T: int, args, settle_ms: float, seed: int, f32: bool = False,
+                 profile: bool = True, keep: bool = False):
+    """SimpleVocoder throughput on mel [B, M, T] per rank (weak scaling); with
+    profile, also the per-kernel HIP-event table (a pass of its own) and the
+    dominant kernel's roofline sampled live inside the timed region.
+    keep: the last timed step's audio stays in cx.last."""
     cfg = STAGE1 if stage == "s1" else STAGE2
     m = cx.model(stage)
     hm = m._hip(cx.dev)
@@ -536,16 +585,21 @@ def vocoder_line(cx: Ctx, stage: str, B: int, T: int, args, settle_ms: float, se
         mel = torch.randn(B, cfg["mel_channels"], T, generator=g).to(cx.dev)
         step = lambda: m.vocoder(mel)  # noqa: E731
         settled = cx.settle(step, settle_ms)
-        # untimed pass with events on all three kernels -> per-kernel table + dominant kernel
-        _, all_ms = cx.timed(step, min(args.steps, 20), 2, hm, kernel_mask=(1 << cx.nk) - 1)
-        per_kernel = cx.kernel_table(hm, all_ms, cfg["vocoder_channels"], cfg["mel_channels"], B, T)
-        dom_i = max(per_kernel, key=lambda d: d["avg_ms"])["index"] if per_kernel else 0
-        # every stride-th call carries the events (at least every 4th: 5 of the
-        # driver's 20 steps): a sampled call pays ~4.5 us before and after its
-        # timed kernel (profiles/r05/r05o_gaps.txt), unsampled none; every call
-        # sampled cost the driver-form line ~3 % (profiles/r06/r06as_bench*.json)
-        stride = max(4, args.steps // 16)
-        elapsed, kern_ms = cx.timed(step, args.steps, args.warmup, hm, kernel_mask=1 << dom_i, stride=stride)
+        if profile:
+            # untimed pass with events on all three kernels -> per-kernel table + dominant kernel
+            _, all_ms = cx.timed(step, min(args.steps, 20), 2, hm, kernel_mask=(1 << cx.nk) - 1)
+            per_kernel = cx.kernel_table(hm, all_ms, cfg["vocoder_channels"], cfg["mel_channels"], B, T)
+            dom_i = max(per_kernel, key=lambda d: d["avg_ms"])["index"] if per_kernel else 0
+            # every stride-th call carries the events (at least every 4th: 5 of
+            # 20 steps): a sampled call pays ~4.5 us before and after its timed
+            # kernel (profiles/r05/r05o_gaps.txt), unsampled none; every call
+            # sampled cost a 20-step line ~3 % (profiles/r06/r06as_bench*.json)
+            stride = max(4, args.steps // 16)
+            elapsed, kern_ms = cx.timed(step, args.steps, args.warmup, hm, kernel_mask=1 << dom_i, stride=stride,
+                                        keep=keep)
+        else:
+            per_kernel, kern_ms, stride = [], [], 0
+            elapsed, _ = cx.timed(step, args.steps, args.warmup, keep=keep)
         path = cx.lib.m2_vocoder_path(hm.handle)
         # (before the path is restored: the table's kernel names and peak are this path's)
         live = cx.kernel_table(hm, kern_ms, cfg["vocoder_channels"], cfg["mel_channels"], B, T)
@@ -592,6 +646,9 @@ def vocoder_line(cx: Ctx, stage: str, B: int, T: int, args, settle_ms: float, se
            "mrf_hbm_fraction_def": "sum(resblock bytes 8cL + weights, SURVEY 8d) / whole-vocoder step time / 8 TB/s",
            "fp32_valu_fraction": round(value / cx.world * flop_s / (FP32_PEAK_TFLOPS * 1e12), 4),
            "fp32_valu_fraction_def": "algorithmic vocoder FLOP/s / 157.3 TF (MI355X fp32 vector peak)"}
+    if not profile:  # no event passes ran: the line carries no per-kernel figures
+        for k in ("roofline", "vocoder_kernels", "vocoder_hbm"):
+            del out[k]
     return out
 
 
@@ -636,16 +693,26 @@ def report_policy_line(cx: Ctx, B: int, T: int, args, head: dict):
                       "(same steps and event sampling); cost = difference of the medians"}
 
 
-def pipeline_line(cx: Ctx, B: int, S: int, args, settle_ms: float):
+def pipeline_line(cx: Ctx, B: int, S: int, args, settle_ms: float, head: bool = False):
+    """head: the run's headline (exactly --steps timed steps after --warmup,
+    the last step's (mel, audio) kept in cx.last); else a side line of a
+    --full run on half of each."""
     m = cx.model("s1")
     g = torch.Generator().manual_seed(1000 + cx.rank)
     ids = torch.randint(0, 42, (B, S), generator=g).to(cx.dev)
     lens = torch.full((B,), S, dtype=torch.long, device=cx.dev)
     step = lambda: m.inference(ids, lens)  # noqa: E731
     settled = cx.settle(step, settle_ms)
-    steps = max(10, args.steps // 2)
-    elapsed, _ = cx.timed(step, steps, max(3, args.warmup // 2))
+    steps = args.steps if head else max(10, args.steps // 2)
+    elapsed, _ = cx.timed(step, steps, args.warmup if head else max(3, args.warmup // 2), keep=head)
     T = 5 * S
+    out = {"value": round(samples_per(B, T) * steps * cx.world / elapsed, 1),
+           "ms_per_step": round(elapsed / steps * 1e3, 5), "steps": steps, "settle_ms": round(settled, 1),
+           "scaling": "weak",
+           "config": {"workload": "stage1_poc M2TTSModel.inference (configs[2])",
+                      "per_gpu_batch": B, "global_batch": B * cx.world, "phonemes": S, "mel_frames": T}}
+    if not args.full:
+        return out
     # SURVEY.md 8d: the frame counts and how far the durations sit from the
     # int() truncation points (a duration within ~1e-6 of an integer could
     # flip a frame count between the GPU and the CPU path)
@@ -653,25 +720,23 @@ def pipeline_line(cx: Ctx, B: int, S: int, args, settle_ms: float):
         mel, _ = m.inference(ids, lens)
         dur = m(ids, lens)["duration_pred"].double()
     tot = torch.trunc(dur).clamp(min=0).sum(1).to(torch.int64).cpu()
-    frames = {"gpu_T_per_utt": tot.tolist(), "T": int(mel.shape[1]),
-              "T_is_batch_max": int(mel.shape[1]) == max(1, int(tot.max())),
-              "min_duration_dist_to_int": float((dur - dur.round()).abs().min()),
-              "ids_seed": 1000 + cx.rank}
-    return {"value": round(samples_per(B, T) * steps * cx.world / elapsed, 1),
-            "ms_per_step": round(elapsed / steps * 1e3, 5), "steps": steps, "settle_ms": round(settled, 1),
-            "scaling": "weak", "frames": frames,
-            "config": {"workload": "stage1_poc M2TTSModel.inference (configs[2])",
-                       "per_gpu_batch": B, "global_batch": B * cx.world, "phonemes": S, "mel_frames": T}}
+    out["frames"] = {"gpu_T_per_utt": tot.tolist(), "T": int(mel.shape[1]),
+                     "T_is_batch_max": int(mel.shape[1]) == max(1, int(tot.max())),
+                     "min_duration_dist_to_int": float((dur - dur.round()).abs().min()),
+                     "ids_seed": 1000 + cx.rank}
+    return out
 
 
 def sharded_line(cx: Ctx, Bg: int, S: int, chunk: int, args, settle_ms: float, steps: int, share: bool = False,
-                 depth: int = 1):
+                 depth: int = 1, warmup: int = 2, keep: bool = False):
     """stage2 inference over a global batch of Bg utterances sharded across the
     ranks (configs[3] / [4]): per step the front half (T_max into a device
     word), RCCL all_reduce(MAX) of that word, the back half reading T from it
     and a gather of mel / audio to rank 0.  depth > 1: ShardedPipeline with
     that many global batches in flight per rank (one stream and model handle
-    per lane; step i + 1's front half beside step i's back half and gather)."""
+    per lane; step i + 1's front half beside step i's back half and gather).
+    keep (depth 1): the last timed step's (mel, audio) stay in cx.last.  The
+    parity check and the phase split after the timed steps run with --full."""
     from m2amd.parallel import ShardedPipeline, hip_stages, shard_bounds, sharded_inference
     import torch.distributed as td
     m = cx.model("s2")
@@ -702,7 +767,17 @@ def sharded_line(cx: Ctx, Bg: int, S: int, chunk: int, args, settle_ms: float, s
         if cx.rank == 0:
             assert mel.shape == (Bg, T, 80) and audio.shape == (Bg, 1, 64 * T)
         settled = cx.settle(step, settle_ms)
-        elapsed, _ = cx.timed(step, steps, 2)
+        elapsed, _ = cx.timed(step, steps, warmup, keep=keep and depth == 1)
+        lo, hi = shard_bounds(Bg, cx.world, cx.rank)
+        out = {"value": round(samples_per(Bg, T) * steps / elapsed, 1), "ms_per_step": round(elapsed / steps * 1e3, 4),
+               "steps": steps, "settle_ms": round(settled, 1), "scaling": "strong", "in_flight": depth,
+               "rtf_x_realtime": round(samples_per(Bg, T) * steps / elapsed / SAMPLE_RATE, 1),
+               "config": {"stage": "stage2_quality", "global_batch": Bg, "per_gpu_batch": hi - lo, "phonemes": S,
+                          "mel_frames": T, "vocoder_chunk_frames": chunk, "n_ranks": cx.world,
+                          "collectives": f"all_reduce(MAX) 1 x int32 + gather of mel/audio to rank 0 ({cx.backend})"
+                          if cx.dist else "none (world 1)"}}
+        if not args.full:
+            return out
         # the outputs of one more step against a world-1 inference of the same
         # global batch on rank 0 (tts_model.py:402-438): the first multi-GPU
         # run checks its own gathered results
@@ -740,7 +815,6 @@ def sharded_line(cx: Ctx, Bg: int, S: int, chunk: int, args, settle_ms: float, s
         # split of one step on the device-T flow the timed line uses (rank-local
         # wall times): front half writing T_max to a device word, all_reduce(MAX)
         # of that word, back half launched for the capacity reading T from it
-        lo, hi = shard_bounds(Bg, cx.world, cx.rank)
         hm = m._hip(cx.dev)
         cap = st.tcap.get((Bg, S, 1.0), T)
         M = 80
@@ -787,14 +861,7 @@ def sharded_line(cx: Ctx, Bg: int, S: int, chunk: int, args, settle_ms: float, s
         med = [sorted(c)[len(c) // 2] for c in zip(*ph)]
     finally:
         m.set_vocoder_chunking(0)
-    return {"value": round(samples_per(Bg, T) * steps / elapsed, 1), "ms_per_step": round(elapsed / steps * 1e3, 4),
-            "steps": steps, "settle_ms": round(settled, 1), "scaling": "strong", "in_flight": depth,
-            "rtf_x_realtime": round(samples_per(Bg, T) * steps / elapsed / SAMPLE_RATE, 1),
-            "config": {"stage": "stage2_quality", "global_batch": Bg, "per_gpu_batch": hi - lo, "phonemes": S,
-                       "mel_frames": T, "vocoder_chunk_frames": chunk, "n_ranks": cx.world,
-                       "collectives": f"all_reduce(MAX) 1 x int32 + gather of mel/audio to rank 0 ({cx.backend})" if cx.dist
-                       else "none (world 1)"},
-            "parity": parity,
+    return {**out, "parity": parity,
             "rank0_phase_ms": {"front_enqueue": round(med[0], 3), "all_reduce_enqueue": round(med[1], 3),
                                "back_enqueue": round(med[2], 3), "drain": round(med[3], 3),
                                "front_gpu_elapsed": round(med[4], 3), "back_gpu_elapsed": round(med[5], 3),
@@ -846,25 +913,35 @@ def run(args):
     wl = args.workload
     extras = _Progress(rank)
 
+    # the headline: exactly --steps timed steps after --warmup, the last step's
+    # outputs kept for --dump-outputs; its event passes only with --full
     if wl == "vocoder":
-        head = vocoder_line(cx, "s1", B, 5 * S, args, args.settle_ms, 1000)
+        head = vocoder_line(cx, "s1", B, 5 * S, args, args.settle_ms, 1000, profile=args.full, keep=True)
         desc = "stage1_poc SimpleVocoder B=32 per GPU (configs[1])"
+        names = ("audio",)
     elif wl == "s2_vocoder":
         b2, t2 = (int(v) for v in args.s2_shape.split("x"))
-        head = vocoder_line(cx, "s2", b2, t2, args, args.settle_ms, 3000)
+        head = vocoder_line(cx, "s2", b2, t2, args, args.settle_ms, 3000, profile=args.full, keep=True)
         desc = f"stage2_quality SimpleVocoder B={b2} T={t2} per GPU (configs[3] per-GPU shape: 8x500)"
+        names = ("audio",)
     elif wl == "pipeline":
-        head = pipeline_line(cx, B, S, args, args.settle_ms)
+        head = pipeline_line(cx, B, S, args, args.settle_ms, head=True)
         desc = head["config"]["workload"]
+        names = ("mel", "audio")
     else:
         Bg, Sg, chunk = (64, 100, 0) if wl == "s2_b64" else (128, 520, 256)
-        head = sharded_line(cx, Bg, Sg, chunk, args, args.settle_ms, args.steps if wl == "s2_b64" else
-                            max(5, args.steps // 10))
+        head = sharded_line(cx, Bg, Sg, chunk, args, args.settle_ms, args.steps, warmup=args.warmup, keep=True)
         desc = f"stage2_quality M2TTSModel.inference global B={Bg} S={Sg} sharded x{world} ({wl}, configs[" \
                f"{3 if wl == 's2_b64' else 4}])"
+        names = ("mel", "audio")  # gathered to rank 0
 
     print(f"[bench rank {rank}] {wl}: {head['ms_per_step']} ms/step", file=sys.stderr, flush=True)
-    if not args.no_extras:
+    last, cx.last = cx.last, None
+    if args.dump_outputs and rank == 0:
+        last = last if isinstance(last, (tuple, list)) else (last,)
+        dump_outputs(args.dump_outputs, list(zip(names, last)))
+    del last
+    if args.full and not args.no_extras:
         if wl != "pipeline":
             extras["pipeline"] = pipeline_line(cx, B, S, args, 100.0)
         if wl == "vocoder":
@@ -902,7 +979,7 @@ def run(args):
             extras["s2_longform_sharded"] = sharded_line(cx, 128, 520, 256, args, 100.0, max(3, args.steps // 40))
 
     out = {"metric": METRIC, "value": head["value"], "unit": "audio samples/s", "n_gpus": world,
-           "steps": args.steps if wl != "pipeline" else head["steps"], "warmup": args.warmup,
+           "steps": args.steps, "warmup": args.warmup, "full": args.full,
            "ms_per_step": head["ms_per_step"], "higher_is_better": True,
            "scaling": head.get("scaling", "weak"), "vs_baseline": None,
            "dtype": head.get("dtype", VOC_PATHS[2][0]),
@@ -926,7 +1003,7 @@ def run(args):
     if isinstance(out.get("roofline"), dict) and extras.get("roofline_exact_f32"):
         out["roofline"]["exact_f32"] = extras["roofline_exact_f32"]
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and wl in ("vocoder", "pipeline"):
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and wl in ("vocoder", "pipeline"):
         pipe = out.get("pipeline") if wl == "vocoder" else head
         cb = cpu_baseline(B, S, 5 * S, runs=args.cpu_runs,
                           ids_seed=pipe["frames"]["ids_seed"] if isinstance(pipe, dict) and "frames" in pipe else None)
