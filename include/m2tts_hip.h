@@ -78,7 +78,8 @@ int64_t m2_weight_numel(const m2_config* cfg, int32_t index);
 /* Packs and uploads the weights once (BatchNorm folded into the duration
  * convs, conv weights re-laid out for the kernels).  `weights[i]` is a device
  * pointer to the tensor named by m2_weight_name(cfg, i) (fp32; the BatchNorm
- * num_batches_tracked entries are int64 and ignored).  Synchronises `stream`. */
+ * num_batches_tracked entries are int64 and ignored).  Reads the weights back
+ * to the host once and synchronises `stream`. */
 int32_t m2_model_create(const m2_config* cfg, const void* const* weights, int32_t n_weights,
                         void* stream, m2_model** out);
 int32_t m2_model_destroy(m2_model* model);

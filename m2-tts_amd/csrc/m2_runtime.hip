@@ -1,4 +1,4 @@
-// C-ABI runtime: weight table, model handle, stage orchestration.
+// C-ABI runtime: switch table, stage orchestration (the handle: m2_model.hip).
 // See include/m2tts_hip.h for the contract of every entry point.
 #include <immintrin.h>
 
@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "m2_common.h"
+#include "m2_model.h"
 #include "transformer_fused.h"
 #include "transformer_layer.h"
 #include "vocoder_fused.h"
@@ -147,7 +148,6 @@ int32_t hip_status(hipError_t e, const char* where) {
     return static_cast<int32_t>(e);
 }
 
-static constexpr int kRates[4] = {4, 4, 2, 2};  // tts_model.py:244
 // Receptive field of one audio sample in mel frames, per side: input_conv 1,
 // ConvT1 ~1 (two taps), then ResBlock/ConvT stages at 4x..64x, 3 frames in
 // total (tools/probe/receptive_field.py propagates the index intervals layer
@@ -159,163 +159,7 @@ static constexpr int kVocHalo = 3;
 // target durations) are M2_E_SHAPE, not a wrapped or truncated int32.
 static constexpr int32_t kMaxFrames = 1 << 24;
 
-
-// ---------------------------------------------------------------------------
-// Weight table in M2TTSModel.state_dict() order (tts_model.py:303-343).
-struct WSpec {
-    std::string name;
-    int64_t numel;
-    bool is_int64;
-};
-
-static void add_layer(std::vector<WSpec>& t, const std::string& p, int64_t H) {
-    t.push_back({p + ".self_attn.qkv.weight", 3 * H * H, false});
-    t.push_back({p + ".self_attn.out_proj.weight", H * H, false});
-    t.push_back({p + ".self_attn.out_proj.bias", H, false});
-    t.push_back({p + ".ffn.linear1.weight", 2 * H * H, false});
-    t.push_back({p + ".ffn.linear1.bias", 2 * H, false});
-    t.push_back({p + ".ffn.linear2.weight", 2 * H * H, false});
-    t.push_back({p + ".ffn.linear2.bias", H, false});
-    t.push_back({p + ".norm1.weight", H, false});
-    t.push_back({p + ".norm1.bias", H, false});
-    t.push_back({p + ".norm2.weight", H, false});
-    t.push_back({p + ".norm2.bias", H, false});
-}
-
-static std::vector<WSpec> weight_table(const m2_config& c) {
-    std::vector<WSpec> t;
-    const int64_t H = c.hidden_dim, M = c.mel_channels, C = c.vocoder_channels;
-    t.push_back({"text_encoder.embedding.weight", (int64_t)c.vocab_size * H, false});
-    t.push_back({"text_encoder.pos_encoding.pe", (int64_t)c.max_positions * H, false});
-    for (int i = 0; i < c.text_encoder_layers; ++i) add_layer(t, "text_encoder.layers." + std::to_string(i), H);
-    t.push_back({"text_encoder.norm.weight", H, false});
-    t.push_back({"text_encoder.norm.bias", H, false});
-    for (int j = 0; j < 2; ++j) {
-        const std::string p = "duration_predictor.predictor.conv_layers." + std::to_string(j);
-        t.push_back({p + ".conv.weight", H * H * 3, false});
-        t.push_back({p + ".conv.bias", H, false});
-        t.push_back({p + ".norm.weight", H, false});
-        t.push_back({p + ".norm.bias", H, false});
-        t.push_back({p + ".norm.running_mean", H, false});
-        t.push_back({p + ".norm.running_var", H, false});
-        t.push_back({p + ".norm.num_batches_tracked", 1, true});
-    }
-    t.push_back({"duration_predictor.predictor.projection.weight", H, false});
-    t.push_back({"duration_predictor.predictor.projection.bias", 1, false});
-    for (int i = 0; i < c.decoder_layers; ++i) add_layer(t, "decoder.layers." + std::to_string(i), H);
-    t.push_back({"decoder.norm.weight", H, false});
-    t.push_back({"decoder.norm.bias", H, false});
-    t.push_back({"decoder.mel_projection.weight", M * H, false});
-    t.push_back({"decoder.mel_projection.bias", M, false});
-    t.push_back({"vocoder.input_conv.weight", C * M * 3, false});
-    t.push_back({"vocoder.input_conv.bias", C, false});
-    int64_t ch = C;
-    for (int k = 0; k < 4; ++k) {
-        const std::string p = "vocoder.upsamples." + std::to_string(k);
-        t.push_back({p + ".weight", ch * (ch / 2) * 2 * kRates[k], false});
-        t.push_back({p + ".bias", ch / 2, false});
-        ch /= 2;
-    }
-    ch = C;
-    for (int k = 0; k < 4; ++k) {
-        ch /= 2;
-        const std::string p = "vocoder.resblocks." + std::to_string(k);
-        t.push_back({p + ".conv1.weight", ch * ch * 3, false});
-        t.push_back({p + ".conv1.bias", ch, false});
-        t.push_back({p + ".conv2.weight", ch * ch * 3, false});
-        t.push_back({p + ".conv2.bias", ch, false});
-    }
-    t.push_back({"vocoder.output_conv.weight", ch * 3, false});
-    t.push_back({"vocoder.output_conv.bias", 1, false});
-    return t;
-}
-
-static bool config_ok(const m2_config* c) {
-    if (!c) return false;
-    const bool pos = c->vocab_size > 0 && c->hidden_dim > 0 && c->mel_channels > 0 &&
-                     c->text_encoder_layers >= 0 && c->decoder_layers >= 0 && c->num_heads > 0 &&
-                     c->vocoder_channels >= 16 && c->max_positions > 0;
-    return pos && c->hidden_dim % c->num_heads == 0 && c->vocoder_channels % 16 == 0;
-}
-
 }  // namespace m2
-
-// ---------------------------------------------------------------------------
-struct m2_layer_w {
-    const float *qkv_w, *out_w, *out_b, *ff1_w, *ff1_b, *ff2_w, *ff2_b, *n1_w, *n1_b, *n2_w, *n2_b;
-    // B-fragment packs for the fused layer kernels (transformer_fused.hip)
-    const float *qkv_p = nullptr, *out_p = nullptr, *ff1_p = nullptr, *ff2_p = nullptr;
-    // the layer's attention scores (log2 units, scale folded) may leave the
-    // f16 range: its one-launch form keeps the softmax base in f32 (TflLayer)
-    bool wide_scores = false;
-};
-
-struct m2_model {
-    m2_config cfg{};
-    float* buf = nullptr;
-    std::vector<const float*> ptr;  // per weight-table entry (nullptr for int64 entries)
-    std::vector<m2_layer_w> enc, dec;
-    const float *emb = nullptr, *pe = nullptr, *enc_nw = nullptr, *enc_nb = nullptr;
-    const float* dur[10] = {};  // w1,b1,alpha1,beta1, w2,b2,alpha2,beta2, proj_w, proj_b
-    // the duration convs' split-f16 fragments, used on the inference path
-    // (fused final LayerNorm) when the static range bound allows (dur_split)
-    const float* dur_split_w[2] = {};
-    bool dur_split = false;
-    const float *dec_nw = nullptr, *dec_nb = nullptr, *mel_w = nullptr, *mel_b = nullptr;
-    const float* mel_p = nullptr;  // packed mel projection (fused path)
-    bool tfused = false;           // transformer layers on ln_gemm + attention + post_attn
-    const float *vin_w = nullptr, *vin_b = nullptr, *vout_w = nullptr, *vout_b = nullptr;
-    const float *up_w[4] = {}, *up_b[4] = {};
-    const float *rb_w1[4] = {}, *rb_b1[4] = {}, *rb_w2[4] = {}, *rb_b2[4] = {};
-    // fused vocoder: packed weights
-    float* vbuf = nullptr;
-    m2::VocW vw{};
-    bool fused = false;
-    // split-f16 vocoder (vocoder_x3.hip): packed hi/lo weights; preferred when supported
-    void* xbuf = nullptr;
-    m2::VocX vx{};
-    bool x3 = false;
-    void* tbuf = nullptr;  // pipelined tail pack (stage1: vx.tp / vx.tpb, stage2: vx.tp2 / vx.tp2b)
-    bool tailp = false;
-    void* mbuf = nullptr;  // pipelined stage1 mid pack (vx.mp / vx.mpb)
-    bool midp = false;
-    bool x3_packed = false;  // split-f16 packs exist (m2_vocoder_select can switch x3 on/off)
-    // streamed vocoder (m2_vocoder_set_chunking): chunks of chunk_frames mel
-    // frames, each computed over a window widened by kVocHalo frames per side
-    int chunk_frames = 0;
-    // split-f16 range: non-finite-audio flag (host-mapped, vx.rflag is its
-    // device address), what a raised flag does (m2_set_range_policy), and the
-    // exact-f32 attention for weights whose q/k/v bound leaves the f16 range
-    int32_t* rflag_host = nullptr;
-    // range policy 1 on the fused vocoders: two device flag words used by
-    // alternate calls (rseq parity) - the split kernels raise the call's word,
-    // the exact-f32 redo kernels run only when it is raised, and the next
-    // call's head kernel zeroes it
-    int* rflag_dev = nullptr;
-    mutable unsigned rseq = 0;
-    // policy 1 on the pipelined tails: the tail's in-launch local redo
-    // instead of the guarded exact-f32 launch (vocoder_redo.h); device copy
-    const m2::VocRedoW* redo_w = nullptr;
-    int range_policy = 0;
-    // one-launch transformer layers: work-queue counters and the launch
-    // sequence whose parity picks their set (one stream per model)
-    unsigned* tflq = nullptr;
-    mutable unsigned tfl_seq = 0;
-    // device-T path: the count kernel's ticket word (after the queue words in
-    // tflq) and the host-mapped [seq, T] pair the back half's first launch
-    // posts (m2_frames_wait)
-    unsigned* cnt_ticket = nullptr;
-    int32_t* fpost_host = nullptr;
-    int32_t* fpost_dev = nullptr;
-    mutable int32_t fpost_seq = 0;
-    bool att_f32 = false;
-    // measurement: per m2_vocoder call, an event pair around each fused kernel
-    mutable std::vector<hipEvent_t> prof_begin, prof_end;  // [call][kernel]
-    mutable int prof_calls = 0;
-    uint32_t prof_mask = ~0u;  // which kernels get an event pair (m2_profile_select)
-    int prof_stride = 1;       // record on every prof_stride-th call (m2_profile_stride)
-    mutable long prof_seen = 0;
-};
 
 using namespace m2;
 
@@ -577,649 +421,7 @@ int32_t m2_abi_version(void) { return M2_ABI_VERSION; }
 
 const char* m2_last_error(void) { return g_last_error.c_str(); }
 
-int32_t m2_weight_count(const m2_config* cfg) {
-    if (!config_ok(cfg)) return fail(M2_E_ARG, "m2_weight_count: invalid config");
-    return (int32_t)weight_table(*cfg).size();
-}
-
-int32_t m2_weight_name(const m2_config* cfg, int32_t index, char* buf, int32_t buflen) {
-    if (!config_ok(cfg) || !buf || buflen <= 0) return fail(M2_E_ARG, "m2_weight_name: bad argument");
-    const auto t = weight_table(*cfg);
-    if (index < 0 || index >= (int32_t)t.size()) return fail(M2_E_ARG, "m2_weight_name: index out of range");
-    const std::string& n = t[index].name;
-    if ((int32_t)n.size() + 1 > buflen) return fail(M2_E_ARG, "m2_weight_name: buffer too small");
-    std::memcpy(buf, n.c_str(), n.size() + 1);
-    return M2_OK;
-}
-
-int64_t m2_weight_numel(const m2_config* cfg, int32_t index) {
-    if (!config_ok(cfg)) return fail(M2_E_ARG, "m2_weight_numel: invalid config");
-    const auto t = weight_table(*cfg);
-    if (index < 0 || index >= (int32_t)t.size()) return fail(M2_E_ARG, "m2_weight_numel: index out of range");
-    return t[index].numel;
-}
-
 void m2_reload_switches(void) { reload_switches(); }
-
-int32_t m2_model_create(const m2_config* cfg, const void* const* weights, int32_t n_weights,
-                        void* stream, m2_model** out) {
-    reload_switches();  // the developer switches of this handle's creation (m2_common.h)
-    M2_CHECK_ARG(config_ok(cfg), "m2_model_create: invalid config");
-    M2_CHECK_ARG(weights && out, "m2_model_create: null argument");
-    const auto table = weight_table(*cfg);
-    if (n_weights != (int32_t)table.size()) return fail(M2_E_WEIGHTS, "m2_model_create: weight count mismatch");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int H = cfg->hidden_dim;
-
-    // Layout: every fp32 weight copied verbatim, then 2x(alpha,beta) for the
-    // BatchNorm inference form; 64-float aligned carves.
-    std::vector<size_t> off(table.size(), 0);
-    size_t total = 0;
-    for (size_t i = 0; i < table.size(); ++i) {
-        if (table[i].is_int64) continue;
-        total = align_up(total, 64);
-        off[i] = total;
-        total += (size_t)table[i].numel;
-        M2_CHECK_ARG(weights[i] != nullptr, "m2_model_create: null weight pointer");
-    }
-    total = align_up(total, 64);
-    const size_t bn_off = total;
-    total += 4 * (size_t)H;
-    total = align_up(total, 64);
-    const size_t dw_off = total;  // duration conv weights, B-fragment order, 2 layers
-    total += 2 * 3 * (size_t)H * H;
-    total = align_up(total, 64);
-    const size_t dws_off = total;  // the same as split-f16 hi/lo fragments (pack_bfrag_split)
-    total += 2 * 3 * (size_t)H * H;
-    total = align_up(total, 64);
-    const size_t tf_off = total;  // fused-layer B-fragment packs: 8H^2 per layer + mel projection
-    const int n_layers = cfg->text_encoder_layers + cfg->decoder_layers;
-    total += (size_t)n_layers * 8 * H * H + (size_t)cfg->mel_channels * H;
-
-    auto* m = new m2_model();
-    m->cfg = *cfg;
-    hipError_t e = hipMalloc(&m->buf, total * sizeof(float));
-    if (e != hipSuccess) { delete m; return hip_status(e, "hipMalloc(model)"); }
-    auto bail = [&](hipError_t err, const char* w) { (void)hipFree(m->buf); delete m; return hip_status(err, w); };
-    for (size_t i = 0; i < table.size(); ++i) {
-        if (table[i].is_int64) continue;
-        e = hipMemcpyAsync(m->buf + off[i], weights[i], table[i].numel * sizeof(float), hipMemcpyDeviceToDevice, st);
-        if (e != hipSuccess) return bail(e, "hipMemcpyAsync(weight)");
-    }
-
-    // name -> index
-    auto idx = [&](const std::string& n) {
-        for (size_t i = 0; i < table.size(); ++i) if (table[i].name == n) return (int)i;
-        return -1;
-    };
-    m->ptr.resize(table.size(), nullptr);
-    for (size_t i = 0; i < table.size(); ++i) if (!table[i].is_int64) m->ptr[i] = m->buf + off[i];
-    auto P = [&](const std::string& n) { return m->ptr[idx(n)]; };
-
-    // BatchNorm1d eval: alpha = gamma / sqrt(var + eps), beta' = beta - mean * alpha
-    // (ATen batch_norm_cpu_collect_linear_and_constant_terms, fp32).
-    std::vector<float> host(4 * (size_t)H), bnw(H), bnb(H), bnm(H), bnv(H);
-    for (int j = 0; j < 2; ++j) {
-        const std::string p = "duration_predictor.predictor.conv_layers." + std::to_string(j) + ".norm.";
-        const float* src[4] = {static_cast<const float*>(weights[idx(p + "weight")]), static_cast<const float*>(weights[idx(p + "bias")]),
-                               static_cast<const float*>(weights[idx(p + "running_mean")]), static_cast<const float*>(weights[idx(p + "running_var")])};
-        float* dst[4] = {bnw.data(), bnb.data(), bnm.data(), bnv.data()};
-        for (int q = 0; q < 4; ++q) {
-            e = hipMemcpyAsync(dst[q], src[q], H * sizeof(float), hipMemcpyDeviceToHost, st);
-            if (e != hipSuccess) return bail(e, "hipMemcpyAsync(bn)");
-        }
-        e = hipStreamSynchronize(st);
-        if (e != hipSuccess) return bail(e, "hipStreamSynchronize");
-        for (int c = 0; c < H; ++c) {
-            const float invstd = 1.0f / std::sqrt(bnv[c] + 1e-5f);
-            const float a = invstd * bnw[c];
-            host[(2 * j) * H + c] = a;
-            host[(2 * j + 1) * H + c] = bnb[c] - bnm[c] * a;
-        }
-    }
-    // Duration convs: W[co][ci][tap] -> GEMM B matrix [co][tap*H + ci] -> B-fragment order
-    // (exact-f32 MFMA) and split-f16 hi/lo fragments (v_mfma_f32_16x16x32_f16).
-    std::vector<float> dpack(2 * 3 * (size_t)H * H), dspack(2 * 3 * (size_t)H * H);
-    bool dsplit = true;
-    double dconv_rows[2] = {0.0, 0.0};  // max over co of sum_{ci, tap} |W[co][ci][tap]|
-    std::vector<float> dconv_bias[2];
-    for (int j = 0; j < 2; ++j) {
-        const std::string n = "duration_predictor.predictor.conv_layers." + std::to_string(j) + ".conv.weight";
-        std::vector<float> w((size_t)3 * H * H), wt((size_t)3 * H * H);
-        e = hipMemcpyAsync(w.data(), weights[idx(n)], w.size() * sizeof(float), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) return bail(e, "hipMemcpyAsync(duration conv)");
-        for (int co = 0; co < H; ++co)
-            for (int ci = 0; ci < H; ++ci)
-                for (int k = 0; k < 3; ++k) wt[(size_t)co * 3 * H + k * H + ci] = w[((size_t)co * H + ci) * 3 + k];
-        const std::vector<float> pk = pack_bfrag(wt.data(), H, 3 * H);
-        std::copy(pk.begin(), pk.end(), dpack.begin() + (size_t)j * 3 * H * H);
-        std::vector<float> pks;
-        if (pack_bfrag_split(wt.data(), H, 3 * H, &pks)) std::copy(pks.begin(), pks.end(), dspack.begin() + (size_t)j * 3 * H * H);
-        else dsplit = false;
-        for (int co = 0; co < H; ++co) {
-            double r = 0.0;
-            for (int k = 0; k < 3 * H; ++k) r += std::fabs((double)wt[(size_t)co * 3 * H + k]);
-            dconv_rows[j] = std::max(dconv_rows[j], r);
-        }
-        dconv_bias[j].resize(H);
-        const std::string nb = "duration_predictor.predictor.conv_layers." + std::to_string(j) + ".conv.bias";
-        e = hipMemcpyAsync(dconv_bias[j].data(), weights[idx(nb)], H * sizeof(float), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) return bail(e, "hipMemcpyAsync(duration conv bias)");
-    }
-    e = hipMemcpyAsync(m->buf + dw_off, dpack.data(), dpack.size() * sizeof(float), hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) return bail(e, "hipMemcpyAsync(duration pack)");
-    e = hipMemcpyAsync(m->buf + dws_off, dspack.data(), dspack.size() * sizeof(float), hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) return bail(e, "hipMemcpyAsync(duration split pack)");
-    // Split-f16 range of the duration convs on the inference path, where their
-    // input is the encoder's final LayerNorm (|LN| <= sqrt(H-1) max|gamma| +
-    // max|beta|) and conv2's input is BN(conv1) after ReLU (<= max|alpha| (row
-    // sum |W1| x that + max|b1|) + max|beta'|): checked once here against half
-    // the f16 range, as the transformer's bound below; outside it (or with a
-    // weight outside the f16 range) the exact-f32 MFMA convs stay.
-    {
-        std::vector<float> g(H), bb(H);
-        e = hipMemcpyAsync(g.data(), weights[idx("text_encoder.norm.weight")], H * sizeof(float), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(bb.data(), weights[idx("text_encoder.norm.bias")], H * sizeof(float), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) return bail(e, "hipMemcpyAsync(encoder norm)");
-        double ga = 0.0, ba = 0.0, b1a = 0.0, a1a = 0.0, c1a = 0.0;
-        for (int c = 0; c < H; ++c) {
-            ga = std::max(ga, (double)std::fabs(g[c]));
-            ba = std::max(ba, (double)std::fabs(bb[c]));
-            b1a = std::max(b1a, (double)std::fabs(dconv_bias[0][c]));
-            a1a = std::max(a1a, (double)std::fabs(host[c]));
-            c1a = std::max(c1a, (double)std::fabs(host[H + c]));
-        }
-        const double x0 = std::sqrt((double)std::max(H - 1, 1)) * ga + ba;
-        const double x1 = a1a * (dconv_rows[0] * x0 + b1a) + c1a;
-        m->dur_split = dsplit && x0 < 32768.0 && x1 < 32768.0;
-    }
-    e = hipMemcpyAsync(m->buf + bn_off, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) return bail(e, "hipMemcpyAsync(bn up)");
-    e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return bail(e, "hipStreamSynchronize");
-
-    m->emb = P("text_encoder.embedding.weight");
-    m->pe = P("text_encoder.pos_encoding.pe");
-    auto layer = [&](const std::string& p) {
-        return m2_layer_w{P(p + ".self_attn.qkv.weight"), P(p + ".self_attn.out_proj.weight"), P(p + ".self_attn.out_proj.bias"),
-                          P(p + ".ffn.linear1.weight"), P(p + ".ffn.linear1.bias"), P(p + ".ffn.linear2.weight"),
-                          P(p + ".ffn.linear2.bias"), P(p + ".norm1.weight"), P(p + ".norm1.bias"),
-                          P(p + ".norm2.weight"), P(p + ".norm2.bias")};
-    };
-    for (int i = 0; i < cfg->text_encoder_layers; ++i) m->enc.push_back(layer("text_encoder.layers." + std::to_string(i)));
-    for (int i = 0; i < cfg->decoder_layers; ++i) m->dec.push_back(layer("decoder.layers." + std::to_string(i)));
-    // Fused transformer layers: pack qkv / out / ffn / mel-projection weights
-    // in B-fragment order (M2_TF_UNFUSED=1 keeps the five-linear layer).
-    m->tfused = tf_fused_supported(H, 3 * H) && tf_fused_supported(H, cfg->mel_channels) &&
-                !sw().tf_unfused;
-    if (m->tfused) {
-        size_t o = tf_off;
-        auto pack_up = [&](const std::string& n, int N, int K, const float** slot) -> hipError_t {
-            std::vector<float> w((size_t)N * K);
-            hipError_t er = hipMemcpyAsync(w.data(), weights[idx(n)], w.size() * sizeof(float), hipMemcpyDeviceToHost, st);
-            if (er == hipSuccess) er = hipStreamSynchronize(st);
-            if (er != hipSuccess) return er;
-            std::vector<float> pk;
-            if (!pack_bfrag_split(w.data(), N, K, &pk)) return hipErrorInvalidValue;  // |w| >= 65504
-            er = hipMemcpyAsync(m->buf + o, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice, st);
-            if (er == hipSuccess) er = hipStreamSynchronize(st);
-            *slot = m->buf + o;
-            o += pk.size();
-            return er;
-        };
-        for (int i = 0; i < n_layers && e == hipSuccess; ++i) {
-            const bool is_enc = i < cfg->text_encoder_layers;
-            m2_layer_w& L = is_enc ? m->enc[i] : m->dec[i - cfg->text_encoder_layers];
-            const std::string p = (is_enc ? "text_encoder.layers." + std::to_string(i)
-                                          : "decoder.layers." + std::to_string(i - cfg->text_encoder_layers));
-            if (e == hipSuccess) e = pack_up(p + ".self_attn.qkv.weight", 3 * H, H, &L.qkv_p);
-            if (e == hipSuccess) e = pack_up(p + ".self_attn.out_proj.weight", H, H, &L.out_p);
-            if (e == hipSuccess) e = pack_up(p + ".ffn.linear1.weight", 2 * H, H, &L.ff1_p);
-            if (e == hipSuccess) e = pack_up(p + ".ffn.linear2.weight", H, 2 * H, &L.ff2_p);
-        }
-        if (e == hipSuccess) e = pack_up("decoder.mel_projection.weight", cfg->mel_channels, H, &m->mel_p);
-        if (e == hipErrorInvalidValue) {  // a weight outside the f16 range: keep the fp32 five-linear layers
-            m->tfused = false;
-            e = hipSuccess;
-        }
-        if (e != hipSuccess) return bail(e, "pack transformer weights");
-    }
-    // Split-f16 range of the transformer.  Its split operands are LayerNorm
-    // outputs (|x^| <= sqrt(H-1) for a normalised row, so |LN| <= sqrt(H-1)
-    // max|gamma| + max|beta|), q/k/v = W_qkv LN1 (<= max row sum |W| x that),
-    // attention outputs (convex combinations of v) and ReLU(FFN1(LN2)) - all
-    // bounded by the weights, so the check is made once, here: past half the
-    // f16 range the layers use the fp32 linears and the exact-f32 attention.
-    {
-        double worst = 0.0;
-        auto host = [&](const std::string& n) {
-            const int i = idx(n);
-            std::vector<float> h((size_t)table[i].numel);
-            hipError_t er = hipMemcpyAsync(h.data(), weights[i], h.size() * sizeof(float), hipMemcpyDeviceToHost, st);
-            if (er == hipSuccess) er = hipStreamSynchronize(st);
-            if (er != hipSuccess) h.assign(h.size(), INFINITY);
-            return h;
-        };
-        auto amax = [](const std::vector<float>& v) {
-            double a = 0.0;
-            for (float x : v) a = std::max(a, (double)std::fabs(x));
-            return a;
-        };
-        auto ln_bound = [&](const std::string& p) {
-            return std::sqrt((double)std::max(H - 1, 1)) * amax(host(p + ".weight")) + amax(host(p + ".bias"));
-        };
-        auto row_sum = [&](const std::string& n, int N, int K) {
-            const std::vector<float> w = host(n);
-            double best = 0.0;
-            for (int r = 0; r < N; ++r) {
-                double s = 0.0;
-                for (int k = 0; k < K; ++k) s += std::fabs(w[(size_t)r * K + k]);
-                best = std::max(best, s);
-            }
-            return best;
-        };
-        // scores in log2 units, |q.k| scale log2(e) <= sum over a head's dims of
-        // |q_d| |k_d| (each bounded by its row sum of |W_qkv| x the LN1 bound)
-        // x scale log2(e): the head_dim-48 wave-specialised attention holds its
-        // softmax base m (<= the largest score) as an f16 hi / lo pair, finite
-        // while |m| < 65520, so a layer whose bound reaches the f16 maximum
-        // runs the f32-base form (m2_layer_w::wide_scores; the seeded stage2
-        // weights bound at ~3.5e4)
-        const int heads = cfg->num_heads, hd = H / std::max(heads, 1);
-        const double sl2 = 1.0 / std::sqrt((double)hd) * 1.4426950408889634;
-        for (int i = 0; i < n_layers; ++i) {
-            const bool is_enc = i < cfg->text_encoder_layers;
-            const std::string p = is_enc ? "text_encoder.layers." + std::to_string(i)
-                                         : "decoder.layers." + std::to_string(i - cfg->text_encoder_layers);
-            const double b1 = ln_bound(p + ".norm1"), b2 = ln_bound(p + ".norm2");
-            const double qkv = row_sum(p + ".self_attn.qkv.weight", 3 * H, H) * b1;
-            {
-                // rows of W_qkv: the reference's reshape (3, heads, head_dim)
-                const std::vector<float> w = host(p + ".self_attn.qkv.weight");
-                auto rs = [&](int r) {
-                    double a = 0.0;
-                    for (int k = 0; k < H; ++k) a += std::fabs(w[(size_t)r * H + k]);
-                    return a * b1;
-                };
-                double sb = 0.0;
-                for (int h = 0; h < heads; ++h) {
-                    double acc = 0.0;
-                    for (int d = 0; d < hd; ++d) acc += rs(h * hd + d) * rs(H + h * hd + d);
-                    sb = std::max(sb, acc * sl2);
-                }
-                m2_layer_w& L = is_enc ? m->enc[i] : m->dec[i - cfg->text_encoder_layers];
-                L.wide_scores = !(sb < 65504.0);
-            }
-            const double hid = row_sum(p + ".ffn.linear1.weight", 2 * H, H) * b2 + amax(host(p + ".ffn.linear1.bias"));
-            worst = std::max(worst, std::max(std::max(b1, b2), std::max(qkv, hid)));
-        }
-        if (cfg->decoder_layers > 0) worst = std::max(worst, ln_bound("decoder.norm"));
-        if (!(worst < 32768.0)) {
-            m->tfused = false;
-            m->att_f32 = true;
-        }
-    }
-    m->enc_nw = P("text_encoder.norm.weight");
-    m->enc_nb = P("text_encoder.norm.bias");
-    for (int j = 0; j < 2; ++j) {
-        const std::string p = "duration_predictor.predictor.conv_layers." + std::to_string(j) + ".conv.";
-        m->dur[4 * j + 0] = m->buf + dw_off + (size_t)j * 3 * H * H;
-        m->dur[4 * j + 1] = P(p + "bias");
-        m->dur[4 * j + 2] = m->buf + bn_off + (2 * j) * H;
-        m->dur[4 * j + 3] = m->buf + bn_off + (2 * j + 1) * H;
-    }
-    m->dur_split_w[0] = m->buf + dws_off;
-    m->dur_split_w[1] = m->buf + dws_off + (size_t)3 * H * H;
-    m->dur[8] = P("duration_predictor.predictor.projection.weight");
-    m->dur[9] = P("duration_predictor.predictor.projection.bias");
-    m->dec_nw = P("decoder.norm.weight");
-    m->dec_nb = P("decoder.norm.bias");
-    m->mel_w = P("decoder.mel_projection.weight");
-    m->mel_b = P("decoder.mel_projection.bias");
-    m->vin_w = P("vocoder.input_conv.weight");
-    m->vin_b = P("vocoder.input_conv.bias");
-    for (int k = 0; k < 4; ++k) {
-        const std::string u = "vocoder.upsamples." + std::to_string(k);
-        const std::string r = "vocoder.resblocks." + std::to_string(k);
-        m->up_w[k] = P(u + ".weight");
-        m->up_b[k] = P(u + ".bias");
-        m->rb_w1[k] = P(r + ".conv1.weight");
-        m->rb_b1[k] = P(r + ".conv1.bias");
-        m->rb_w2[k] = P(r + ".conv2.weight");
-        m->rb_b2[k] = P(r + ".conv2.bias");
-    }
-    m->vout_w = P("vocoder.output_conv.weight");
-    m->vout_b = P("vocoder.output_conv.bias");
-
-    // Fused vocoder: pack conv / convT weights into MFMA A-fragment order.
-    m->fused = vocoder_fused_supported(cfg->mel_channels, cfg->vocoder_channels) && !sw().voc_perlayer;
-    if (m->fused) {
-        auto fetch = [&](const std::string& n) {
-            const int i = idx(n);
-            std::vector<float> h((size_t)table[i].numel);
-            hipError_t er = hipMemcpyAsync(h.data(), weights[i], h.size() * sizeof(float), hipMemcpyDeviceToHost, st);
-            if (er == hipSuccess) er = hipStreamSynchronize(st);
-            if (er != hipSuccess) h.clear();
-            return h;
-        };
-        std::vector<std::vector<float>> parts;
-        std::vector<const float**> slots;
-        auto add = [&](std::vector<float> v, const float** slot) { parts.push_back(std::move(v)); slots.push_back(slot); };
-        const int M = cfg->mel_channels, C = cfg->vocoder_channels;
-        auto wi = fetch("vocoder.input_conv.weight");
-        if (wi.empty()) return bail(hipErrorUnknown, "fetch vocoder weights");
-        add(pack_conv3(wi.data(), C, M), &m->vw.wi);
-        add(fetch("vocoder.input_conv.bias"), &m->vw.bi);
-        int ch = C;
-        for (int k = 0; k < 4; ++k) {
-            const std::string u = "vocoder.upsamples." + std::to_string(k);
-            const std::string r = "vocoder.resblocks." + std::to_string(k);
-            auto wt = fetch(u + ".weight");
-            add(pack_convT(wt.data(), ch, ch / 2, kRates[k]), &m->vw.wt[k]);
-            add(fetch(u + ".bias"), &m->vw.bt[k]);
-            ch /= 2;
-            auto w1 = fetch(r + ".conv1.weight");
-            add(pack_conv3(w1.data(), ch, ch), &m->vw.w1[k]);
-            add(fetch(r + ".conv1.bias"), &m->vw.b1[k]);
-            auto w2 = fetch(r + ".conv2.weight");
-            add(pack_conv3(w2.data(), ch, ch), &m->vw.w2[k]);
-            add(fetch(r + ".conv2.bias"), &m->vw.b2[k]);
-            if (k == 3 && ch == 8 && kRates[3] == 2) {  // the two-phase forms of the last stage
-                add(pack_convT2_paired(wt.data(), 2 * ch), &m->vw.wt4p);
-                add(pack_conv3_2p(w1.data()), &m->vw.w1p);
-                add(pack_conv3_2p(w2.data()), &m->vw.w2p);
-            }
-        }
-        if ((M == 64 && C == 128) || (M == 80 && C == 256)) {  // the exact-f32 head's composed input conv o ConvT1
-            std::vector<uint16_t> hw_unused;
-            std::vector<float> hb, he;
-            bool hok = true;
-            const auto bi = fetch("vocoder.input_conv.bias"), wt0 = fetch("vocoder.upsamples.0.weight"),
-                       bt0 = fetch("vocoder.upsamples.0.bias");
-            if (pack_x3_head_comp(wi.data(), bi.data(), wt0.data(), bt0.data(), M, M, C, &hw_unused, &hb, &he, &hok)) {
-                add(pack_f32_head_comp(wi.data(), wt0.data(), M, C), &m->vw.hcw);
-                add(std::move(hb), &m->vw.hcb);
-                add(std::move(he), &m->vw.hce);
-            }
-        }
-        size_t tot = 0;
-        std::vector<size_t> offs;
-        for (auto& v : parts) { tot = align_up(tot, 64); offs.push_back(tot); tot += v.size(); }
-        std::vector<float> host(tot, 0.f);
-        for (size_t i = 0; i < parts.size(); ++i) std::copy(parts[i].begin(), parts[i].end(), host.begin() + offs[i]);
-        e = hipMalloc(&m->vbuf, std::max<size_t>(tot, 1) * sizeof(float));
-        if (e != hipSuccess) return bail(e, "hipMalloc(vocoder pack)");
-        e = hipMemcpyAsync(m->vbuf, host.data(), tot * sizeof(float), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) { (void)hipFree(m->vbuf); return bail(e, "upload vocoder pack"); }
-        for (size_t i = 0; i < parts.size(); ++i) *slots[i] = m->vbuf + offs[i];
-        m->vw.wo = m->vout_w;
-        m->vw.bo = m->vout_b;
-
-        // Split-f16 packs (default path when the shapes are supported and every
-        // weight is inside the f16 range; M2_VOC_F32=1 keeps the exact-f32 MFMA).
-        if (vocoder_x3_supported(M, C) && !sw().voc_f32) {
-            bool ok = true;
-            std::vector<std::vector<uint16_t>> xp;
-            std::vector<const vx_u32x4**> xs;
-            xp.push_back(pack_x3_conv3(wi.data(), C, M, vocoder_x3_mel_pad(M), &ok, false));
-            xs.push_back(&m->vx.wi);
-            int c2 = C;
-            for (int k = 0; k < 4; ++k) {
-                const std::string u = "vocoder.upsamples." + std::to_string(k);
-                const std::string r = "vocoder.resblocks." + std::to_string(k);
-                auto wt = fetch(u + ".weight");
-                xp.push_back(pack_x3_convT(wt.data(), c2, c2 / 2, kRates[k], &ok));
-                xs.push_back(&m->vx.wt[k]);
-                c2 /= 2;
-                auto w1 = fetch(r + ".conv1.weight");
-                xp.push_back(pack_x3_conv3(w1.data(), c2, c2, c2, &ok, false));
-                xs.push_back(&m->vx.w1[k]);
-                auto w2 = fetch(r + ".conv2.weight");
-                xp.push_back(pack_x3_conv3(w2.data(), c2, c2, c2, &ok, true));
-                xs.push_back(&m->vx.w2[k]);
-            }
-            // stage1 head: input_conv composed into ConvT1 (fp32 bias / edge
-            // tables ride in the same buffer as u16 pairs)
-            const vx_u32x4* hcb_at = nullptr;
-            const vx_u32x4* hce_at = nullptr;
-            if ((M == 64 && C == 128) || (M == 80 && C == 256)) {
-                std::vector<uint16_t> hw;
-                std::vector<float> hb, he;
-                const auto bi = fetch("vocoder.input_conv.bias"), wt0 = fetch("vocoder.upsamples.0.weight"),
-                           bt0 = fetch("vocoder.upsamples.0.bias");
-                bool hok = true;
-                if (pack_x3_head_comp(wi.data(), bi.data(), wt0.data(), bt0.data(), M, vocoder_x3_mel_pad(M), C, &hw,
-                                      &hb, &he, &hok) && hok) {
-                    auto as_u16 = [](const std::vector<float>& f) {
-                        std::vector<uint16_t> u(f.size() * 2);
-                        std::memcpy(u.data(), f.data(), f.size() * sizeof(float));
-                        return u;
-                    };
-                    xp.push_back(std::move(hw));
-                    xs.push_back(&m->vx.hc);
-                    xp.push_back(as_u16(hb));
-                    xs.push_back(&hcb_at);
-                    xp.push_back(as_u16(he));
-                    xs.push_back(&hce_at);
-                }
-            }
-            if (ok) {
-                size_t xt = 0;
-                std::vector<size_t> xo;
-                for (auto& v : xp) { xt = align_up(xt, 128); xo.push_back(xt); xt += v.size(); }
-                std::vector<uint16_t> hx(xt, 0);
-                for (size_t i = 0; i < xp.size(); ++i) std::copy(xp[i].begin(), xp[i].end(), hx.begin() + xo[i]);
-                e = hipMalloc(&m->xbuf, std::max<size_t>(xt, 1) * sizeof(uint16_t));
-                if (e != hipSuccess) { (void)hipFree(m->vbuf); return bail(e, "hipMalloc(x3 pack)"); }
-                e = hipMemcpyAsync(m->xbuf, hx.data(), xt * sizeof(uint16_t), hipMemcpyHostToDevice, st);
-                if (e == hipSuccess) e = hipStreamSynchronize(st);
-                if (e != hipSuccess) { (void)hipFree(m->vbuf); (void)hipFree(m->xbuf); return bail(e, "upload x3 pack"); }
-                for (size_t i = 0; i < xp.size(); ++i)
-                    *xs[i] = reinterpret_cast<const vx_u32x4*>(static_cast<uint16_t*>(m->xbuf) + xo[i]);
-                m->vx.hcb = reinterpret_cast<const float*>(hcb_at);
-                m->vx.hce = reinterpret_cast<const float*>(hce_at);
-                m->vx.bi = m->vw.bi;
-                for (int k = 0; k < 4; ++k) {
-                    m->vx.bt[k] = m->vw.bt[k];
-                    m->vx.b1[k] = m->vw.b1[k];
-                    m->vx.b2[k] = m->vw.b2[k];
-                }
-                m->vx.wo = m->vw.wo;
-                m->vx.bo = m->vw.bo;
-                m->x3 = true;
-                m->x3_packed = true;
-                // stage1 / stage2: the last two upsampling stages as one
-                // pipelined kernel (M2_VOC_TAIL_X3=1 keeps the x3 tail kernel).
-                const bool s2tail = M == 80 && C == 256;
-                if (((M == 64 && C == 128) || s2tail) && !sw().voc_tail_x3) {
-                    const char* names[14] = {
-                        "vocoder.upsamples.2.weight",         "vocoder.upsamples.2.bias",
-                        "vocoder.resblocks.2.conv1.weight", "vocoder.resblocks.2.conv1.bias",
-                        "vocoder.resblocks.2.conv2.weight", "vocoder.resblocks.2.conv2.bias",
-                        "vocoder.upsamples.3.weight",         "vocoder.upsamples.3.bias",
-                        "vocoder.resblocks.3.conv1.weight", "vocoder.resblocks.3.conv1.bias",
-                        "vocoder.resblocks.3.conv2.weight", "vocoder.resblocks.3.conv2.bias",
-                        "vocoder.output_conv.weight",         "vocoder.output_conv.bias"};
-                    std::vector<float> hw[14];
-                    bool got = true;
-                    for (int i = 0; i < 14; ++i) got = got && !(hw[i] = fetch(names[i])).empty();
-                    const TailpSrc src{hw[0].data(), hw[1].data(), hw[2].data(),  hw[3].data(),  hw[4].data(),
-                                       hw[5].data(), hw[6].data(), hw[7].data(),  hw[8].data(),  hw[9].data(),
-                                       hw[10].data(), hw[11].data(), hw[12].data(), hw[13].data()};
-                    std::vector<uint16_t> pw;
-                    std::vector<float> pb;
-                    bool rok = true;
-                    if (got && (s2tail ? pack_tailp2(src, &pw, &pb, &rok) : pack_tailp(src, &pw, &pb, &rok)) && rok) {
-                        const size_t wb = pw.size() * sizeof(uint16_t);
-                        e = hipMalloc(&m->tbuf, wb + pb.size() * sizeof(float));
-                        if (e == hipSuccess) e = hipMemcpyAsync(m->tbuf, pw.data(), wb, hipMemcpyHostToDevice, st);
-                        if (e == hipSuccess)
-                            e = hipMemcpyAsync(static_cast<char*>(m->tbuf) + wb, pb.data(), pb.size() * sizeof(float),
-                                               hipMemcpyHostToDevice, st);
-                        if (e == hipSuccess) e = hipStreamSynchronize(st);
-                        if (e != hipSuccess) {
-                            (void)hipFree(m->vbuf);
-                            (void)hipFree(m->xbuf);
-                            if (m->tbuf) (void)hipFree(m->tbuf);
-                            return bail(e, "upload tailp pack");
-                        }
-                        const auto* tw = static_cast<const vx_u32x4*>(m->tbuf);
-                        const auto* tb = reinterpret_cast<const float*>(static_cast<char*>(m->tbuf) + wb);
-                        if (s2tail) {
-                            m->vx.tp2 = tw;
-                            m->vx.tp2b = tb;
-                        } else {
-                            m->vx.tp = tw;
-                            m->vx.tpb = tb;
-                        }
-                        m->tailp = true;
-                    }
-                }
-                // stage1: the second upsampling stage as one pipelined kernel
-                // (M2_VOC_MID_X3=1 keeps the x3 mid kernel).
-                if (M == 64 && C == 128 && !sw().voc_mid_x3) {
-                    const char* names[6] = {"vocoder.upsamples.1.weight",         "vocoder.upsamples.1.bias",
-                                            "vocoder.resblocks.1.conv1.weight", "vocoder.resblocks.1.conv1.bias",
-                                            "vocoder.resblocks.1.conv2.weight", "vocoder.resblocks.1.conv2.bias"};
-                    std::vector<float> hw[6];
-                    bool got = true;
-                    for (int i = 0; i < 6; ++i) got = got && !(hw[i] = fetch(names[i])).empty();
-                    const MidpSrc src{hw[0].data(), hw[1].data(), hw[2].data(), hw[3].data(), hw[4].data(), hw[5].data()};
-                    std::vector<uint16_t> pw;
-                    std::vector<float> pb;
-                    bool rok = true;
-                    if (got && pack_midp(src, &pw, &pb, &rok) && rok) {
-                        const size_t wb = pw.size() * sizeof(uint16_t);
-                        e = hipMalloc(&m->mbuf, wb + pb.size() * sizeof(float));
-                        if (e == hipSuccess) e = hipMemcpyAsync(m->mbuf, pw.data(), wb, hipMemcpyHostToDevice, st);
-                        if (e == hipSuccess)
-                            e = hipMemcpyAsync(static_cast<char*>(m->mbuf) + wb, pb.data(), pb.size() * sizeof(float),
-                                               hipMemcpyHostToDevice, st);
-                        if (e == hipSuccess) e = hipStreamSynchronize(st);
-                        if (e != hipSuccess) {
-                            (void)hipFree(m->vbuf);
-                            (void)hipFree(m->xbuf);
-                            if (m->tbuf) (void)hipFree(m->tbuf);
-                            if (m->mbuf) (void)hipFree(m->mbuf);
-                            return bail(e, "upload midp pack");
-                        }
-                        m->vx.mp = static_cast<const vx_u32x4*>(m->mbuf);
-                        m->vx.mpb = reinterpret_cast<const float*>(static_cast<char*>(m->mbuf) + wb);
-                        m->midp = true;
-                    }
-                }
-            }
-        }
-    }
-    // the split path's non-finite-audio flag, host-mapped so the host can read
-    // it without a copy (m2_model_check, the M2_E_RANGE check on entry)
-    {
-        void* h = nullptr;
-        void* d = nullptr;
-        e = hipHostMalloc(&h, 64, hipHostMallocMapped | hipHostMallocCoherent);
-        if (e == hipSuccess) e = hipHostGetDevicePointer(&d, h, 0);
-        if (e != hipSuccess) {
-            if (h) (void)hipHostFree(h);
-            m2_model_destroy(m);
-            return hip_status(e, "hipHostMalloc(range flag)");
-        }
-        std::memset(h, 0, 64);
-        m->rflag_host = static_cast<int32_t*>(h);
-        m->vx.rflag = static_cast<int*>(d);
-        void* dv = nullptr;
-        e = hipMalloc(&dv, 64);
-        if (e == hipSuccess) e = hipMemsetAsync(dv, 0, 64, st);
-        if (e != hipSuccess) {
-            if (dv) (void)hipFree(dv);
-            m2_model_destroy(m);
-            return hip_status(e, "hipMalloc(range flags)");
-        }
-        m->rflag_dev = static_cast<int*>(dv);
-    }
-    // the local redo's weight table (range policy "fallback" on the pipelined
-    // tails, vocoder_redo.h): the raw fp32 vocoder weights, one device copy
-    if (m->vx.tp || m->vx.tp2) {
-        VocRedoW rw;
-        rw.M = cfg->mel_channels;
-        rw.C = cfg->vocoder_channels;
-        rw.wi = m->vin_w;
-        rw.bi = m->vin_b;
-        for (int k = 0; k < 4; ++k) {
-            rw.wt[k] = m->up_w[k];
-            rw.bt[k] = m->up_b[k];
-            rw.w1[k] = m->rb_w1[k];
-            rw.b1[k] = m->rb_b1[k];
-            rw.w2[k] = m->rb_w2[k];
-            rw.b2[k] = m->rb_b2[k];
-        }
-        rw.wo = m->vout_w;
-        rw.bo = m->vout_b;
-        void* dv = nullptr;
-        e = hipMalloc(&dv, sizeof(VocRedoW));
-        if (e == hipSuccess) e = hipMemcpyAsync(dv, &rw, sizeof(VocRedoW), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) {
-            if (dv) (void)hipFree(dv);
-            m2_model_destroy(m);
-            return hip_status(e, "hipMalloc(redo weights)");
-        }
-        m->redo_w = static_cast<const VocRedoW*>(dv);
-    }
-    // work-queue counters of the one-launch transformer layers (TflQueue)
-    // (+ 16 words: the count kernel's ticket of the device-T front half)
-    e = hipMalloc(&m->tflq, (kTflQueueWords + 16) * sizeof(unsigned));
-    if (e == hipSuccess) e = hipMemsetAsync(m->tflq, 0, (kTflQueueWords + 16) * sizeof(unsigned), st);
-    if (e == hipSuccess) m->cnt_ticket = m->tflq + kTflQueueWords;
-    if (e == hipSuccess) {
-        void* h = nullptr;
-        e = hipHostMalloc(&h, 64, hipHostMallocMapped | hipHostMallocCoherent | hipHostMallocPortable);
-        if (e == hipSuccess) {
-            std::memset(h, 0, 64);
-            m->fpost_host = static_cast<int32_t*>(h);
-            void* d = nullptr;
-            e = hipHostGetDevicePointer(&d, h, 0);
-            m->fpost_dev = static_cast<int32_t*>(d);
-        }
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        m2_model_destroy(m);
-        return hip_status(e, "hipMalloc(tfl queue)");
-    }
-    *out = m;
-    return M2_OK;
-}
-
-int32_t m2_profile_disable(m2_model* model);
-
-int32_t m2_model_destroy(m2_model* model) {
-    if (!model) return M2_OK;
-    m2_profile_disable(model);
-    if (model->vbuf) (void)hipFree(model->vbuf);
-    if (model->xbuf) (void)hipFree(model->xbuf);
-    if (model->tbuf) (void)hipFree(model->tbuf);
-    if (model->mbuf) (void)hipFree(model->mbuf);
-    if (model->rflag_host) (void)hipHostFree(model->rflag_host);
-    if (model->rflag_dev) (void)hipFree(model->rflag_dev);
-    if (model->tflq) (void)hipFree(model->tflq);
-    if (model->fpost_host) (void)hipHostFree(model->fpost_host);
-    if (model->redo_w) (void)hipFree(const_cast<VocRedoW*>(model->redo_w));
-    hipError_t e = hipFree(model->buf);
-    delete model;
-    if (e != hipSuccess) return hip_status(e, "hipFree(model)");
-    return M2_OK;
-}
-
-int32_t m2_model_config(const m2_model* model, m2_config* out) {
-    M2_CHECK_ARG(model && out, "m2_model_config: null argument");
-    *out = model->cfg;
-    return M2_OK;
-}
 
 size_t m2_workspace_bytes(const m2_model* model, int32_t B, int32_t S, int32_t T) {
     if (!model || B < 0 || S < 0 || T < 0) return 0;

@@ -220,6 +220,53 @@ def test_transformer_range_bound_selects_f32(gpu):
     assert rms(audio, ref_audio) <= AUDIO_RMS_TOL
 
 
+def _huge_weight_transformer(sd):
+    sd["text_encoder.layers.0.ffn.linear1.weight"][0, 0] = 7e4
+    sd["text_encoder.layers.0.ffn.linear2.weight"][:, 0] = 0
+
+
+def _huge_weight_duration(sd):
+    p = "duration_predictor.predictor.conv_layers."
+    sd[p + "0.conv.weight"][0, 0, 0] = 7e4
+    sd[p + "1.conv.weight"][:, 0, :] = 0
+
+
+def _huge_weight_vocoder(sd):
+    sd["vocoder.resblocks.3.conv1.weight"][0, 0, 0] = 7e4
+    sd["vocoder.resblocks.3.conv2.weight"][:, 0, :] = 0
+
+
+@pytest.mark.parametrize("stage", ["s1", "s2"])
+@pytest.mark.parametrize("unit", ["transformer", "duration", "vocoder"])
+def test_weight_outside_f16_range_selects_f32(gpu, stage, unit):
+    """One weight of 7e4 (outside the f16 range) on a unit whose consumer
+    column is zero, so it contributes exactly nothing: the split-f16 pack of
+    that family reports the weight, creation succeeds on the family's fp32
+    kernels and the result is the oracle's."""
+    from m2amd import _lib
+    from test_gpu_tailp import kernel_names
+    lib = _lib.load()
+    sd = {k: v.clone() for k, v in golden_state(stage).items()}
+    {"transformer": _huge_weight_transformer, "duration": _huge_weight_duration,
+     "vocoder": _huge_weight_vocoder}[unit](sd)
+    m = build_model(stage, gpu, sd)
+    hip = m._hip(gpu)
+    if unit == "transformer":
+        assert lib.m2_transformer_path(hip.handle) == 0
+    elif unit == "duration":
+        assert lib.m2_transformer_path(hip.handle) == 1
+    else:
+        assert hip.vocoder_path() == 1
+        assert not any(n.startswith(("tailp", "midp")) for n in kernel_names(m, gpu))
+    g = golden(f"{stage}_small")
+    ids, lens = torch.from_numpy(g["ids"]), torch.from_numpy(g["lengths"])
+    mel, audio = m.inference(ids.to(gpu), lens.to(gpu))
+    ref_mel, ref_audio = orc.inference(sd, stage_config(stage), ids, lens, as_written=False)
+    assert mel.shape == ref_mel.shape
+    assert maxabs(mel, ref_mel) <= MEL_MAXABS_TOL
+    assert rms(audio, ref_audio) <= AUDIO_RMS_TOL
+
+
 @pytest.mark.parametrize("stage", ["s1", "s2"])
 @pytest.mark.parametrize("scale", [0.3, 10.0])
 @pytest.mark.parametrize("rb,form", [("1", "auto"), ("2", "auto"), ("4", "auto"), ("4", "3"), ("4", "4"),
