@@ -381,6 +381,55 @@ int32_t m2_griffin_lim(const m2_dsp* dsp, const float* mel, const float* mag, co
                        int32_t B, int32_t T, int32_t n_iter, float momentum, int32_t nnls_iters,
                        float* out_audio, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- evaluation metrics (src/evaluation/metrics.py) -------------------------
+ * Per-utterance rows of double sums; the scalar finishing of the reference's
+ * metrics (log10, clips, MOS weights, correlation) is the caller's.  Columns
+ * are named: m2_eval_column_count(kind) / m2_eval_column_name(kind, i), kind
+ * 0 = m2_eval_audio, 1 = m2_eval_pair_stats, 2 = m2_eval_mcd.  All reductions
+ * run in a fixed order, so equal inputs give equal bits.
+ *
+ * m2_eval_audio: estimate_mos_score's sums (metrics.py:79-148, with
+ * compute_spectral_convergence and compute_log_spectral_distance, :27-58) for
+ * pred [B, Lp] and target [B, Lt] (NULL: reference-free), STFT n_fft / hop /
+ * window / sample rate of `dsp`.  With L = min(Lp, Lt) and X(.) the STFT of
+ * the first L samples (1 + L / hop frames):
+ *   spec_err_sq  sum (|X(target)| - |X(pred)|)^2     spec_ref_sq  sum |X(target)|^2
+ *   log_spec_sq  sum (ln(|X(pred)| + 1e-8) - ln(|X(target)| + 1e-8))^2
+ *   pair_bins    their count, (1 + L / hop) (n_fft / 2 + 1)
+ *   target_sq, noise_sq   sum target^2, sum (pred - target)^2 over [0, L); pair_len = L
+ *   pred_sq, sign_changes sum pred^2 and sum |sign(x[i+1]) - sign(x[i])| over
+ *                the whole pred (sign(0) = 0); pred_len = Lp
+ *   centroid_sum, bandwidth_sum  sums over the whole pred's pred_frames =
+ *                1 + Lp / hop frames of librosa's spectral_centroid and
+ *                spectral_bandwidth (p = 2) of the magnitude spectrum
+ * The columns that need a target are 0 without one.  B <= 65535.
+ *
+ * m2_eval_pair_stats: target [B, R, C]; pred [B, R, C], or [B, C, R] read
+ * transposed (the model's mel [B, T, M] against a target [B, M, T]); cols
+ * (int32 [B] or NULL) keeps each utterance's first min(cols[b], C) columns
+ * (metrics.py:244-248).  Per utterance abs_diff = sum |p - t|, sq_diff,
+ * sum_p, sum_t, sum_pp, sum_tt, sum_pt, count, and the centred second moments
+ * cen_pp = sum (p - mean p)^2, cen_tt, cen_pt (a constant row gives exactly 0).
+ * compute_mel_distance (:15-24) and compute_duration_accuracy (:151-177, R = 1).
+ *
+ * m2_eval_mcd: compute_mcd (:61-76): target [B, M, Tt]; pred [B, M, Tp] or
+ * [B, Tp, M]; over the first min(Tp, Tt, cols[b]) frames, mcd_sum = sum of
+ * sqrt(sum_c (D (pred - target))_c^2) with D = `table`, device doubles
+ * [m2_eval_mcd_coefficients() = 13, M]: the first rows of the orthonormal
+ * DCT-II (librosa.feature.mfcc(S=., n_mfcc=13) takes no dB step), which
+ * m2_eval_dct_table writes to HOST memory for the caller to upload. */
+int32_t m2_eval_column_count(int32_t kind);
+const char* m2_eval_column_name(int32_t kind, int32_t index);
+size_t m2_eval_audio_workspace_bytes(const m2_dsp* dsp, int32_t B, int32_t Lp);
+int32_t m2_eval_audio(const m2_dsp* dsp, const float* pred, const float* target, int32_t B, int32_t Lp,
+                      int32_t Lt, double* out, void* workspace, size_t workspace_bytes, void* stream);
+int32_t m2_eval_pair_stats(const float* pred, const float* target, const int32_t* cols, int32_t B, int32_t R,
+                           int32_t C, int32_t pred_transposed, double* out, void* stream);
+int32_t m2_eval_mcd_coefficients(void);
+int32_t m2_eval_dct_table(int32_t n_mels, double* out_host);
+int32_t m2_eval_mcd(const float* pred, const float* target, const int32_t* cols, const double* table, int32_t B,
+                    int32_t n_mels, int32_t Tp, int32_t Tt, int32_t pred_transposed, double* out, void* stream);
+
 /* ---- measurement ----------------------------------------------------------
  * Kernel timing with HIP events recorded on the launch stream around each of
  * the fused vocoder's kernels (bench.py's roofline).  enable: allocate event

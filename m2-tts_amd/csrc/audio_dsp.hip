@@ -24,51 +24,10 @@
 #include <cstring>
 #include <vector>
 
-#include "m2_common.h"
+#include "audio_dsp.h"
 
 namespace m2 {
 namespace dsp {
-
-constexpr int NT = 256;  // threads per frame workgroup
-
-__device__ __forceinline__ float2 cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-
-// In-LDS radix-2 Stockham FFT of N points (natural order in and out),
-// a -> result in a or b (returned).  tw[k] = exp(-2 pi i k / N), k < N/2;
-// INV: conjugated twiddles (unnormalised inverse).
-template <int N, bool INV>
-__device__ float2* fft_lds(float2* a, float2* b, const float2* __restrict__ tw) {
-    float2* x = a;
-    float2* y = b;
-    for (int ns = 1; ns < N; ns <<= 1) {
-        for (int j = threadIdx.x; j < N / 2; j += NT) {
-            const int k = j & (ns - 1);
-            float2 w = tw[k * (N / (2 * ns))];
-            if (INV) w.y = -w.y;
-            const float2 u = x[j], v = cmul(x[j + N / 2], w);
-            const int o = ((j - k) << 1) + k;
-            y[o] = make_float2(u.x + v.x, u.y + v.y);
-            y[o + ns] = make_float2(u.x - v.x, u.y - v.y);
-        }
-        __syncthreads();
-        float2* t = x;
-        x = y;
-        y = t;
-    }
-    return x;
-}
-
-// Frame t of utterance b: samples t*hop - N/2 + n (centre padding, zero
-// outside [0, L)) times the window, into LDS as complex.
-template <int N>
-__device__ void load_frame(const float* __restrict__ y, int L, int hop, int t, const float* __restrict__ win, float2* a) {
-    const int s0 = t * hop - N / 2;
-    for (int n = threadIdx.x; n < N; n += NT) {
-        const int i = s0 + n;
-        a[n] = make_float2((i >= 0 && i < L) ? y[i] * win[n] : 0.f, 0.f);
-    }
-    __syncthreads();
-}
 
 // STFT to power, mel filters: mel[b, m, t] = sum_f W[m, f] |X_t[f]|^2
 // (band m covers bins [lo[m], hi[m])).  Or the complex spectrum
@@ -344,17 +303,8 @@ __global__ __launch_bounds__(1024) void peak_norm_kernel(float* __restrict__ y, 
 
 // ---------------------------------------------------------------------------
 // Host side: the per-configuration tables (window, twiddles, mel filters and
-// their pseudo-inverse) live in one device allocation owned by m2_dsp.
-struct m2_dsp {
-    int sr, n_fft, hop, win_length, n_mels;
-    float fmin, fmax;
-    float* buf = nullptr;
-    float *win, *W, *Wp;
-    float2* tw;
-    int *lo, *hi;
-    float step;  // NNLS gradient step 1 / ||W||_2^2
-};
-
+// their pseudo-inverse) live in one device allocation owned by m2_dsp
+// (audio_dsp.h).
 namespace {
 using namespace m2;
 

@@ -82,6 +82,14 @@ _SIGNATURES = {
     "m2_mel_to_magnitude_workspace_bytes": (c_size, [c_vp, c_i32, c_i32]),
     "m2_mel_to_magnitude": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_size, c_vp]),
     "m2_griffin_lim": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_f32, c_i32, c_vp, c_vp, c_size, c_vp]),
+    "m2_eval_column_count": (c_i32, [c_i32]),
+    "m2_eval_column_name": (ctypes.c_char_p, [c_i32, c_i32]),
+    "m2_eval_audio_workspace_bytes": (c_size, [c_vp, c_i32, c_i32]),
+    "m2_eval_audio": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_size, c_vp]),
+    "m2_eval_pair_stats": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    "m2_eval_mcd_coefficients": (c_i32, []),
+    "m2_eval_dct_table": (c_i32, [c_i32, ctypes.POINTER(ctypes.c_double)]),
+    "m2_eval_mcd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "m2_transformer_path": (c_i32, [c_vp]),
     "m2_front_bytes": (c_size, [c_vp, c_i32, c_i32]),
     "m2_inference_workspace_bytes": (c_size, [c_vp, c_i32, c_i32, c_i32]),

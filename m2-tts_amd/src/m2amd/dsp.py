@@ -117,6 +117,24 @@ class Dsp:
                   int(nnls_iters), out.data_ptr(), self._ws.data_ptr(), self._ws.numel(), stream_handle(src.device))
         return out
 
+    def eval_audio(self, pred: Tensor, target: Optional[Tensor] = None) -> Tensor:
+        """The sums behind estimate_mos_score (metrics.py:79-148) for pred [B, Lp]
+        and target [B, Lt] (None: reference-free) -> float64 [B, K] on the
+        device, columns ``eval_columns("audio")`` (m2_eval_audio)."""
+        y = self._audio(pred)
+        B, Lp = y.shape
+        q = None
+        if target is not None:
+            q = self._audio(target)
+            if q.shape[0] != B:
+                raise ValueError(f"eval_audio: {B} predictions, {q.shape[0]} targets")
+        out = torch.empty(B, len(eval_columns("audio")), device=y.device, dtype=torch.float64)
+        need = int(_lib.load().m2_eval_audio_workspace_bytes(self.handle, B, Lp))
+        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=y.device)
+        _lib.call("m2_eval_audio", self.handle, y.data_ptr(), None if q is None else q.data_ptr(), B, Lp,
+                  0 if q is None else q.shape[1], out.data_ptr(), ws.data_ptr(), ws.numel(), stream_handle(y.device))
+        return out
+
 
 _CACHE: Dict[Tuple, Dsp] = {}
 
@@ -129,3 +147,68 @@ def get_dsp(sample_rate=22050, n_fft=1024, hop_length=256, win_length=1024, n_me
     if d is None:
         d = _CACHE[key] = Dsp(sample_rate, n_fft, hop_length, win_length, n_mels, fmin, fmax, dev)
     return d
+
+
+_EVAL_KINDS = {"audio": 0, "pair": 1, "mcd": 2}
+_EVAL_COLUMNS: Dict[str, Tuple[str, ...]] = {}
+_DCT_TABLES: Dict[Tuple, Tensor] = {}
+
+
+def eval_columns(kind: str) -> Tuple[str, ...]:
+    """Column names of the rows of eval_audio ("audio"), pair_stats ("pair") and mcd ("mcd")."""
+    cols = _EVAL_COLUMNS.get(kind)
+    if cols is None:
+        lib, k = _lib.load(), _EVAL_KINDS[kind]
+        cols = _EVAL_COLUMNS[kind] = tuple(lib.m2_eval_column_name(k, i).decode()
+                                           for i in range(lib.m2_eval_column_count(k)))
+    return cols
+
+
+def _pair(pred: Tensor, target: Tensor, cols: Optional[Tensor], what: str):
+    require_device(pred, target, cols, what=what)
+    t = target.float().contiguous()
+    p = pred.float().contiguous()
+    if t.dim() != 3 or p.dim() != 3 or p.shape[0] != t.shape[0]:
+        raise ValueError(f"{what}: pred {tuple(pred.shape)} and target {tuple(target.shape)} must be [B, ., .]")
+    if cols is not None:
+        cols = cols.to(torch.int32).contiguous()
+        if cols.numel() != t.shape[0]:
+            raise ValueError(f"{what}: {cols.numel()} lengths for {t.shape[0]} utterances")
+    return p, t, cols
+
+
+def pair_stats(pred: Tensor, target: Tensor, transposed: bool = False, cols: Optional[Tensor] = None) -> Tensor:
+    """Sums of p - t, p, t and their products per utterance (m2_eval_pair_stats):
+    target [B, R, C]; pred [B, R, C], or [B, C, R] with ``transposed``; ``cols``
+    [B] keeps each utterance's first columns -> float64 [B, K], ``eval_columns("pair")``."""
+    p, t, cols = _pair(pred, target, cols, "m2 pair_stats")
+    B, R, C = t.shape
+    if tuple(p.shape) != ((B, C, R) if transposed else (B, R, C)):
+        raise ValueError(f"m2 pair_stats: pred {tuple(p.shape)} does not match target {tuple(t.shape)}"
+                         f"{' transposed' if transposed else ''}")
+    out = torch.empty(B, len(eval_columns("pair")), device=t.device, dtype=torch.float64)
+    _lib.call("m2_eval_pair_stats", p.data_ptr(), t.data_ptr(), None if cols is None else cols.data_ptr(), B, R, C,
+              int(transposed), out.data_ptr(), stream_handle(t.device))
+    return out
+
+
+def mcd(pred: Tensor, target: Tensor, transposed: bool = False, cols: Optional[Tensor] = None) -> Tensor:
+    """compute_mcd's sums (metrics.py:61-76, m2_eval_mcd): target [B, M, Tt]; pred
+    [B, M, Tp], or [B, Tp, M] with ``transposed`` -> float64 [B, 2]: the sum over
+    the first min(Tp, Tt, cols[b]) frames of the 13-coefficient distance, and that count."""
+    p, t, cols = _pair(pred, target, cols, "m2 mcd")
+    B, M, Tt = t.shape
+    Tp = p.shape[1] if transposed else p.shape[2]
+    if (p.shape[2] if transposed else p.shape[1]) != M:
+        raise ValueError(f"m2 mcd: pred {tuple(p.shape)} does not have the target's {M} mel bands")
+    key = (M, t.device)
+    table = _DCT_TABLES.get(key)
+    if table is None:
+        lib = _lib.load()
+        host = (ctypes.c_double * (lib.m2_eval_mcd_coefficients() * M))()
+        _lib.check(lib.m2_eval_dct_table(M, host), "m2_eval_dct_table")
+        table = _DCT_TABLES[key] = torch.tensor(list(host), dtype=torch.float64).to(t.device)
+    out = torch.empty(B, len(eval_columns("mcd")), device=t.device, dtype=torch.float64)
+    _lib.call("m2_eval_mcd", p.data_ptr(), t.data_ptr(), None if cols is None else cols.data_ptr(), table.data_ptr(),
+              B, M, Tp, Tt, int(transposed), out.data_ptr(), stream_handle(t.device))
+    return out
