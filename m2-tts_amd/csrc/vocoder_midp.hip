@@ -24,23 +24,18 @@
 // (ring protocol, warm-up chunk -1, zero columns outside [0, L1), permlane16
 // swapped 16-B epilogue stores).  The conv2 waves add the residual (ring R1,
 // ConvT2's output) in the epilogue and store U2 rows straight to global.
-#include <cmath>
+#include <algorithm>
 #include <cstdlib>
-#include <cstring>
-#include <type_traits>
 #include <vector>
 
 #include "m2_common.h"
 #include "vocoder_fused.h"
+#include "vocoder_pipe.h"
 
 namespace m2 {
 namespace mp {
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef vx_u32x4 u32x4;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+using namespace pipe;  // vector types, mfma_h, step_barrier
 
 constexpr int RROWS = 64;               // 4 chunks of 16 columns
 constexpr int RS0 = 288;                // R0 row: 256 B (hi[64] lo[64]) + pad, RS/16 = 2 mod 4
@@ -56,15 +51,6 @@ constexpr int NWAVES = 13;              // 4 phases x 3 layers + 1 loader (wave 
 // 32 banks) hit two-way conflicts; the swap makes all three conflict-free
 // (tools/probe/midp_banks.py models every access of the kernel).
 __device__ __forceinline__ unsigned r12_at(int row, int u) { return row * RS1 + 16 * (u ^ ((row >> 2) & 1)); }
-
-__device__ __forceinline__ f32x4 mfma_h(u32x4 a, u32x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, a), __builtin_bit_cast(h8, b), c, 0, 0, 0);
-}
-
-__device__ __forceinline__ void step_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-template <int V>
-using ic = std::integral_constant<int, V>;
 
 // Layer L (0 ConvT2, 1 conv1, 2 conv2) of phase S: both m-blocks 2S, 2S+1.
 // As in vocoder_tailp.hip: one fp32 accumulator per m-block for the three
@@ -370,46 +356,18 @@ int32_t launch_vocoder_midp(const void* U1, int L1, int B, const vx_u32x4* W, co
     // round; the round-4 sweep at 8 / 16 / 32 measured 23.1 / 20.0 / 29.9 us).
     // M2_MIDP_NCH forces one.
     int nch = sw().midp_nch > 0 ? std::min(sw().midp_nch, 4096) : 0;
-    if (!nch) {
-        const long chunks = cdiv(L1, 16);
-        long best = -1;
-        for (int n = 4; n <= 256; ++n) {
-            const long wgs = (long)cdiv((int)chunks, n) * B, rounds = (wgs + 255) / 256, cost = rounds * (n + 4);
-            if (best < 0 || cost < best) best = cost, nch = n;
-        }
-    }
+    if (!nch) nch = pipe::pick_strip(cdiv(L1, 16), B, 4, 256, 4);
     return nch == 16 ? mp::launch<16>(nch, U1, L1, B, W, bias, U2, st, dT)
                      : mp::launch<0>(nch, U1, L1, B, W, bias, U2, st, dT);
 }
 
 // ---------------------------------------------------------------------------
-// Host packing: dense polyphase matrices Wd[row][dq + 1][input row] (128 x 3 x
-// 128) cut into (m-block, k-block) fragment pairs along mp::mslot, unscaled
-// hi/lo halves (split2u's format).
-namespace {
-
-int floordiv(int a, int b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
-
-struct Dense {
-    std::vector<float> w = std::vector<float>(128 * 3 * 128, 0.f);
-    float& at(int row, int dq, int in) { return w[(row * 3 + dq + 1) * 128 + in]; }
-};
-
-void put_split(std::vector<uint16_t>& out, size_t idx, float v, bool* range_ok) {
-    if (!(std::fabs(v) < 65504.f)) *range_ok = false;
-    const _Float16 h = (_Float16)v;
-    const _Float16 l = (_Float16)(v - (float)h);
-    uint16_t hb, lb;
-    std::memcpy(&hb, &h, 2);
-    std::memcpy(&lb, &l, 2);
-    out[idx] = hb;
-    out[idx + 64 * 8] = lb;
-}
-
-}  // namespace
-
+// Host packing (vocoder_pipe.h): dense polyphase matrices Wd[row][dq + 1][input
+// row] (128 x 3 x 128) cut into (m-block, k-block) fragment pairs along
+// mp::mslot (no m-block reads a slot twice), unscaled hi/lo halves.
 bool pack_midp(const MidpSrc& s, std::vector<uint16_t>* wout, std::vector<float>* bout, bool* range_ok) {
-    Dense d[3];
+    using namespace pipe;
+    std::vector<PolyDense> d(3, PolyDense(128, 128));
     // ConvTranspose1d(64 -> 32, k 8, stride 4, pad 2), W [64][32][8]
     // (tts_model.py:255-263): out[4m + s] = x[m] W[s+2] + (s < 2 ? x[m-1] W[s+6] : x[m+1] W[s-2]).
     for (int sp = 0; sp < 4; ++sp)
@@ -419,42 +377,15 @@ bool pack_midp(const MidpSrc& s, std::vector<uint16_t>* wout, std::vector<float>
                 if (sp < 2) d[0].at(32 * sp + co, -1, ci) += s.wt[((size_t)ci * 32 + co) * 8 + sp + 6];
                 else d[0].at(32 * sp + co, 1, ci) += s.wt[((size_t)ci * 32 + co) * 8 + sp - 2];
             }
-    // Conv1d(32 -> 32, k 3, pad 1), W [32][32][3], on the 4-phase signal.
-    const float* wc[2] = {s.w1, s.w2};
-    for (int l = 1; l <= 2; ++l)
-        for (int sp = 0; sp < 4; ++sp)
-            for (int k = 0; k < 3; ++k) {
-                const int pp = sp + k - 1, dq = floordiv(pp, 4), p2 = pp - dq * 4;
-                for (int co = 0; co < 32; ++co)
-                    for (int ci = 0; ci < 32; ++ci)
-                        d[l].at(32 * sp + co, dq, 32 * p2 + ci) += wc[l - 1][((size_t)co * 32 + ci) * 3 + k];
-            }
-    for (int l = 0; l < 3; ++l)
-        for (int row = 0; row < 128; ++row)
-            for (int dq = -1; dq <= 1; ++dq)
-                for (int in = 0; in < 128; ++in) {
-                    if (d[l].at(row, dq, in) == 0.f) continue;
-                    bool missing = true;
-                    for (int kb = 0; missing && kb < mp::mkb(l); ++kb)
-                        for (int g = 0; g < 4; ++g) {
-                            const mp::MSlot sl = mp::mslot(l, row / 32, kb, g);
-                            if (sl.dq == dq && sl.oct == in / 8) missing = false;
-                        }
-                    if (missing) return false;
-                }
+    dense_conv3(d[1], s.w1, 4, 32, 32);
+    dense_conv3(d[2], s.w2, 4, 32, 32);
     wout->assign((size_t)mp::kUnits * 2 * 64 * 8, 0);
     for (int l = 0; l < 3; ++l)
         for (int mb = 0; mb < 8; ++mb)
-            for (int kb = 0; kb < mp::mkb(l); ++kb) {
-                const int u = mp::munit0(l) + mb * mp::mkb(l) + kb;
-                for (int lane = 0; lane < 64; ++lane) {
-                    const int row = mb * 16 + (lane & 15);
-                    const mp::MSlot sl = mp::mslot(l, mb / 2, kb, lane >> 4);
-                    for (int e = 0; e < 8; ++e)
-                        put_split(*wout, (((size_t)u * 2) * 64 + lane) * 8 + e, d[l].at(row, sl.dq, 8 * sl.oct + e),
-                                  range_ok);
-                }
-            }
+            if (!cut_fragments(
+                    d[l], mp::munit0(l) + mb * mp::mkb(l), mp::mkb(l), [&](int li) { return mb * 16 + li; },
+                    [&](int kb, int g) { return mp::mslot(l, mb / 2, kb, g); }, wout, range_ok))
+                return false;
     bout->assign(3 * 128, 0.f);
     const float* bsrc[3] = {s.bt, s.b1, s.b2};
     for (int l = 0; l < 3; ++l)

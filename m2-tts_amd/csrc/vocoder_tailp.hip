@@ -40,23 +40,17 @@
 // qa - 8 + l of chunk -1 on while later layers need it from qa - 6 + l.
 // Columns outside [0, L2) store 0 (the next conv's zero padding).
 #include <algorithm>
-#include <cmath>
 #include <cstdlib>
-#include <cstring>
-#include <type_traits>
 #include <vector>
 
 #include "m2_common.h"
 #include "vocoder_fused.h"
+#include "vocoder_pipe.h"
 
 namespace m2 {
 namespace tp {
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef vx_u32x4 u32x4;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+using namespace pipe;  // vector types, mfma_h, step_barrier, tanh_fast, off_l / last_step, ring_row
 
 // LDS rings.  R0 = U2 input, R(l+1) = output of layer l (l = 0..5); a ring
 // row is one column: 32 rows x (hi, lo) f16 kept as a hi plane and a lo plane
@@ -68,25 +62,17 @@ typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 // without padding (tools/probe/tailp_banks.py).  The swizzle depends on row
 // bits 1-2 only, so it does not change from chunk to chunk.  Rings hold 4
 // chunks of 16 columns (3 for R6, whose only reader is one step behind its
-// writer, and for R0 with the register loader; R1 and R4 also feed a residual
-// reader two layers down): three workgroups per CU.
-// TAILP_DMA (default): the loader moves U2 into R0 by LDS-DMA (buffer_load
-// ... lds: L2 -> LDS, no VGPR staging, no ds_write), one chunk ahead, so R0
-// holds 4 chunks (TAILP_DMA=0 keeps the register loader
-// and a 3-chunk R0).  Alternated twice on one box (profiles/r06/
-// r06s_tail_dma_ab/): tail 21.85 / 21.76 -> 21.46 / 21.47 us under
-// rocprofv3 at B=32 (-1.6 %; the loader's two ds_write_b128 per step were
-// 2 KB of the ~12 KB each chunk writes into LDS), 141 tail / range /
-// stress / streaming / parity tests green (r06s_tests.log).
-#ifndef TAILP_DMA
-#define TAILP_DMA 1
-#endif
-constexpr int kRingRows[7] = {TAILP_DMA ? 64 : 48, 64, 64, 64, 64, 64, 48};
+// writer; R1 and R4 also feed a residual reader two layers down): three
+// workgroups per CU.  R0 is filled by LDS-DMA (loader_role_dma below), one
+// chunk ahead, so it holds 4 chunks; the A/B against the register loader it
+// replaced (tail 21.85 / 21.76 -> 21.46 / 21.47 us at B=32) is recorded in
+// profiles/r06/r06s_tail_dma_ab/.
+constexpr int kRingRows[7] = {64, 64, 64, 64, 64, 64, 48};
 constexpr int kRingOff(int n) { return n == 0 ? 0 : kRingOff(n - 1) + kRingRows[n - 1] * 128; }
 constexpr int kLoOff(int n) { return kRingRows[n] * 64; }
 constexpr int kPeriod(int n) { return kRingRows[n] / 16; }  // chunks per ring (3 or 4)
 // NL computing layers use rings R0 .. R(NL-1) and NL + 1 waves (one per layer
-// + the loader): NL = 7 53,248 B, NL = 6 (outc_role) 47,120 B.
+// + the loader): NL = 7 55,312 B, NL = 6 (outc_role) 49,184 B of LDS in all.
 // NL = 6 also keeps the outc edge-term slot (4 floats) after the rings.
 constexpr int kCorrSlot = kRingOff(6);
 constexpr int ring_bytes(int nl) { return nl == 6 ? kCorrSlot + 16 : kRingOff(nl); }
@@ -96,7 +82,8 @@ constexpr int kFlagOff(int nl) { return ring_bytes(nl); }
 constexpr int lds_bytes(int nl) { return ring_bytes(nl) + 16; }
 constexpr int nwaves(int nl) { return nl + 1; }
 static_assert(lds_bytes(6) * 3 <= 160 * 1024, "three workgroups per CU");
-static_assert(TAILP_DMA || lds_bytes(7) * 3 <= 160 * 1024, "three workgroups per CU");
+// (the seven-layer form, an A/B switch, has fitted only two since R0 grew to 4 chunks)
+static_assert(lds_bytes(7) * 2 <= 160 * 1024, "two workgroups per CU");
 #ifdef M2_STAMPS
 constexpr int NWAVES = 8;  // stamp buffer size (the larger variant)
 #endif
@@ -105,22 +92,6 @@ constexpr int NWAVES = 8;  // stamp buffer size (the larger variant)
 __device__ __forceinline__ unsigned ring_at(int n, int row, int oct) {
     return kRingOff(n) + row * 64 + 16 * (oct ^ ((row >> 1) & 3));
 }
-// Row of column offset c (-2 .. 16) of the chunk in ring phase j.
-__device__ __forceinline__ int ring_row(int n, int j, int c) {
-    const int r = 16 * j + c, R = kRingRows[n];
-    return r < 0 ? r + R : (r >= R ? r - R : r);
-}
-
-__device__ __forceinline__ f32x4 mfma_h(u32x4 a, u32x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, a), __builtin_bit_cast(h8, b), c, 0, 0, 0);
-}
-
-// LDS hand-off between roles: the step's ds_writes complete, then the
-// workgroup barrier.  No vmcnt wait (the loader's prefetches stay in flight),
-// and the "memory" clobber keeps the compiler from moving LDS accesses across.
-// (An LDS-flag protocol that lets the roles run decoupled measured slower:
-// 48 vs 35.5 us, its polls sit on every hand-off of the chain.)
-__device__ __forceinline__ void step_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // Diagnostic build only (-DM2_STAMPS): per-wave s_memtime at the start of
 // every step (after the barrier) and before its barrier, [workgroup][wave]
@@ -142,21 +113,9 @@ __device__ unsigned long long g_tp_stamps[1024][NWAVES][64][2];
     } while (0)
 #endif
 
-// tanh(x) = 1 - 2 / (1 + e^{2x}) on v_exp_f32 / v_rcp_f32: absolute error
-// ~1e-7 (saturates to +-1 through inf / 0), against ~40 instructions for tanhf.
-__device__ __forceinline__ float tanh_fast(float x) { return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + __expf(2.f * x)); }
-
-// Layer l computes chunk k in step k + l + 1; the last step is layer 6's
-// chunk nch - 1.  (Staggered epilogues, where some layers store chunk k one
-// step after computing it, measured slower and were dropped.)
 // NL = number of computing layers: 7 (ResBlock4 conv2 and output_conv as two
 // layers) or 6 (the two composed into one, outc_role below).
-constexpr int off_l(int l) { return l + 1; }
-constexpr int last_step(int nch, int nl) { return nch - 1 + off_l(nl - 1); }
-
-template <int V>
-using ic = std::integral_constant<int, V>;
-
+//
 // One wave per layer (all NMB m-blocks).  Everything lane-dependent that does
 // not change along the strip is precomputed: the weights, biases and the LDS
 // addresses of the fragment reads, residual reads and epilogue stores for the
@@ -206,10 +165,10 @@ __device__ __forceinline__ void layer_role(unsigned char* lds, int qa, int L2, i
 #pragma unroll
         for (int f = 0; f < NF; ++f) {
             const Slot sl = fslot(L, f, g);
-            radr[f][j] = ring_at(L, ring_row(L, j, li + sl.dq - 1), sl.oct);
+            radr[f][j] = ring_at(L, ring_row(kRingRows[L], j, li + sl.dq - 1), sl.oct);
         }
 #pragma unroll
-    for (int j = 0; j < PX; ++j) xadr[j] = RES ? ring_at(L - 1, ring_row(L - 1, j, li - 2), g) : 0u;
+    for (int j = 0; j < PX; ++j) xadr[j] = RES ? ring_at(L - 1, ring_row(kRingRows[L - 1], j, li - 2), g) : 0u;
     // epilogue: after the permlane16 swap lane group g stores the hi (g even)
     // or lo (g odd) octet of rows 8(g >> 1) .. +7 of each m-block: ring octet
     // 2m + (g >> 1) (address oadr ^ 32m); ConvT4's permuted m-blocks hold
@@ -218,7 +177,7 @@ __device__ __forceinline__ void layer_role(unsigned char* lds, int qa, int L2, i
     const int obase = L == 3 ? 1 + (g >> 1) : (g >> 1);
 #pragma unroll
     for (int j = 0; j < PO; ++j)
-        oadr[j] = L < 6 ? (g & 1) * kLoOff(L + 1) + ring_at(L + 1, ring_row(L + 1, j, li), obase) : 0u;
+        oadr[j] = L < 6 ? (g & 1) * kLoOff(L + 1) + ring_at(L + 1, ring_row(kRingRows[L + 1], j, li), obase) : 0u;
     // identity A of m-block m: row li takes input row 16m + li = 8g + e
     u32x4 aid[NMB];
 #pragma unroll
@@ -407,8 +366,8 @@ __device__ __forceinline__ void outc_role(unsigned char* lds, int qa, int L2, in
     for (int f = 0; f < NF; ++f) {
         const Slot sl = outc_slot(f, g);
         // R5 holds layer 4's columns one ahead of this layer's, R4 layer 3's two
-        rbase[f] = f < 2 ? ring_at(5, ring_row(5, 0, li + sl.dq - 1), sl.oct) - kRingOff(5)
-                         : ring_at(4, ring_row(4, 0, li + sl.dq - 2), sl.oct) - kRingOff(4);
+        rbase[f] = f < 2 ? ring_at(5, ring_row(kRingRows[5], 0, li + sl.dq - 1), sl.oct) - kRingOff(5)
+                         : ring_at(4, ring_row(kRingRows[4], 0, li + sl.dq - 2), sl.oct) - kRingOff(4);
     }
     auto radr = [&](int f, int j) { return (f < 2 ? kRingOff(5) : kRingOff(4)) + ((rbase[f] + 1024u * j) & 4095u); };
     auto work = [&](int k, auto jc) {
@@ -460,67 +419,9 @@ __device__ __forceinline__ void outc_role(unsigned char* lds, int qa, int L2, in
     }
 }
 
-// U2 rows (128 B: hi[32] lo[32], the mid kernel's output format) into ring R0,
-// two chunks ahead: chunk c = columns [qa + 7 + 16c, +16), zero outside [0, L2).
-// EDGE: the strip's columns (with the prologue / epilogue chunks) may leave
-// [0, L2); interior strips skip the clamps and the zero selects.
-template <int NL, bool EDGE>
-__device__ __forceinline__ void loader_role(unsigned char* lds, int qa, int L2, int nch,
-                                            const unsigned char* __restrict__ u2) {
-    const int lane = threadIdx.x & 63, r = lane >> 3, pc = lane & 7;
-    // Every step issues its two loads unconditionally (column clamped into the
-    // utterance, zeroed when written) so the compiler can count them: the
-    // write of chunk s then waits with vmcnt(4) for its own loads only, not
-    // for the two younger chunks still in flight.
-    auto fetch = [&](int c, u32x4 (&v)[2]) {
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            int col = qa + NL + 16 * c + r + 8 * h;
-            if (EDGE) col = min(max(col, 0), L2 - 1);
-            v[h] = *reinterpret_cast<const u32x4*>(u2 + (size_t)col * 128 + pc * 16);
-        }
-    };
-    // Three register buffers used in rotation by a loop unrolled by three, so
-    // no register that a load in flight writes is ever copied (a copy would
-    // wait for that load).
-    u32x4 buf[3][2];
-    // R0 has 3 chunks: chunk s sits in ring phase s mod 3 (the loop below is
-    // unrolled by three, so copy i writes phase (i + 2) mod 3).  Lanes pc 0-3
-    // carry hi octets, 4-7 lo octets.
-    unsigned wadr[3][2];
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-#pragma unroll
-        for (int h = 0; h < 2; ++h) wadr[j][h] = (pc >> 2) * kLoOff(0) + ring_at(0, ring_row(0, j, r + 8 * h), pc & 3);
-    auto step = [&](int s, auto jc, u32x4 (&cur)[2], u32x4 (&ahead)[2]) {
-        constexpr int j = decltype(jc)::value;
-        fetch(min(s + 2, nch - 1), ahead);  // past the strip: re-read the last chunk (an L2 hit)
-        if (s < nch) {
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int col = qa + NL + 16 * s + r + 8 * h;
-                const bool in = !EDGE || (col >= 0 && col < L2);
-                const u32x4 z{0u, 0u, 0u, 0u};
-                *reinterpret_cast<u32x4*>(lds + wadr[j][h]) = in ? cur[h] : z;
-            }
-        }
-        step_barrier();
-    };
-    fetch(-1, buf[0]);
-    fetch(0, buf[1]);
-    int s = -1;
-#pragma unroll 1
-    for (; s + 2 <= last_step(nch, NL); s += 3) {  // covers every step with work (s <= nch - 1)
-        step(s, ic<2>{}, buf[0], buf[2]);
-        step(s + 1, ic<0>{}, buf[1], buf[0]);
-        step(s + 2, ic<1>{}, buf[2], buf[1]);
-    }
-#pragma unroll 1
-    for (; s <= last_step(nch, NL); ++s) step_barrier();
-}
-
-// TAILP_DMA: U2 rows into ring R0 by LDS-DMA.  One buffer_load_dwordx4 ...
-// lds writes 64 lanes x 16 B = 1 KB at M0 + 16 x lane, i.e. exactly the 16
+// U2 rows (128 B: hi[32] lo[32], the mid kernel's output format) into ring R0
+// by LDS-DMA (buffer_load ... lds: L2 -> LDS, no VGPR staging, no ds_write).
+// One buffer_load_dwordx4 ... lds writes 64 lanes x 16 B = 1 KB at M0 + 16 x lane, i.e. exactly the 16
 // rows (columns) of a chunk's hi plane (or lo plane) in ring phase c mod 4;
 // lane l fills row l / 4, slot l % 4, so it loads the U2 octet ring_at
 // places there (octet (l % 4) ^ ((row >> 1) & 3)).  The descriptor spans the
@@ -613,9 +514,7 @@ __global__ __launch_bounds__(nwaves(NL) * 64, 6) void tailp_kernel(const unsigne
             }
             [[fallthrough]];
         default:
-            if constexpr (TAILP_DMA) loader_role_dma<NL>(lds, qa, L2, nch, u2);
-            else if (edge) loader_role<NL, true>(lds, qa, L2, nch, u2);
-            else loader_role<NL, false>(lds, qa, L2, nch, u2);
+            loader_role_dma<NL>(lds, qa, L2, nch, u2);
             break;
     }
     TPSTAMP(63, 0);
@@ -669,14 +568,7 @@ int32_t launch_vocoder_tailp(const void* U2, int L2, int B, const vx_u32x4* W, c
     // round; B = 8: 63 strips of 8).  M2_TAILP_NCH forces one.
     const int nl = sw().tailp_seven ? 7 : 6;
     int nch = sw().tailp_nch > 0 ? std::min(sw().tailp_nch, 4096) : 0;
-    if (!nch) {
-        const long chunks = cdiv(L2, 16);
-        long best = -1;
-        for (int n = 8; n <= 256; ++n) {
-            const long wgs = (long)cdiv((int)chunks, n) * B, rounds = (wgs + 767) / 768, cost = rounds * (n + nl + 1);
-            if (best < 0 || cost < best) best = cost, nch = n;
-        }
-    }
+    if (!nch) nch = pipe::pick_strip(cdiv(L2, 16), B, 8, 768, nl + 1);
     // M2_TAILP_SEVEN=1: ResBlock4 conv2 and the output conv as two layers
     // (the round-2 form; A/B and test switch, m2_common.h switch table).
     // (A wave -> role map that balances the MFMA load of the SIMDs — the
@@ -690,62 +582,17 @@ int32_t launch_vocoder_tailp(const void* U2, int L2, int B, const vx_u32x4* W, c
 }
 
 // ---------------------------------------------------------------------------
-// Host packing.  Each layer is first written as a dense polyphase matrix
-// Wd[row][dq + 1][input row] (32 x 3 x 32), then cut into (m-block, k-block)
-// fragment pairs along tp::kslot: A[row = mb*16 + (lane&15)][slot g = lane>>4,
-// element e] = Wd[row][dq + 1][8*oct + e], zero on a repeated slot.  Every
-// non-zero of Wd must sit on a slot.
-namespace {
-
-int floordiv(int a, int b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
-
-struct Dense {
-    std::vector<float> w = std::vector<float>(32 * 3 * 32, 0.f);
-    float& at(int row, int dq, int in) { return w[(row * 3 + dq + 1) * 32 + in]; }
-};
-
-// ConvTranspose1d(k=4, stride 2, pad 1), W [Cin][Cout][4], on a Pin-phase input
-// (Cin channels per phase) -> 2*Pin phases of Cout channels (tts_model.py:255-263):
-// out[2i] = x[i] W1 + x[i-1] W3, out[2i+1] = x[i+1] W0 + x[i] W2.
-void dense_convT2(Dense& d, const float* W, int Pin, int Cin, int Cout) {
-    const int taps[2][2][2] = {{{0, 1}, {-1, 3}}, {{1, 0}, {0, 2}}};  // [s][j] = (input offset, kernel tap)
-    for (int pin = 0; pin < Pin; ++pin)
-        for (int s = 0; s < 2; ++s)
-            for (int j = 0; j < 2; ++j) {
-                const int pp = pin + taps[s][j][0], dq = floordiv(pp, Pin), p2 = pp - dq * Pin, kk = taps[s][j][1];
-                for (int co = 0; co < Cout; ++co)
-                    for (int ci = 0; ci < Cin; ++ci)
-                        d.at((2 * pin + s) * Cout + co, dq, p2 * Cin + ci) += W[((size_t)ci * Cout + co) * 4 + kk];
-            }
-}
-
-// Conv1d(k=3, pad 1), W [Cout][Cin][3], on a P-phase signal.
-void dense_conv3(Dense& d, const float* W, int P, int Cin, int Cout) {
-    for (int p = 0; p < P; ++p)
-        for (int k = 0; k < 3; ++k) {
-            const int pp = p + k - 1, dq = floordiv(pp, P), p2 = pp - dq * P;
-            for (int co = 0; co < Cout; ++co)
-                for (int ci = 0; ci < Cin; ++ci) d.at(p * Cout + co, dq, p2 * Cin + ci) += W[((size_t)co * Cin + ci) * 3 + k];
-        }
-}
-
-void put_split(std::vector<uint16_t>& out, size_t idx, float v, bool* range_ok) {
-    if (!(std::fabs(v) < 65504.f)) *range_ok = false;
-    const _Float16 h = (_Float16)v;
-    const _Float16 l = (_Float16)(v - (float)h);
-    uint16_t hb, lb;
-    std::memcpy(&hb, &h, 2);
-    std::memcpy(&lb, &l, 2);
-    out[idx] = hb;
-    out[idx + 64 * 8] = lb;
-}
-
-}  // namespace
-
-bool pack_outc(const TailpSrc& s, std::vector<uint16_t>* wout, std::vector<float>* bout, bool* range_ok);
-
+// Host packing (vocoder_pipe.h).  Each layer is first written as a dense
+// polyphase matrix Wd[row][dq + 1][input row] (32 x 3 x 32; the output conv 4
+// rows), then cut into (m-block, k-block) fragment pairs along tp::kslot:
+// A[row = mb*16 + (lane&15)][slot g = lane>>4, element e] =
+// Wd[prow(row)][dq + 1][8*oct + e], zero on a repeated slot.  Every non-zero of
+// Wd must sit on a slot.
 bool pack_tailp(const TailpSrc& s, std::vector<uint16_t>* wout, std::vector<float>* bout, bool* range_ok) {
-    Dense d[tp::kLayers];
+    using namespace pipe;
+    const int nrows[tp::kLayers] = {32, 32, 32, 32, 32, 32, 4};
+    std::vector<PolyDense> d;
+    for (int l = 0; l < tp::kLayers; ++l) d.emplace_back(nrows[l], 32);
     dense_convT2(d[0], s.wt3, 1, 32, 16);
     dense_conv3(d[1], s.w31, 2, 16, 16);
     dense_conv3(d[2], s.w32, 2, 16, 16);
@@ -753,134 +600,24 @@ bool pack_tailp(const TailpSrc& s, std::vector<uint16_t>* wout, std::vector<floa
     dense_conv3(d[4], s.w41, 4, 8, 8);
     dense_conv3(d[5], s.w42, 4, 8, 8);
     dense_conv3(d[6], s.wo, 4, 8, 1);
-    const int nrows[tp::kLayers] = {32, 32, 32, 32, 32, 32, 4};
-    for (int l = 0; l < tp::kLayers; ++l)
-        for (int R = 0; R < 32; ++R)  // MFMA row R computes dense row prow(l, R)
-            for (int dq = -1; dq <= 1; ++dq)
-                for (int in = 0; in < 32; ++in) {
-                    const int row = tp::prow(l, R);
-                    if (d[l].at(row, dq, in) == 0.f) continue;
-                    bool missing = row < nrows[l];
-                    for (int kb = 0; missing && kb < tp::nkbm(l, R / 16); ++kb)
-                        for (int g = 0; g < 4; ++g) {
-                            const tp::Slot sl = tp::kslot(l, R / 16, kb, g);
-                            if (sl.dq == dq && sl.oct == in / 8) missing = false;
-                        }
-                    if (missing) return false;  // a non-zero weight that no slot reads
-                }
     wout->assign((size_t)(tp::kUnits + tp::kOutcUnits) * 2 * 64 * 8, 0);
     for (int l = 0; l < tp::kLayers; ++l)
-        for (int mb = 0; mb < tp::nmb(l); ++mb)
-            for (int kb = 0; kb < tp::nkbm(l, mb); ++kb) {
-                const int u = tp::unit0(l) + mb * tp::nkb(l) + kb;
-                for (int lane = 0; lane < 64; ++lane) {
-                    const int row = tp::prow(l, mb * 16 + (lane & 15)), g = lane >> 4;
-                    const tp::Slot sl = tp::kslot(l, mb, kb, g);
-                    // a (dq, octet) the m-block already reads in an earlier slot gets zeros
-                    bool dup = false;
-                    for (int j = 0; j < kb * 4 + g; ++j) {
-                        const tp::Slot o = tp::kslot(l, mb, j / 4, j % 4);
-                        dup = dup || (o.dq == sl.dq && o.oct == sl.oct);
-                    }
-                    for (int e = 0; e < 8; ++e) {
-                        float v = 0.f;
-                        if (row < nrows[l] && !dup) v = d[l].at(row, sl.dq, 8 * sl.oct + e);
-                        put_split(*wout, (((size_t)u * 2) * 64 + lane) * 8 + e, v, range_ok);
-                    }
-                }
-            }
+        for (int mb = 0; mb < tp::nmb(l); ++mb)  // MFMA row R computes dense row prow(l, R)
+            if (!cut_fragments(
+                    d[l], tp::unit0(l) + mb * tp::nkb(l), tp::nkbm(l, mb),
+                    [&](int li) { return tp::prow(l, mb * 16 + li); },
+                    [&](int kb, int g) { return tp::kslot(l, mb, kb, g); }, wout, range_ok))
+                return false;  // a non-zero weight that no slot reads
     bout->assign(tp::kBiasFloats, 0.f);
     const float* bsrc[tp::kLayers] = {s.bt3, s.b31, s.b32, s.bt4, s.b41, s.b42, s.bo};
     const int cper[tp::kLayers] = {16, 16, 16, 8, 8, 8, 1};
     for (int l = 0; l < tp::kLayers; ++l)
         for (int R = 0; R < nrows[l]; ++R) (*bout)[l * 32 + R] = bsrc[l][tp::prow(l, R) % cper[l]];
-    return pack_outc(s, wout, bout, range_ok);
-}
-
-// The composed ResBlock4-conv2 + output_conv layer (outc_role), in double:
-// audio[t] = tanh(bo' + sum_d Wo[c][d] x[c][t+d] + sum_j Wc[c'][j] h[c'][t+j]),
-// Wc[c'][j] = sum_{d+e=j} sum_c Wo[c][d] W2[c][c'][e], bo' = bo + sum_d sum_c
-// Wo[c][d] b2[c]; on the 4-phase columns (row p = output phase, input row
-// p2*8 + c at column q + dq).  Edge terms: the y the composed form sees at
-// t = -1 is b2 + W2[.][.][2] h[., 0], at t = L4 it is b2 + W2[.][.][0] h[., L4-1].
-namespace {
-// The composed layer's dense matrices on the 4-phase columns (dh on ResBlock4's
-// intermediate h, dx on ConvT4's output x: [output phase][dq + 1][input row]),
-// its bias and the edge terms vL[8], vR[8], kL, kR.
-struct OutcDense {
-    double dh[4][3][32] = {}, dx[4][3][32] = {}, bo = 0.0, corr[18] = {};
-};
-OutcDense outc_dense(const TailpSrc& s) {
-    OutcDense o;
-    auto& dh = o.dh;
-    auto& dx = o.dx;
-    auto wo = [&](int c, int k) { return (double)s.wo[c * 3 + k]; };
-    auto w2 = [&](int c, int ci, int k) { return (double)s.w42[(c * 8 + ci) * 3 + k]; };
-    for (int p = 0; p < 4; ++p)
-        for (int d = -1; d <= 1; ++d)
-            for (int c = 0; c < 8; ++c) {
-                const int tx = p + d, qx = floordiv(tx, 4);
-                dx[p][qx + 1][(tx - 4 * qx) * 8 + c] += wo(c, d + 1);
-                for (int e = -1; e <= 1; ++e)
-                    for (int ci = 0; ci < 8; ++ci) {
-                        const int th = p + d + e, qh = floordiv(th, 4);
-                        dh[p][qh + 1][(th - 4 * qh) * 8 + ci] += wo(c, d + 1) * w2(c, ci, e + 1);
-                    }
-            }
-    double bo = s.bo[0], kl = 0.0, kr = 0.0;
-    for (int c = 0; c < 8; ++c) {
-        for (int k = 0; k < 3; ++k) bo += wo(c, k) * s.b42[c];
-        kl += wo(c, 0) * s.b42[c];
-        kr += wo(c, 2) * s.b42[c];
-    }
-    o.bo = bo;
-    for (int ci = 0; ci < 8; ++ci) {
-        double vl = 0.0, vr = 0.0;
-        for (int c = 0; c < 8; ++c) {
-            vl += wo(c, 0) * w2(c, ci, 2);
-            vr += wo(c, 2) * w2(c, ci, 0);
-        }
-        o.corr[ci] = vl;
-        o.corr[8 + ci] = vr;
-    }
-    o.corr[16] = kl;
-    o.corr[17] = kr;
-    return o;
-}
-}  // namespace
-
-bool pack_outc(const TailpSrc& s, std::vector<uint16_t>* wout, std::vector<float>* bout, bool* range_ok) {
-    const OutcDense o = outc_dense(s);
-    const auto& dh = o.dh;
-    const auto& dx = o.dx;
-    // every non-zero on a slot (fragments 0, 1: h; 2, 3: x)
-    for (int p = 0; p < 4; ++p)
-        for (int dq = -1; dq <= 1; ++dq)
-            for (int in = 0; in < 32; ++in)
-                for (int src = 0; src < 2; ++src) {
-                    if ((src ? dx : dh)[p][dq + 1][in] == 0.0) continue;
-                    bool found = false;
-                    for (int f = 2 * src; f < 2 * src + 2; ++f)
-                        for (int g = 0; g < 4; ++g) {
-                            const tp::Slot sl = tp::outc_slot(f, g);
-                            found = found || (sl.dq == dq && sl.oct == in / 8);
-                        }
-                    if (!found) return false;
-                }
-    for (int f = 0; f < tp::kOutcUnits; ++f)
-        for (int lane = 0; lane < 64; ++lane) {
-            const int row = lane & 15, g = lane >> 4;
-            const tp::Slot sl = tp::outc_slot(f, g);
-            const bool dup = f == 3 && g >= 2;  // (q, 2), (q, 3) of x are read by fragment 2
-            for (int e = 0; e < 8; ++e) {
-                double v = 0.0;
-                if (row < 4 && !dup) v = (f < 2 ? dh : dx)[row][sl.dq + 1][8 * sl.oct + e];
-                put_split(*wout, (((size_t)(tp::kOutcUnit0 + f) * 2) * 64 + lane) * 8 + e, (float)v, range_ok);
-            }
-        }
-    for (int r = 0; r < 4; ++r) (*bout)[tp::kOutcBias + r] = (float)o.bo;
-    for (int i = 0; i < 18; ++i) (*bout)[tp::kOutcCorr + i] = (float)o.corr[i];
-    return true;
+    // The composed ResBlock4-conv2 + output_conv layer (outc_role): fragments
+    // 0, 1 on h, 2, 3 on x, whose slots (q, 2), (q, 3) of fragment 3 repeat
+    // fragment 2's and get zeros.
+    return pack_outc_layer(s, 8, tp::kOutcUnit0, 2, 2, tp::outc_slot, tp::kOutcBias, tp::kOutcCorr, wout, bout,
+                           range_ok);
 }
 
 }  // namespace m2

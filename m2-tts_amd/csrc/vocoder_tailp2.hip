@@ -18,29 +18,25 @@
 //   ResBlock4 wave w = phases 2w, 2w + 1 (16-channel units p-1 .. p+2 of the
 //             unit sequence (q-1, 3), (q, 0..3), (q+1, 0), two per fragment)
 //   output_conv one wave, one m-block (rows 0-3 = the 4 audio phases)
-// 13 layer waves + 1 loader wave, one workgroup per CU (104 KB of rings).
+// 13 layer waves + 1 loader wave, one workgroup per CU (108 KB of rings).
 // Pipeline protocol, warm-up chunk, zero columns outside [0, L2), lean
 // epilogues and the identity-A residual MFMAs are those of vocoder_tailp.hip.
 // Default (NL = 6): ResBlock4's conv2 and output_conv composed into one layer
 // on one wave (outc2_role; the stage1 tail's outc_role at 16 channels): 11
-// layer waves + the loader, 92 KB of rings, one pipeline step fewer.
+// layer waves + the loader, 96 KB of rings, one pipeline step fewer.
 // M2_TAILP2_SEVEN=1 keeps the seven-layer form.
 #include <algorithm>
-#include <cmath>
 #include <cstdlib>
-#include <cstring>
-#include <type_traits>
 #include <vector>
 
 #include "m2_common.h"
 #include "vocoder_fused.h"
+#include "vocoder_pipe.h"
 
 namespace m2 {
 namespace tp2 {
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef vx_u32x4 u32x4;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace pipe;  // vector types, mfma_h, step_barrier, tanh_fast, off_l / last_step, ring_row
 
 // LDS rings: R0 = U2, R(l+1) = output of layer l; a ring row is one column as
 // a 128-B hi row (64 f16) in the hi plane and a 128-B lo row kLoOff(n) bytes
@@ -48,16 +44,11 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // (ds_read_b128), residual read and epilogue store (ds_write_b128) of the
 // kernel is then bank-conflict free (tools/probe/tailp2_banks.py models them
 // all).  R6 holds 3 chunks of 16 columns (its only reader is one step behind
-// the writer; R0 too with the register loader), the others 4.
-// TAILP2_DMA (default): U2 into R0 by LDS-DMA, one chunk ahead, R0 4 chunks
-// (loader_role_dma below; TAILP2_DMA=0 keeps the register loader, R0 3 chunks).
-// Alternated twice on one box (profiles/r06/r06t_tail2_dma_ab/): tail2
-// 19.38 / 19.51 -> 18.97 / 18.84 us at B=8 T=500, 146.0 / 146.4 -> 145.4 /
-// 145.4 us at B=16 T=2600; 174 tests green (r06t_tests.log).
-#ifndef TAILP2_DMA
-#define TAILP2_DMA 1
-#endif
-constexpr int kRingRows[7] = {TAILP2_DMA ? 64 : 48, 64, 64, 64, 64, 64, 48};
+// the writer), the others 4.  R0 is filled by LDS-DMA, one chunk ahead
+// (loader_role_dma below); the A/B against the register loader it replaced
+// (tail2 19.38 / 19.51 -> 18.97 / 18.84 us at B=8 T=500) is recorded in
+// profiles/r06/r06t_tail2_dma_ab/.
+constexpr int kRingRows[7] = {64, 64, 64, 64, 64, 64, 48};
 constexpr int kRingOff(int n) { return n == 0 ? 0 : kRingOff(n - 1) + kRingRows[n - 1] * 256; }
 constexpr int kLoOff(int n) { return kRingRows[n] * 128; }
 constexpr int kPeriod(int n) { return kRingRows[n] / 16; }
@@ -76,25 +67,6 @@ constexpr int nwaves(int nl) { return nl == 6 ? 12 : 14; }
 __device__ __forceinline__ unsigned ring_at(int n, int row, int oct) {
     return kRingOff(n) + row * 128 + 16 * (oct ^ (row & 7));
 }
-__device__ __forceinline__ int ring_row(int n, int j, int c) {
-    const int r = 16 * j + c, R = kRingRows[n];
-    return r < 0 ? r + R : (r >= R ? r - R : r);
-}
-
-__device__ __forceinline__ f32x4 mfma_h(u32x4 a, u32x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, a), __builtin_bit_cast(h8, b), c, 0, 0, 0);
-}
-
-__device__ __forceinline__ void step_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-__device__ __forceinline__ float tanh_fast(float x) { return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + __expf(2.f * x)); }
-
-constexpr int off_l(int l) { return l + 1; }
-constexpr int last_step(int nch, int nl) { return nch - 1 + off_l(nl - 1); }
-
-template <int V>
-using ic = std::integral_constant<int, V>;
-
 // ---------------------------------------------------------------------------
 // Slot tables (shared by the packer and the kernel).
 struct Slot {
@@ -109,14 +81,13 @@ constexpr int kUnits = unit0(kLayers);
 constexpr int unit_of(int l, int w, int m, int kb) { return unit0(l) + (w * nmbw(l) + m) * nkb(l) + kb; }
 // dense m-block (output rows 16 d .. 16 d + 15) of wave w's m-block m
 constexpr int dmb(int l, int w, int m) { return l == 3 ? (w == 0 ? 1 + m : (m == 0 ? 0 : 3)) : nmbw(l) * w + m; }
-constexpr int fdiv(int a, int b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
 // 16-channel units of a 4-phase signal around column q: (q-1, 3), (q, 0..3), (q+1, 0)
 constexpr Slot s4unit(int j) { return j == 0 ? Slot{-1, 3} : (j == 5 ? Slot{1, 0} : Slot{0, j - 1}); }
 constexpr Slot kslot(int l, int w, int m, int kb, int g) {
     if (l == 0)  // phase w: columns (q, q-1) for phase 0, (q+1, q) for phase 1; 64 channels = 2 k-blocks each
         return Slot{kb < 2 ? (w == 0 ? 0 : 1) : (w == 0 ? -1 : 0), 4 * (kb & 1) + g};
     if (l == 1 || l == 2) {  // phase w, tap t3 + kb - 1: phase pp mod 2 of column q + floor(pp / 2)
-        const int pp = w + kb - 1, dq = fdiv(pp, 2);
+        const int pp = w + kb - 1, dq = floordiv(pp, 2);
         return Slot{dq, 4 * (pp - 2 * dq) + g};
     }
     if (l == 3) {  // ConvT4 output phase s reads two (column, phase) slots of u3
@@ -185,17 +156,18 @@ __device__ __forceinline__ void layer_role(unsigned char* lds, int qa, int L2, i
 #pragma unroll
         for (int f = 0; f < NF; ++f) {
             const Slot sl = fslot(L, W, f, g);
-            radr[f][j] = ring_at(L, ring_row(L, j, li + sl.dq - 1), sl.oct);
+            radr[f][j] = ring_at(L, ring_row(kRingRows[L], j, li + sl.dq - 1), sl.oct);
         }
     // residual x: the block input (ring R(L-1), two columns ahead), octets 4W .. 4W+3
 #pragma unroll
-    for (int j = 0; j < PX; ++j) xadr[j] = RES ? ring_at(L - 1, ring_row(L - 1, j, li - 2), 4 * W + g) : 0u;
+    for (int j = 0; j < PX; ++j) xadr[j] = RES ? ring_at(L - 1, ring_row(kRingRows[L - 1], j, li - 2), 4 * W + g) : 0u;
     // epilogue: lane group g stores the hi (g even) / lo (g odd) octet 2 d + (g >> 1)
     // of m-block d = dmb(L, W, m); the m-blocks' addresses differ by an XOR of
     // 32 (d ^ d0) in the octet field (the swizzle is an XOR on bits 4-6)
 #pragma unroll
     for (int j = 0; j < PO; ++j)
-        oadr[j] = L < 6 ? (g & 1) * kLoOff(L + 1) + ring_at(L + 1, ring_row(L + 1, j, li), 2 * dmb(L, W, 0) + (g >> 1))
+        oadr[j] = L < 6 ? (g & 1) * kLoOff(L + 1) +
+                              ring_at(L + 1, ring_row(kRingRows[L + 1], j, li), 2 * dmb(L, W, 0) + (g >> 1))
                         : 0u;
     u32x4 aid[NMB];  // identity A of m-block m: row li takes fragment row 16 m + li = 8 g + e
 #pragma unroll
@@ -354,8 +326,8 @@ __device__ __forceinline__ void outc2_role(unsigned char* lds, int qa, int L2, i
 #pragma unroll
     for (int f = 0; f < NF; ++f) {
         const Slot sl = outc_slot(f, g);
-        rbase[f] = f < 4 ? ring_at(5, ring_row(5, 0, li + sl.dq - 1), sl.oct) - kRingOff(5)
-                         : ring_at(4, ring_row(4, 0, li + sl.dq - 2), sl.oct) - kRingOff(4);
+        rbase[f] = f < 4 ? ring_at(5, ring_row(kRingRows[5], 0, li + sl.dq - 1), sl.oct) - kRingOff(5)
+                         : ring_at(4, ring_row(kRingRows[4], 0, li + sl.dq - 2), sl.oct) - kRingOff(4);
     }
     auto radr = [&](int f, int j) { return (f < 4 ? kRingOff(5) : kRingOff(4)) + ((rbase[f] + 2048u * j) & 8191u); };
     auto work = [&](int k, auto jc) {
@@ -407,56 +379,7 @@ __device__ __forceinline__ void outc2_role(unsigned char* lds, int qa, int L2, i
     }
 }
 
-// U2 rows (256 B: hi[64] lo[64]) into ring R0, two chunks ahead: chunk c =
-// columns [qa + 7 + 16c, +16), zero outside [0, L2).  Lane (r = lane >> 4, pc =
-// lane & 15) moves 16 B of columns r, r + 4, r + 8, r + 12 (pc < 8: hi octet pc,
-// else lo octet pc - 8); loads unconditional (clamped) so their waits are counted.
-template <int NL, bool EDGE>
-__device__ __forceinline__ void loader_role(unsigned char* lds, int qa, int L2, int nch,
-                                            const unsigned char* __restrict__ u2) {
-    const int lane = threadIdx.x & 63, r = lane >> 4, pc = lane & 15;
-    auto fetch = [&](int c, u32x4 (&v)[4]) {
-#pragma unroll
-        for (int h = 0; h < 4; ++h) {
-            int col = qa + NL + 16 * c + r + 4 * h;
-            if (EDGE) col = min(max(col, 0), L2 - 1);
-            v[h] = *reinterpret_cast<const u32x4*>(u2 + (size_t)col * 256 + pc * 16);
-        }
-    };
-    u32x4 buf[3][4];
-    unsigned wadr[3][4];
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-#pragma unroll
-        for (int h = 0; h < 4; ++h) wadr[j][h] = (pc >> 3) * kLoOff(0) + ring_at(0, ring_row(0, j, r + 4 * h), pc & 7);
-    auto step = [&](int s, auto jc, u32x4 (&cur)[4], u32x4 (&ahead)[4]) {
-        constexpr int j = decltype(jc)::value;
-        fetch(min(s + 2, nch - 1), ahead);
-        if (s < nch) {
-#pragma unroll
-            for (int h = 0; h < 4; ++h) {
-                const int col = qa + NL + 16 * s + r + 4 * h;
-                const bool in = !EDGE || (col >= 0 && col < L2);
-                const u32x4 z{0u, 0u, 0u, 0u};
-                *reinterpret_cast<u32x4*>(lds + wadr[j][h]) = in ? cur[h] : z;
-            }
-        }
-        step_barrier();
-    };
-    fetch(-1, buf[0]);
-    fetch(0, buf[1]);
-    int s = -1;
-#pragma unroll 1
-    for (; s + 2 <= last_step(nch, NL); s += 3) {
-        step(s, ic<2>{}, buf[0], buf[2]);
-        step(s + 1, ic<0>{}, buf[1], buf[0]);
-        step(s + 2, ic<1>{}, buf[2], buf[1]);
-    }
-#pragma unroll 1
-    for (; s <= last_step(nch, NL); ++s) step_barrier();
-}
-
-// TAILP2_DMA: U2 rows into ring R0 by LDS-DMA (as vocoder_tailp.hip's
+// U2 rows (256 B: hi[64] lo[64]) into ring R0 by LDS-DMA (as vocoder_tailp.hip's
 // loader_role_dma).  A chunk's hi plane is 16 rows x 128 B = two 1-KB
 // buffer_load_dwordx4 ... lds (rows 8i .. 8i + 7: lane l fills row 8i + l / 8,
 // slot l % 8, i.e. octet (l % 8) ^ (row & 7)), its lo plane two more; columns
@@ -553,9 +476,7 @@ __global__ __launch_bounds__(nwaves(NL) * 64, 1) void tailp2_kernel(const unsign
             }
             [[fallthrough]];
         default:
-            if constexpr (TAILP2_DMA) loader_role_dma<NL>(lds, qa, L2, nch, u2);
-            else if (edge) loader_role<NL, true>(lds, qa, L2, nch, u2);
-            else loader_role<NL, false>(lds, qa, L2, nch, u2);
+            loader_role_dma<NL>(lds, qa, L2, nch, u2);
             break;
     }
     if (rd.rw) {  // range policy "fallback": this strip's audio again in fp32 if it is not finite
@@ -598,76 +519,23 @@ int32_t launch_vocoder_tailp2(const void* U2, int L2, int B, const vx_u32x4* W, 
     const bool seven = sw().tailp2_seven;
     const int nl = seven ? 7 : 6;
     int nch = sw().tailp2_nch > 0 ? std::min(sw().tailp2_nch, 4096) : 0;
-    if (!nch) {
-        const long chunks = cdiv(L2, 16);
-        long best = -1;
-        for (int n = 8; n <= 256; ++n) {
-            const long wgs = (long)cdiv((int)chunks, n) * B, rounds = (wgs + 255) / 256, cost = rounds * (n + nl);
-            if (best < 0 || cost < best) best = cost, nch = n;
-        }
-    }
+    if (!nch) nch = pipe::pick_strip(cdiv(L2, 16), B, 8, 256, nl);
     return seven ? tp2::launch_nl<7>(nch, U2, L2, B, W, bias, audio, rflag, st, dT, rd)
                  : tp2::launch_nl<6>(nch, U2, L2, B, W, bias, audio, rflag, st, dT, rd);
 }
 
 // ---------------------------------------------------------------------------
-// Host packing: each layer as a dense polyphase matrix Wd[row][dq + 1][input
-// row] (64 x 3 x 64), cut into (wave, m-block, k-block) fragment pairs along
-// tp2::kslot: A[row = lane & 15][slot g = lane >> 4, element e] =
-// Wd[16 dmb + (lane & 15)][dq + 1][8 oct + e], zero on a slot the m-block
-// already read.  Every non-zero of Wd must sit on a slot.
-namespace {
-
-int floordiv2(int a, int b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
-
-struct Dense64 {
-    std::vector<float> w = std::vector<float>(64 * 3 * 64, 0.f);
-    float& at(int row, int dq, int in) { return w[(row * 3 + dq + 1) * 64 + in]; }
-};
-
-// ConvTranspose1d(k=4, stride 2, pad 1), W [Cin][Cout][4], on a Pin-phase input
-// -> 2 Pin phases of Cout channels: out[2i] = x[i] W1 + x[i-1] W3,
-// out[2i+1] = x[i+1] W0 + x[i] W2 (tts_model.py:255-263).
-void dense_convT2(Dense64& d, const float* W, int Pin, int Cin, int Cout) {
-    const int taps[2][2][2] = {{{0, 1}, {-1, 3}}, {{1, 0}, {0, 2}}};
-    for (int pin = 0; pin < Pin; ++pin)
-        for (int s = 0; s < 2; ++s)
-            for (int j = 0; j < 2; ++j) {
-                const int pp = pin + taps[s][j][0], dq = floordiv2(pp, Pin), p2 = pp - dq * Pin, kk = taps[s][j][1];
-                for (int co = 0; co < Cout; ++co)
-                    for (int ci = 0; ci < Cin; ++ci)
-                        d.at((2 * pin + s) * Cout + co, dq, p2 * Cin + ci) += W[((size_t)ci * Cout + co) * 4 + kk];
-            }
-}
-
-// Conv1d(k=3, pad 1), W [Cout][Cin][3], on a P-phase signal.
-void dense_conv3(Dense64& d, const float* W, int P, int Cin, int Cout) {
-    for (int p = 0; p < P; ++p)
-        for (int k = 0; k < 3; ++k) {
-            const int pp = p + k - 1, dq = floordiv2(pp, P), p2 = pp - dq * P;
-            for (int co = 0; co < Cout; ++co)
-                for (int ci = 0; ci < Cin; ++ci) d.at(p * Cout + co, dq, p2 * Cin + ci) += W[((size_t)co * Cin + ci) * 3 + k];
-        }
-}
-
-void put_split(std::vector<uint16_t>& out, size_t idx, float v, bool* range_ok) {
-    if (!(std::fabs(v) < 65504.f)) *range_ok = false;
-    const _Float16 h = (_Float16)v;
-    const _Float16 l = (_Float16)(v - (float)h);
-    uint16_t hb, lb;
-    std::memcpy(&hb, &h, 2);
-    std::memcpy(&lb, &l, 2);
-    out[idx] = hb;
-    out[idx + 64 * 8] = lb;
-}
-
-}  // namespace
-
-bool pack_outc2(const TailpSrc& s, std::vector<uint16_t>* wout, std::vector<float>* bout, bool* range_ok);
-
+// Host packing (vocoder_pipe.h): each layer as a dense polyphase matrix
+// Wd[row][dq + 1][input row] (64 x 3 x 64; the output conv 4 rows), cut into
+// (wave, m-block, k-block) fragment pairs along tp2::kslot: A[row = lane & 15]
+// [slot g = lane >> 4, element e] = Wd[16 dmb + (lane & 15)][dq + 1][8 oct + e],
+// zero on a slot the m-block already read.  Every non-zero of Wd must sit on a
+// slot.
 bool pack_tailp2(const TailpSrc& s, std::vector<uint16_t>* wout, std::vector<float>* bout, bool* range_ok) {
     using namespace tp2;
-    Dense64 d[kLayers];
+    const int nrows[kLayers] = {64, 64, 64, 64, 64, 64, 4};
+    std::vector<PolyDense> d;
+    for (int l = 0; l < kLayers; ++l) d.emplace_back(nrows[l], 64);
     dense_convT2(d[0], s.wt3, 1, 64, 32);
     dense_conv3(d[1], s.w31, 2, 32, 32);
     dense_conv3(d[2], s.w32, 2, 32, 32);
@@ -675,126 +543,24 @@ bool pack_tailp2(const TailpSrc& s, std::vector<uint16_t>* wout, std::vector<flo
     dense_conv3(d[4], s.w41, 4, 16, 16);
     dense_conv3(d[5], s.w42, 4, 16, 16);
     dense_conv3(d[6], s.wo, 4, 16, 1);
-    const int nrows[kLayers] = {64, 64, 64, 64, 64, 64, 4};
-    // every non-zero dense weight must be read by some slot of its m-block
-    for (int l = 0; l < kLayers; ++l)
-        for (int w = 0; w < nwv(l); ++w)
-            for (int m = 0; m < nmbw(l); ++m)
-                for (int rr = 0; rr < 16; ++rr) {
-                    const int row = 16 * dmb(l, w, m) + rr;
-                    if (row >= nrows[l]) continue;
-                    for (int dq = -1; dq <= 1; ++dq)
-                        for (int in = 0; in < 64; ++in) {
-                            if (d[l].at(row, dq, in) == 0.f) continue;
-                            bool found = false;
-                            for (int kb = 0; kb < nkb(l) && !found; ++kb)
-                                for (int g = 0; g < 4; ++g) {
-                                    const Slot sl = kslot(l, w, m, kb, g);
-                                    if (sl.dq == dq && sl.oct == in / 8) found = true;
-                                }
-                            if (!found) return false;
-                        }
-                }
     wout->assign((size_t)(kUnits + kOutcF) * 2 * 64 * 8, 0);
-    for (int l = 0; l < kLayers; ++l)
-        for (int w = 0; w < nwv(l); ++w)
-            for (int m = 0; m < nmbw(l); ++m)
-                for (int kb = 0; kb < nkb(l); ++kb) {
-                    const int u = unit_of(l, w, m, kb);
-                    for (int lane = 0; lane < 64; ++lane) {
-                        const int row = 16 * dmb(l, w, m) + (lane & 15), g = lane >> 4;
-                        const Slot sl = kslot(l, w, m, kb, g);
-                        bool dup = false;  // a (dq, octet) this m-block already reads in an earlier slot
-                        for (int j = 0; j < kb * 4 + g; ++j) {
-                            const Slot o = kslot(l, w, m, j / 4, j % 4);
-                            dup = dup || (o.dq == sl.dq && o.oct == sl.oct);
-                        }
-                        for (int e = 0; e < 8; ++e) {
-                            float v = 0.f;
-                            if (row < nrows[l] && !dup) v = d[l].at(row, sl.dq, 8 * sl.oct + e);
-                            put_split(*wout, (((size_t)u * 2) * 64 + lane) * 8 + e, v, range_ok);
-                        }
-                    }
-                }
     // biases in MFMA row order: [layer][wave][m-block][16 rows]
     bout->assign(kBiasFloats, 0.f);
     const float* bsrc[kLayers] = {s.bt3, s.b31, s.b32, s.bt4, s.b41, s.b42, s.bo};
     const int cper[kLayers] = {32, 32, 32, 16, 16, 16, 1};
     for (int l = 0; l < kLayers; ++l)
         for (int w = 0; w < nwv(l); ++w)
-            for (int m = 0; m < nmbw(l); ++m)
-                for (int rr = 0; rr < 16; ++rr) {
-                    const int row = 16 * dmb(l, w, m) + rr;
-                    if (row < nrows[l]) (*bout)[l * 64 + (nmbw(l) * w + m) * 16 + rr] = bsrc[l][row % cper[l]];
-                }
-    return pack_outc2(s, wout, bout, range_ok);
-}
-
-// The composed layer (outc2_role), in double: audio[t] = tanh(bo' + sum_d
-// Wo[c][d] x[c][t+d] + sum_j Wc[c'][j] h[c'][t+j]), Wc[c'][j] = sum_{d+e=j}
-// sum_c Wo[c][d] W2[c][c'][e], bo' = bo + sum_d sum_c Wo[c][d] b2[c]; rows =
-// the 4 output phases, input row p2 * 16 + c at column q + dq.  Edge terms as
-// in vocoder_tailp.hip's pack_outc.
-bool pack_outc2(const TailpSrc& s, std::vector<uint16_t>* wout, std::vector<float>* bout, bool* range_ok) {
-    using namespace tp2;
-    constexpr int C = 16;
-    std::vector<double> dh(4 * 3 * 64, 0.0), dx(4 * 3 * 64, 0.0);
-    auto at = [](std::vector<double>& d, int p, int dq, int in) -> double& { return d[(p * 3 + dq + 1) * 64 + in]; };
-    auto wo = [&](int c, int k) { return (double)s.wo[c * 3 + k]; };
-    auto w2 = [&](int c, int ci, int k) { return (double)s.w42[(c * C + ci) * 3 + k]; };
-    for (int p = 0; p < 4; ++p)
-        for (int d = -1; d <= 1; ++d)
-            for (int c = 0; c < C; ++c) {
-                const int tx = p + d, qx = floordiv2(tx, 4);
-                at(dx, p, qx, (tx - 4 * qx) * C + c) += wo(c, d + 1);
-                for (int e = -1; e <= 1; ++e)
-                    for (int ci = 0; ci < C; ++ci) {
-                        const int th = p + d + e, qh = floordiv2(th, 4);
-                        at(dh, p, qh, (th - 4 * qh) * C + ci) += wo(c, d + 1) * w2(c, ci, e + 1);
-                    }
+            for (int m = 0; m < nmbw(l); ++m) {
+                auto row = [&](int li) { return 16 * dmb(l, w, m) + li; };
+                if (!cut_fragments(
+                        d[l], unit_of(l, w, m, 0), nkb(l), row, [&](int kb, int g) { return kslot(l, w, m, kb, g); },
+                        wout, range_ok))
+                    return false;
+                for (int rr = 0; rr < 16; ++rr)
+                    if (row(rr) < nrows[l]) (*bout)[l * 64 + (nmbw(l) * w + m) * 16 + rr] = bsrc[l][row(rr) % cper[l]];
             }
-    for (int p = 0; p < 4; ++p)
-        for (int dq = -1; dq <= 1; ++dq)
-            for (int in = 0; in < 64; ++in)
-                for (int src = 0; src < 2; ++src) {
-                    if (at(src ? dx : dh, p, dq, in) == 0.0) continue;
-                    bool found = false;
-                    for (int f = src ? 4 : 0; f < (src ? kOutcF : 4); ++f)
-                        for (int g = 0; g < 4; ++g) {
-                            const Slot sl = outc_slot(f, g);
-                            found = found || (sl.dq == dq && sl.oct == in / 8);
-                        }
-                    if (!found) return false;
-                }
-    for (int f = 0; f < kOutcF; ++f)
-        for (int lane = 0; lane < 64; ++lane) {
-            const int row = lane & 15, g = lane >> 4;
-            const Slot sl = outc_slot(f, g);
-            for (int e = 0; e < 8; ++e) {
-                double v = 0.0;
-                if (row < 4) v = at(f < 4 ? dh : dx, row, sl.dq, 8 * sl.oct + e);
-                put_split(*wout, (((size_t)(kOutcUnit0 + f) * 2) * 64 + lane) * 8 + e, (float)v, range_ok);
-            }
-        }
-    double bo = s.bo[0], kl = 0.0, kr = 0.0;
-    for (int c = 0; c < C; ++c) {
-        for (int k = 0; k < 3; ++k) bo += wo(c, k) * s.b42[c];
-        kl += wo(c, 0) * s.b42[c];
-        kr += wo(c, 2) * s.b42[c];
-    }
-    for (int r = 0; r < 4; ++r) (*bout)[kOutcBias + r] = (float)bo;
-    for (int ci = 0; ci < C; ++ci) {
-        double vl = 0.0, vr = 0.0;
-        for (int c = 0; c < C; ++c) {
-            vl += wo(c, 0) * w2(c, ci, 2);
-            vr += wo(c, 2) * w2(c, ci, 0);
-        }
-        (*bout)[kOutcCorr + ci] = (float)vl;
-        (*bout)[kOutcCorr + 16 + ci] = (float)vr;
-    }
-    (*bout)[kOutcCorr + 32] = (float)kl;
-    (*bout)[kOutcCorr + 33] = (float)kr;
-    return true;
+    // The composed layer (outc2_role): fragments 0-3 on h, 4-6 on x, no slot repeated.
+    return pack_outc_layer(s, 16, kOutcUnit0, 4, kOutcF - 4, outc_slot, kOutcBias, kOutcCorr, wout, bout, range_ok);
 }
 
 }  // namespace m2
