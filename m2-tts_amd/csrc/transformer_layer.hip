@@ -94,16 +94,6 @@ __device__ unsigned long long g_tfl_stamps[4096][8][16];
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef vx_u32x4 u32x4;
 
-// Diagnostic builds only (-DTFL_DIAG=bits, tools/runs): attention_qsplit2's
-// lean path without 1 its global K / V loads after step 2, 2 its softmax
-// VALU, 4 its LDS stores, 8 its QK^T MFMAs, 16 its PV MFMAs - the
-// per-step time each piece holds (results are garbage; never the product).
-#ifndef TFL_DIAG
-#define TFL_DIAG 0
-#endif
-#ifndef TFL_STAGE_FIRST  // A/B builds: 0 = a step's staging after its K fragment reads
-#define TFL_STAGE_FIRST 1  // (0: decoder layers +4.5 % at B=128 T=2600, profiles/r04/r04i_stage_order.txt)
-#endif
 constexpr float kLog2e = 1.4426950408889634f;
 constexpr float kLazyT = 8.f;  // unmasked lazy rescale: weights stay <= 2^kLazyT
 constexpr int TQ = 16;         // rows (queries) per workgroup
@@ -431,6 +421,285 @@ __device__ __forceinline__ void claim_tile(int B, int ntile, unsigned* __restric
 }
 
 // ---------------------------------------------------------------------------
+// The attention kit: what attention_tile, attention_qsplit2 and
+// attention_quarters below share, each piece written once.  A block is 16
+// queries (or 16 keys), a chunk 32 keys (two key blocks u = 0, 1); a chunk's
+// scores of one query block are s[u][r]: key k0 + 16 u + 4 g + r of query li
+// (lane = 16 g + li), base 2.  The bodies differ in their wave mapping, their
+// loop schedule, their choice of the rules below and their merge.
+// (attention_qsplit still spells the same steps out by hand: rebuilt on the
+// kit it returned NaN at head_dim 16, bit-equal at 32 and 48, cause not found;
+// tests/test_gpu_tf_layer.py::test_head_dim_16_on_64_row_tiles pins it.)
+template <int V>
+struct CI {  // a compile-time index passed by value
+    static constexpr int value = V;
+};
+
+// The Q^T fragments (B operand) of one 16-query block at blk: lane (query li,
+// dims 32 ks + 8 g .. + 7); the tail step's planes are stored for lane groups
+// 0, 1 only, groups 2, 3 hold zeros - or, BOTH (attention_quarters' two-MFMA
+// tail), xh's groups 2, 3 repeat the hi plane.
+template <int HD>
+struct QFrag {
+    using G = Geo<HD>;
+    u32x4 h[G::KSA], l[G::KSA], xh, xl;
+    template <bool BOTH = false>
+    __device__ __forceinline__ void load(const unsigned char* blk, int lane) {
+        const unsigned char* qp = blk + 16 * lane;
+#pragma unroll
+        for (int ks = 0; ks < G::KS; ++ks) {
+            h[ks] = *reinterpret_cast<const u32x4*>(qp + 2048 * ks);
+            l[ks] = *reinterpret_cast<const u32x4*>(qp + 2048 * ks + 1024);
+        }
+        if constexpr (G::KT) {
+            const u32x4 z = u32x4{0u, 0u, 0u, 0u};
+            if constexpr (BOTH) xh = *reinterpret_cast<const u32x4*>(qp - 16 * lane + 16 * (lane & 31) + G::TAIL);
+            else xh = lane < 32 ? *reinterpret_cast<const u32x4*>(qp + G::TAIL) : z;
+            xl = lane < 32 ? *reinterpret_cast<const u32x4*>(qp + G::TAIL + 512) : z;
+        }
+    }
+};
+// The K fragments (A operand) of one 16-key block, and a chunk's V^T fragments.
+template <int HD>
+struct KFrag {
+    using G = Geo<HD>;
+    u32x4 h[G::KSA], l[G::KSA], xh, xl;
+    // from a block staged in LDS; the lanes of groups 2, 3 read other tail
+    // bytes: their Q operand is zero
+    __device__ __forceinline__ void load_lds(const unsigned char* blk, int lane) {
+        const unsigned char* kp = blk + 16 * lane;
+#pragma unroll
+        for (int ks = 0; ks < G::KS; ++ks) {
+            h[ks] = *reinterpret_cast<const u32x4*>(kp + 2048 * ks);
+            l[ks] = *reinterpret_cast<const u32x4*>(kp + 2048 * ks + 1024);
+        }
+        if constexpr (G::KT) {
+            xh = *reinterpret_cast<const u32x4*>(kp + G::TAIL);
+            xl = *reinterpret_cast<const u32x4*>(kp + G::TAIL + 512 - 512 * (lane >> 5));
+        }
+    }
+};
+template <int MT>
+struct VFrag {
+    u32x4 h[MT], l[MT];
+    __device__ __forceinline__ void load_lds(const unsigned char* chunk, int lane) {
+        const unsigned char* vp = chunk + 16 * lane;
+#pragma unroll
+        for (int t = 0; t < MT; ++t) {
+            h[t] = *reinterpret_cast<const u32x4*>(vp + t * 2048);
+            l[t] = *reinterpret_cast<const u32x4*>(vp + t * 2048 + 1024);
+        }
+    }
+};
+
+// S^T += K . Q^T of one key block against NB query blocks, every fp32 product
+// as kh.qh + kh.ql + kl.qh: the 32-dim k-steps (k-step outer, query block
+// inner), and with the 16-dim tail step (K = 32 MFMAs on zero-padded
+// operands: the chaining hazard in the layout comment above).
+template <int HD, int NB>
+__device__ __forceinline__ void qk_steps(const KFrag<HD>& k, const QFrag<HD>* q, f32x4 (&st)[NB]) {
+#pragma unroll
+    for (int ks = 0; ks < Geo<HD>::KS; ++ks)
+#pragma unroll
+        for (int qq = 0; qq < NB; ++qq) {
+            st[qq] = mfma(k.h[ks], q[qq].h[ks], st[qq]);
+            st[qq] = mfma(k.h[ks], q[qq].l[ks], st[qq]);
+            st[qq] = mfma(k.l[ks], q[qq].h[ks], st[qq]);
+        }
+}
+template <int HD, int NB>
+__device__ __forceinline__ void qk_block(const KFrag<HD>& k, const QFrag<HD>* q, f32x4 (&st)[NB]) {
+    qk_steps<HD, NB>(k, q, st);
+    if constexpr (Geo<HD>::KT)
+#pragma unroll
+        for (int qq = 0; qq < NB; ++qq) {
+            st[qq] = mfma(k.xh, q[qq].xh, st[qq]);
+            st[qq] = mfma(k.xh, q[qq].xl, st[qq]);
+            st[qq] = mfma(k.xl, q[qq].xh, st[qq]);
+        }
+}
+
+// Masked scores of the chunk from key k0 (g: the lane's group): scores * scale,
+// masked keys exactly the -1e9 fill, keys past N -inf.  Unmasked, a chunk that
+// straddles N is clipped: keys past N score -inf.
+__device__ __forceinline__ void mask_scores(float (&s)[2][4], int k0, int g, int len, int N, float sl2) {
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int key = k0 + 16 * u + 4 * g + r;
+            s[u][r] = key < len ? s[u][r] * sl2 : (key < N ? kMaskFill * kLog2e : -INFINITY);
+        }
+}
+__device__ __forceinline__ void clip_scores(float (&s)[2][4], int k0, int g, int N) {
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) s[u][r] = k0 + 16 * u + 4 * g + r < N ? s[u][r] : -INFINITY;
+}
+__device__ __forceinline__ float max8(const float (&s)[2][4]) {
+    return fmaxf(fmaxf(fmaxf(s[0][0], s[0][1]), fmaxf(s[0][2], s[0][3])),
+                 fmaxf(fmaxf(s[1][0], s[1][1]), fmaxf(s[1][2], s[1][3])));
+}
+__device__ __forceinline__ void sub_scores(float (&s)[2][4], float d) {
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) s[u][r] -= d;
+}
+// The scores become the weights 2^s, added to the lane's row sum in key order.
+template <bool SUM = true>
+__device__ __forceinline__ void exp_scores(float (&s)[2][4], float& lsum) {
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            s[u][r] = __builtin_amdgcn_exp2f(s[u][r]);
+            if constexpr (SUM) lsum += s[u][r];
+        }
+}
+// B = P^T as split f16: lane (query li) holds keys 4g + e (u = 0) and
+// 16 + 4g + e (u = 1), the key order of the V^T layout.
+__device__ __forceinline__ void p_fragments(const float (&p)[2][4], u32x4& bh, u32x4& bl) {
+    unsigned ph[4], pl[4];
+    split2u(p[0][0], p[0][1], ph[0], pl[0]);
+    split2u(p[0][2], p[0][3], ph[1], pl[1]);
+    split2u(p[1][0], p[1][1], ph[2], pl[2]);
+    split2u(p[1][2], p[1][3], ph[3], pl[3]);
+    bh = u32x4{ph[0], ph[1], ph[2], ph[3]};
+    bl = u32x4{pl[0], pl[1], pl[2], pl[3]};
+}
+// O^T += V^T . P^T of NB query blocks, as vh.bh + vh.bl + vl.bh (d-block
+// outer, query block inner: a V^T fragment feeds every block).
+template <int MT, int NB>
+__device__ __forceinline__ void pv_block(const VFrag<MT>& v, const u32x4* bh, const u32x4* bl, f32x4 (*acc)[MT]) {
+#pragma unroll
+    for (int t = 0; t < MT; ++t)
+#pragma unroll
+        for (int qq = 0; qq < NB; ++qq) {
+            acc[qq][t] = mfma(v.h[t], bh[qq], acc[qq][t]);
+            acc[qq][t] = mfma(v.h[t], bl[qq], acc[qq][t]);
+            acc[qq][t] = mfma(v.l[t], bh[qq], acc[qq][t]);
+        }
+}
+// Row sums by the matrix core: P_hi + P_lo against an all-ones A fragment,
+// complete over the chunk's keys in every lane of the query.
+__device__ __forceinline__ void ones_sum(u32x4 bh, u32x4 bl, f32x4& lacc) {
+    const u32x4 ones = u32x4{0x3C003C00u, 0x3C003C00u, 0x3C003C00u, 0x3C003C00u};  // f16 1.0 x 8
+    lacc = mfma(ones, bh, lacc);
+    lacc = mfma(ones, bl, lacc);
+}
+
+// The softmax base rules, each for one query block with its row sum l (the
+// fp32 lane sum, or the accumulator of ones_sum) and output accumulators; the
+// wave-uniform decision to move a base (a ballot over all of a wave's blocks)
+// is the caller's.
+template <int MT, typename L>
+__device__ __forceinline__ void scale_block(L& l, f32x4 (&acc)[MT], float corr) {
+    l *= corr;
+#pragma unroll
+    for (int t = 0; t < MT; ++t) acc[t] *= corr;
+}
+// Masked: the online maximum (m = -inf before the first chunk: corr = 0).
+// The caller subtracts the new m from the scores.
+template <int MT, typename L>
+__device__ __forceinline__ void masked_base(float cmax, float& m, L& l, f32x4 (&acc)[MT]) {
+    const float mn = vmax(m, grp4_max(cmax));
+    scale_block(l, acc, __builtin_amdgcn_exp2f(m - mn));
+    m = mn;
+}
+// Unmasked, lazy (attention_split_kernel): the base moves only on the wave's
+// first chunk or when a score exceeds it by more than kLazyT, so the weights
+// stay <= 2^kLazyT.  cmax is finite: every chunk processed has a live key.
+// Absolute scores (the caller subtracts m afterwards):
+template <int MT, typename L>
+__device__ __forceinline__ void lazy_base_abs(bool fresh, float cmax, float& m, L& l, f32x4 (&acc)[MT]) {
+    const float cm = grp4_max(cmax);
+    const float mn = fresh ? cm : vmax(cm, m);
+    if (!fresh) scale_block(l, acc, __builtin_amdgcn_exp2f(m - mn));
+    m = mn;
+}
+// Scores relative to the base already (the QK^T chain started from C = -m):
+// returns the move, which the caller subtracts from the scores.
+template <int MT, typename L>
+__device__ __forceinline__ float lazy_base_rel(bool fresh, float cmax, float& m, L& l, f32x4 (&acc)[MT]) {
+    const float cm = grp4_max(cmax);
+    const float d = fresh ? cm : vmax(cm, 0.f);
+    m += d;
+    if (!fresh) scale_block(l, acc, __builtin_amdgcn_exp2f(-d));
+    return d;
+}
+
+// Lean unmasked softmax: true when a weight of the step exceeds 2^kLazyT,
+// read from the f16 hi halves of P (8 packed words).  The weights are >= 0,
+// so an f16 hi half orders as its bit pattern: packed u16 maxima compared with
+// the bits of 2^kLazyT, which also catches +inf (0x7C00) and NaN (0x7Exx).
+// (The earlier f16 form - packed f16 maxima converted to f32 and compared -
+// missed a +inf hi half on gfx950: a weight past 65504, i.e. a later chunk's
+// score more than 16 above the base, went unmoved and the output became NaN;
+// tests/test_gpu_range.py::test_attention_scores_past_f16_range.)
+__device__ __forceinline__ bool p_hi_exceeds(u32x4 a, u32x4 b) {
+    typedef unsigned short u2 __attribute__((ext_vector_type(2)));
+    auto h = [](unsigned w) { return __builtin_bit_cast(u2, w); };
+    u2 mx = __builtin_elementwise_max(h(a[0]), h(a[1]));
+    mx = __builtin_elementwise_max(mx, __builtin_elementwise_max(h(a[2]), h(a[3])));
+    mx = __builtin_elementwise_max(mx, __builtin_elementwise_max(h(b[0]), h(b[1])));
+    mx = __builtin_elementwise_max(mx, __builtin_elementwise_max(h(b[2]), h(b[3])));
+    static_assert(kLazyT == 8.f, "the bit pattern below is f16 256.0");
+    constexpr unsigned short lim = 0x5C00;  // f16 256.0
+    return mx.x > lim || mx.y > lim;
+}
+// The lean step over two score sets (two blocks' chunk, or the two chunks of
+// one block's 64-key step), the scores relative to the base already.  The
+// wave's first chunk sets the base from the maximum; later the base moves
+// only when some weight exceeds 2^kLazyT, detected AFTER the exponentials on
+// the f16 hi halves of P (packed maxima: ~10 VALU in place of the ~23 of a
+// per-score maximum before them); then, rarely, the exponentials are
+// recomputed from the kept scores.  move(first) moves the bases and the
+// scores (lean_base); esum, if given, takes each set's fp32 lane sum of the
+// weights (the other way to the row sums is ones_sum on the fragments).
+template <typename Move>
+__device__ __forceinline__ void lean_step(float (&s)[2][2][4], bool first, u32x4 (&bh)[2], u32x4 (&bl)[2], Move move,
+                                          float* esum = nullptr) {
+    auto exp_split = [&]() {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            float e[2][4];
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) e[u][r] = __builtin_amdgcn_exp2f(s[i][u][r]);
+            if (esum) esum[i] = ((e[0][0] + e[0][1]) + (e[0][2] + e[0][3])) + ((e[1][0] + e[1][1]) + (e[1][2] + e[1][3]));
+            p_fragments(e, bh[i], bl[i]);
+        }
+    };
+    if (first) move(true);  // wave-uniform
+    exp_split();
+    if (__builtin_amdgcn_ballot_w64(p_hi_exceeds(bh[0], bh[1])) != 0) {  // wave-uniform, rare
+        move(false);
+        exp_split();
+    }
+}
+// One block's base in the lean step: the maximum itself on the first chunk,
+// else up by max(maximum, 0) with the sums scaled.  set_base(v) stores the
+// base; where it rounds v (RND: form 12's f16-pair base) the move is read
+// back from the stored base.  Returns what the block's scores lose.
+template <bool RND, int MT, typename L, typename SetBase>
+__device__ __forceinline__ float lean_base(bool first, float cmax, const float& m, L& l, f32x4 (&acc)[MT],
+                                           SetBase set_base) {
+    const float cm = grp4_max(cmax);
+    if (first) {
+        set_base(cm);
+        return m;
+    }
+    const float mold = m, up = vmax(cm, 0.f);
+    set_base(mold + up);
+    const float d = RND ? m - mold : up;
+    scale_block(l, acc, __builtin_amdgcn_exp2f(-d));
+    return d;
+}
+
+// ---------------------------------------------------------------------------
 // Attention of the tile's 16 RB queries (RB 16-query blocks share every K / V
 // fragment), both heads, over all N keys.  Leaves the normalised output rows
 // as split LDS rows A [16 RB][srs(H)] (the out projection's B operand).  The
@@ -441,36 +710,24 @@ __device__ __forceinline__ void attention_tile(const unsigned char* __restrict__
                                                const unsigned char* __restrict__ vb, int b, int t0, int N, int npad,
                                                int len, float sl2, unsigned char* A, float* xs, Between between) {
     using G = Geo<HD>;
-    constexpr int KS = G::KS, KSA = G::KSA, KT = G::KT, MT = G::MT, QKBLK = G::QKBLK, VCH = G::VCH, XW = G::XW;
+    constexpr int KS = G::KS, KT = G::KT, MT = G::MT, QKBLK = G::QKBLK, VCH = G::VCH, XW = G::XW;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 15, g = lane >> 4;
     const int h = wave / WPH, kq = wave - h * WPH;
     const int nch = npad / KC, nchl = (N + KC - 1) / KC;  // layout chunks, chunks holding live keys
     const size_t bh = (size_t)__builtin_amdgcn_readfirstlane(b * HEADS + h);
 
-    // B = Q^T fragments: lane (query li of block qt, dims 32 ks + 8 g .. + 7)
-    u32x4 qh[RB][KSA], ql[RB][KSA], qxh[RB], qxl[RB];
+    QFrag<HD> qf[RB];
 #pragma unroll
-    for (int qt = 0; qt < RB; ++qt) {
-        const unsigned char* qp = qb + (bh * (npad / 16) + t0 / 16 + qt) * QKBLK + 16 * lane;
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            qh[qt][ks] = *reinterpret_cast<const u32x4*>(qp + 2048 * ks);
-            ql[qt][ks] = *reinterpret_cast<const u32x4*>(qp + 2048 * ks + 1024);
-        }
-        if constexpr (KT) {
-            const u32x4 z = u32x4{0u, 0u, 0u, 0u};
-            qxh[qt] = lane < 32 ? *reinterpret_cast<const u32x4*>(qp + G::TAIL) : z;
-            qxl[qt] = lane < 32 ? *reinterpret_cast<const u32x4*>(qp + G::TAIL + 512) : z;
-        }
-    }
+    for (int qt = 0; qt < RB; ++qt) qf[qt].load(qb + (bh * (npad / 16) + t0 / 16 + qt) * QKBLK, lane);
     // Chunk c's K fragments and V^T fragments through a buffer descriptor whose
     // record count is 0 past the last chunk: the prefetch of a chunk that does
     // not exist is issued unconditionally (no branch around a load, so the
     // compiler's vmcnt waits stay graded) and reads zeros without traffic.
     const int loff = 16 * lane, toff = tail_off(lane);
     struct Frag {
-        u32x4 kh[2][KSA], kl[2][KSA], kxh[2], kxl[2], vh[MT], vl[MT];
+        KFrag<HD> k[2];
+        VFrag<MT> v;
     };
     auto load = [&](Frag& f, int c) {
         const bool ok = c < nchl;
@@ -483,23 +740,23 @@ __device__ __forceinline__ void attention_tile(const unsigned char* __restrict__
         for (int u = 0; u < 2; ++u)
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
-                f.kh[u][ks] = __builtin_bit_cast(
+                f.k[u].h[ks] = __builtin_bit_cast(
                     u32x4, __builtin_amdgcn_raw_buffer_load_b128(rk, loff + u * QKBLK + 2048 * ks, 0, 0));
-                f.kl[u][ks] = __builtin_bit_cast(
+                f.k[u].l[ks] = __builtin_bit_cast(
                     u32x4, __builtin_amdgcn_raw_buffer_load_b128(rk, loff + u * QKBLK + 2048 * ks + 1024, 0, 0));
             }
         if constexpr (KT)
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
-                f.kxh[u] = __builtin_bit_cast(
+                f.k[u].xh = __builtin_bit_cast(
                     u32x4, __builtin_amdgcn_raw_buffer_load_b128(rk, toff, u * QKBLK + G::TAIL, 0));
-                f.kxl[u] = __builtin_bit_cast(
+                f.k[u].xl = __builtin_bit_cast(
                     u32x4, __builtin_amdgcn_raw_buffer_load_b128(rk, toff, u * QKBLK + G::TAIL + 512, 0));
             }
 #pragma unroll
         for (int t = 0; t < MT; ++t) {
-            f.vh[t] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rv, loff + t * 2048, 0, 0));
-            f.vl[t] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rv, loff + t * 2048 + 1024, 0, 0));
+            f.v.h[t] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rv, loff + t * 2048, 0, 0));
+            f.v.l[t] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rv, loff + t * 2048 + 1024, 0, 0));
         }
     };
 
@@ -515,67 +772,34 @@ __device__ __forceinline__ void attention_tile(const unsigned char* __restrict__
     bool fresh = true;  // unmasked: no chunk processed yet (wave-uniform)
 
     auto process = [&](const Frag& f, int c) {
-        float s[RB][2][4];  // key 32 c + 16 u + 4 g + r of query li of block qt (base-2 score)
+        float s[RB][2][4];
 #pragma unroll
         for (int qt = 0; qt < RB; ++qt) {
-            const float nm = (MASKED || fresh) ? 0.f : -m[qt];
+            const float nm = (MASKED || fresh) ? 0.f : -m[qt];  // unmasked: scores relative to the base
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
-                f32x4 st = f32x4{nm, nm, nm, nm};
+                f32x4 st[1] = {f32x4{nm, nm, nm, nm}};
+                qk_block<HD, 1>(f.k[u], &qf[qt], st);
 #pragma unroll
-                for (int ks = 0; ks < KS; ++ks) {
-                    st = mfma(f.kh[u][ks], qh[qt][ks], st);
-                    st = mfma(f.kh[u][ks], ql[qt][ks], st);
-                    st = mfma(f.kl[u][ks], qh[qt][ks], st);
-                }
-                if constexpr (KT) {
-                    st = mfma(f.kxh[u], qxh[qt], st);
-                    st = mfma(f.kxh[u], qxl[qt], st);
-                    st = mfma(f.kxl[u], qxh[qt], st);
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r) s[qt][u][r] = st[r];
+                for (int r = 0; r < 4; ++r) s[qt][u][r] = st[0][r];
             }
         }
         const int k0 = c * KC;
-        if constexpr (MASKED) {
-            // scores * scale, masked keys exactly the -1e9 fill, keys past N -inf
-#pragma unroll
-            for (int u = 0; u < 2; ++u)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int key = k0 + 16 * u + 4 * g + r;
-#pragma unroll
-                    for (int qt = 0; qt < RB; ++qt)
-                        s[qt][u][r] = key < len ? s[qt][u][r] * sl2 : (key < N ? kMaskFill * kLog2e : -INFINITY);
-                }
-        } else if (N - k0 < KC) {  // the last chunk: keys past N score -inf (wave-uniform)
-#pragma unroll
-            for (int u = 0; u < 2; ++u)
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-#pragma unroll
-                    for (int qt = 0; qt < RB; ++qt)
-                        s[qt][u][r] = k0 + 16 * u + 4 * g + r < N ? s[qt][u][r] : -INFINITY;
-        }
         float cmax[RB];
+        if constexpr (MASKED) {
 #pragma unroll
-        for (int qt = 0; qt < RB; ++qt)
-            cmax[qt] = fmaxf(fmaxf(fmaxf(s[qt][0][0], s[qt][0][1]), fmaxf(s[qt][0][2], s[qt][0][3])),
-                             fmaxf(fmaxf(s[qt][1][0], s[qt][1][1]), fmaxf(s[qt][1][2], s[qt][1][3])));
+            for (int qt = 0; qt < RB; ++qt) mask_scores(s[qt], k0, g, len, N, sl2);
+        } else if (N - k0 < KC) {  // the last chunk (wave-uniform)
+#pragma unroll
+            for (int qt = 0; qt < RB; ++qt) clip_scores(s[qt], k0, g, N);
+        }
+#pragma unroll
+        for (int qt = 0; qt < RB; ++qt) cmax[qt] = max8(s[qt]);
         if constexpr (MASKED) {
 #pragma unroll
             for (int qt = 0; qt < RB; ++qt) {
-                const float mn = vmax(m[qt], grp4_max(cmax[qt]));
-                const float corr = __builtin_amdgcn_exp2f(m[qt] - mn);  // m = -inf on the first chunk -> 0
-                lsum[qt] *= corr;
-#pragma unroll
-                for (int t = 0; t < MT; ++t) acc[qt][t] *= corr;
-#pragma unroll
-                for (int u = 0; u < 2; ++u)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) s[qt][u][r] -= mn;
-                m[qt] = mn;
+                masked_base(cmax[qt], m[qt], lsum[qt], acc[qt]);
+                sub_scores(s[qt], m[qt]);
             }
         } else {
             bool up = fresh;
@@ -583,51 +807,17 @@ __device__ __forceinline__ void attention_tile(const unsigned char* __restrict__
             for (int qt = 0; qt < RB; ++qt) up = up || cmax[qt] > kLazyT;
             if (__builtin_amdgcn_ballot_w64(up) != 0) {  // wave-uniform: move the base
 #pragma unroll
-                for (int qt = 0; qt < RB; ++qt) {
-                    const float cm = grp4_max(cmax[qt]);  // finite: every chunk has a live key
-                    const float d = fresh ? cm : vmax(cm, 0.f);
-                    m[qt] += d;
-                    if (!fresh) {
-                        const float corr = __builtin_amdgcn_exp2f(-d);
-                        lsum[qt] *= corr;
-#pragma unroll
-                        for (int t = 0; t < MT; ++t) acc[qt][t] *= corr;
-                    }
-#pragma unroll
-                    for (int u = 0; u < 2; ++u)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) s[qt][u][r] -= d;
-                }
+                for (int qt = 0; qt < RB; ++qt) sub_scores(s[qt], lazy_base_rel(fresh, cmax[qt], m[qt], lsum[qt], acc[qt]));
             }
             fresh = false;
         }
         u32x4 bh4[RB], bl4[RB];
 #pragma unroll
         for (int qt = 0; qt < RB; ++qt) {
-#pragma unroll
-            for (int u = 0; u < 2; ++u)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    s[qt][u][r] = __builtin_amdgcn_exp2f(s[qt][u][r]);
-                    lsum[qt] += s[qt][u][r];
-                }
-            // B = P^T: lane (query li) holds keys 4g + e (u = 0) and 16 + 4g + e (u = 1)
-            unsigned ph[4], pl[4];
-            split2u(s[qt][0][0], s[qt][0][1], ph[0], pl[0]);
-            split2u(s[qt][0][2], s[qt][0][3], ph[1], pl[1]);
-            split2u(s[qt][1][0], s[qt][1][1], ph[2], pl[2]);
-            split2u(s[qt][1][2], s[qt][1][3], ph[3], pl[3]);
-            bh4[qt] = u32x4{ph[0], ph[1], ph[2], ph[3]};
-            bl4[qt] = u32x4{pl[0], pl[1], pl[2], pl[3]};
+            exp_scores(s[qt], lsum[qt]);
+            p_fragments(s[qt], bh4[qt], bl4[qt]);
         }
-#pragma unroll
-        for (int t = 0; t < MT; ++t)
-#pragma unroll
-            for (int qt = 0; qt < RB; ++qt) {
-                acc[qt][t] = mfma(f.vh[t], bh4[qt], acc[qt][t]);
-                acc[qt][t] = mfma(f.vh[t], bl4[qt], acc[qt][t]);
-                acc[qt][t] = mfma(f.vl[t], bh4[qt], acc[qt][t]);
-            }
+        pv_block<MT, RB>(f.v, bh4, bl4, acc);
     };
 
     // chunks kq, kq + 4, ... through a two-slot register ring.  The scheduling
@@ -740,25 +930,6 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t wave_rsrc(const unsigned char*
     const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)((uintptr_t)base >> 32));
     void* p = reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo);
     return __builtin_amdgcn_make_buffer_rsrc(p, 0, 0x7ffffff0, 0x00020000);
-}
-// Lean unmasked softmax: true when a weight of the step exceeds 2^kLazyT,
-// read from the f16 hi halves of P (8 packed words).  The weights are >= 0,
-// so an f16 hi half orders as its bit pattern: packed u16 maxima compared with
-// the bits of 2^kLazyT, which also catches +inf (0x7C00) and NaN (0x7Exx).
-// (The earlier f16 form - packed f16 maxima converted to f32 and compared -
-// missed a +inf hi half on gfx950: a weight past 65504, i.e. a later chunk's
-// score more than 16 above the base, went unmoved and the output became NaN;
-// tests/test_gpu_range.py::test_attention_scores_past_f16_range.)
-__device__ __forceinline__ bool p_hi_exceeds(u32x4 a, u32x4 b) {
-    typedef unsigned short u2 __attribute__((ext_vector_type(2)));
-    auto h = [](unsigned w) { return __builtin_bit_cast(u2, w); };
-    u2 mx = __builtin_elementwise_max(h(a[0]), h(a[1]));
-    mx = __builtin_elementwise_max(mx, __builtin_elementwise_max(h(a[2]), h(a[3])));
-    mx = __builtin_elementwise_max(mx, __builtin_elementwise_max(h(b[0]), h(b[1])));
-    mx = __builtin_elementwise_max(mx, __builtin_elementwise_max(h(b[2]), h(b[3])));
-    static_assert(kLazyT == 8.f, "the bit pattern below is f16 2^8");
-    constexpr unsigned short lim = 0x5C00;  // f16 256.0
-    return mx.x > lim || mx.y > lim;
 }
 
 // LEAN (M2_TFL_QS2=4): the lean softmax of attention_qsplit2 (C = -m
@@ -1070,54 +1241,39 @@ __device__ __forceinline__ void attention_qsplit(const unsigned char* __restrict
 // query pair) merge through LDS at the end (each finalises one block).  A
 // chunk wholly past N is skipped (wave-uniform), so a wave may see no key:
 // its record then carries m = -inf and weight 0.
-template <int V>
-struct CI {
-    static constexpr int value = V;
-};
-
+//
 // LEAN (M2_TFL_QS2=3): the softmax with fewer VALU instructions per step -
-// unmasked, the QK^T MFMAs start from C = -m (scores arrive relative to the
-// lazy base: no subtraction before exp2), and the row sums come from two more
-// MFMAs on a constant all-ones A fragment (P_hi + P_lo summed by the matrix
-// core, already complete over the chunk's keys) instead of 16 adds per step.
+// the row sums come from two more MFMAs on a constant all-ones A fragment
+// (ones_sum: P_hi + P_lo summed by the matrix core, already complete over the
+// chunk's keys) instead of 16 adds per step, and, unmasked, the QK^T MFMAs
+// start from C = -m (scores arrive relative to the lazy base: no subtraction
+// before exp2; lean_step).
 template <int H, int HD, bool MASKED, bool LEAN = false>
 __device__ __forceinline__ void attention_qsplit2(const unsigned char* __restrict__ qb, const unsigned char* __restrict__ kb,
                                                   const unsigned char* __restrict__ vb, int b, int t0, int N, int npad,
                                                   int len, float sl2, unsigned char* A, unsigned char* ring) {
     using G = Geo<HD>;
     using Q = QsGeo<HD>;
-    constexpr int KS = G::KS, KSA = G::KSA, KT = G::KT, MT = G::MT, QKBLK = G::QKBLK, CB = Q::CB, SB = Q::SB;
-    constexpr int PPT = Q::PPT, RW = 2 + 4 * MT;  // merge record floats per lane
+    constexpr int MT = G::MT, QKBLK = G::QKBLK, CB = Q::CB, SB = Q::SB, PPT = Q::PPT;
+    constexpr int RW = 2 + 4 * MT;  // merge record floats per lane
     static_assert(NW * RW * 64 * 4 <= 2 * SB, "merge records fit the ring");
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 15, g = lane >> 4;
     const int h = wave >> 2, qp = (wave >> 1) & 1, j = wave & 1;
-    const int nch = npad / KC, nsc = (N + 2 * KC - 1) / (2 * KC);
+    const int nsc = (N + 2 * KC - 1) / (2 * KC);
 
-    // B = Q^T fragments of this wave's two 16-query blocks 2 qp, 2 qp + 1
-    u32x4 qh[2][KSA], ql[2][KSA], qxh[2], qxl[2];
+    QFrag<HD> qf[2];  // this wave's two 16-query blocks 2 qp, 2 qp + 1
 #pragma unroll
-    for (int qq = 0; qq < 2; ++qq) {
-        const unsigned char* qp8 =
-            qb + ((size_t)(b * HEADS + h) * (npad / 16) + t0 / 16 + 2 * qp + qq) * QKBLK + 16 * lane;
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            qh[qq][ks] = *reinterpret_cast<const u32x4*>(qp8 + 2048 * ks);
-            ql[qq][ks] = *reinterpret_cast<const u32x4*>(qp8 + 2048 * ks + 1024);
-        }
-        if constexpr (KT) {
-            const u32x4 z = u32x4{0u, 0u, 0u, 0u};
-            qxh[qq] = lane < 32 ? *reinterpret_cast<const u32x4*>(qp8 + G::TAIL) : z;
-            qxl[qq] = lane < 32 ? *reinterpret_cast<const u32x4*>(qp8 + G::TAIL + 512) : z;
-        }
-    }
-    // the staging of a 64-key step into LDS: as attention_qsplit, but every
-    // piece through a buffer descriptor of its region (a wave's 1-KB piece
-    // lies in one K or V^T region: the region bytes are multiples of 1 KB),
-    // so a step's loads take the per-lane offset from a fixed VGPR and the
-    // step's advance from an SGPR - no 64-bit address arithmetic per step
+    for (int qq = 0; qq < 2; ++qq)
+        qf[qq].load(qb + ((size_t)(b * HEADS + h) * (npad / 16) + t0 / 16 + 2 * qp + qq) * QKBLK, lane);
+    // the global source of piece i (16 B) of 64-key step 0: [chunk][head][K blocks | V^T chunk],
+    // through a buffer descriptor of its region (a wave's 1-KB piece lies in
+    // one K or V^T region: the region bytes are multiples of 1 KB), so a
+    // step's loads take the per-lane offset from a fixed VGPR and the step's
+    // advance from an SGPR - no 64-bit address arithmetic per step
+    const int nch = npad / KC;
     __amdgpu_buffer_rsrc_t rsrc[PPT];
-    int voff[PPT], sstep[PPT];
+    int sstep[PPT];  // bytes from one 64-key step to the next for that piece
 #pragma unroll
     for (int i = 0; i < PPT; ++i) {
         const int o = 16 * (tid + NW * 64 * i), jj = o / CB, oc = o - jj * CB, hh = oc / Q::HB, r = oc - hh * Q::HB;
@@ -1126,14 +1282,13 @@ __device__ __forceinline__ void attention_qsplit2(const unsigned char* __restric
         const unsigned char* base = isk ? kb + (bh * (npad / 16) + 2 * jj) * QKBLK + (r & ~1023)
                                         : vb + (bh * nch + jj) * G::VCH + ((r - Q::KB) & ~1023);
         rsrc[i] = wave_rsrc(base);
-        voff[i] = 16 * lane;
         sstep[i] = __builtin_amdgcn_readfirstlane(isk ? 4 * QKBLK : 2 * G::VCH);
     }
     u32x4 pre[PPT];
     auto gload = [&](int p) {
 #pragma unroll
         for (int i = 0; i < PPT; ++i)
-            pre[i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc[i], voff[i], p * sstep[i], 0));
+            pre[i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc[i], 16 * lane, p * sstep[i], 0));
     };
     auto lstore = [&](int buf) {
 #pragma unroll
@@ -1150,30 +1305,16 @@ __device__ __forceinline__ void attention_qsplit2(const unsigned char* __restric
         lsum[qq] = 0.f;
         lacc[qq] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
-    const u32x4 ones = u32x4{0x3C003C00u, 0x3C003C00u, 0x3C003C00u, 0x3C003C00u};  // f16 1.0 x 8
     bool fresh = true;  // no chunk processed yet (wave-uniform)
 
     // keys 64 p + 32 j + 16 u + 4 g + r of query li of block qq
-    // stage: the next steps' staging (LDS stores, global loads), issued
-    // before this chunk's K fragment reads (TFL_STAGE_FIRST, the default) or
-    // after them (measured slower)
-    auto process = [&](const unsigned char* sb, int p, auto&& stage) {
+    auto process = [&](const unsigned char* sb, int p) {
+        const int k0 = p * 2 * KC + j * KC;
+        if (k0 >= N) return;  // the chunk lies wholly past N (wave-uniform)
         float s[2][2][4];
-        u32x4 kf[2][KSA][2], kx[2][2];
+        KFrag<HD> k[2];
 #pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const unsigned char* kp = sb + j * CB + h * Q::HB + u * QKBLK + 16 * lane;
-#pragma unroll
-            for (int ks = 0; ks < KS * !(TFL_DIAG & 8); ++ks) {
-                kf[u][ks][0] = *reinterpret_cast<const u32x4*>(kp + 2048 * ks);
-                kf[u][ks][1] = *reinterpret_cast<const u32x4*>(kp + 2048 * ks + 1024);
-            }
-            if constexpr (KT && !(TFL_DIAG & 8)) {  // lanes of groups 2, 3 read other tail bytes: their Q operand is zero
-                kx[u][0] = *reinterpret_cast<const u32x4*>(kp + G::TAIL);
-                kx[u][1] = *reinterpret_cast<const u32x4*>(kp + G::TAIL + 512 - 512 * (lane >> 5));
-            }
-        }
-        if constexpr (!TFL_STAGE_FIRST) stage();
+        for (int u = 0; u < 2; ++u) k[u].load_lds(sb + j * CB + h * Q::HB + u * QKBLK, lane);
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             f32x4 st[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
@@ -1181,261 +1322,74 @@ __device__ __forceinline__ void attention_qsplit2(const unsigned char* __restric
                 if (!fresh)
 #pragma unroll
                     for (int qq = 0; qq < 2; ++qq) st[qq] = f32x4{-m[qq], -m[qq], -m[qq], -m[qq]};
-#pragma unroll
-            for (int ks = 0; ks < KS * !(TFL_DIAG & 8); ++ks) {
-#pragma unroll
-                for (int qq = 0; qq < 2; ++qq) {
-                    st[qq] = mfma(kf[u][ks][0], qh[qq][ks], st[qq]);
-                    st[qq] = mfma(kf[u][ks][0], ql[qq][ks], st[qq]);
-                    st[qq] = mfma(kf[u][ks][1], qh[qq][ks], st[qq]);
-                }
-            }
-            if constexpr (KT && !(TFL_DIAG & 8)) {
-#pragma unroll
-                for (int qq = 0; qq < 2; ++qq) {
-                    st[qq] = mfma(kx[u][0], qxh[qq], st[qq]);
-                    st[qq] = mfma(kx[u][0], qxl[qq], st[qq]);
-                    st[qq] = mfma(kx[u][1], qxh[qq], st[qq]);
-                }
-            }
+            qk_block<HD, 2>(k[u], qf, st);
 #pragma unroll
             for (int qq = 0; qq < 2; ++qq)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) s[qq][u][r] = st[qq][r];
         }
-        const int k0 = p * 2 * KC + j * KC;
         if constexpr (MASKED) {
 #pragma unroll
-            for (int u = 0; u < 2; ++u)
+            for (int qq = 0; qq < 2; ++qq) mask_scores(s[qq], k0, g, len, N, sl2);
+        } else if (N - k0 < KC) {  // the chunk straddles N (wave-uniform)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int key = k0 + 16 * u + 4 * g + r;
-#pragma unroll
-                    for (int qq = 0; qq < 2; ++qq)
-                        s[qq][u][r] = key < len ? s[qq][u][r] * sl2 : (key < N ? kMaskFill * kLog2e : -INFINITY);
-                }
-        } else if (N - k0 < KC) {  // the chunk straddles N: keys past N score -inf (wave-uniform)
-#pragma unroll
-            for (int u = 0; u < 2; ++u)
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-#pragma unroll
-                    for (int qq = 0; qq < 2; ++qq)
-                        s[qq][u][r] = k0 + 16 * u + 4 * g + r < N ? s[qq][u][r] : -INFINITY;
+            for (int qq = 0; qq < 2; ++qq) clip_scores(s[qq], k0, g, N);
         }
-        auto chunk_max = [&](int qq) {
-            return fmaxf(fmaxf(fmaxf(s[qq][0][0], s[qq][0][1]), fmaxf(s[qq][0][2], s[qq][0][3])),
-                         fmaxf(fmaxf(s[qq][1][0], s[qq][1][1]), fmaxf(s[qq][1][2], s[qq][1][3])));
-        };
+        u32x4 bh4[2], bl4[2];
         if constexpr (LEAN && !MASKED) {
-            // the scores arrive relative to the base.  First chunk: the base is
-            // the chunk's maximum.  Later: the base moves only when some weight
-            // exceeds 2^kLazyT, detected AFTER the exponentials on the f16 hi
-            // halves of P (packed maxima: ~10 VALU in place of the ~23 of a
-            // per-score maximum before them); then, rarely, the exponentials
-            // are recomputed from the kept scores.
-            if (fresh) {  // wave-uniform
+            lean_step(s, fresh, bh4, bl4, [&](bool first) {
 #pragma unroll
-                for (int qq = 0; qq < 2; ++qq) {
-                    const float cm = grp4_max(chunk_max(qq));  // finite: the chunk holds a key < N
-                    m[qq] = cm;
-#pragma unroll
-                    for (int u = 0; u < 2; ++u)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) s[qq][u][r] -= cm;
-                }
-                fresh = false;
-            }
-            u32x4 bh4[2], bl4[2];
-            auto exp_split = [&]() {
-#pragma unroll
-                for (int qq = 0; qq < 2; ++qq) {
-                    float e[2][4];
-#pragma unroll
-                    for (int u = 0; u < 2; ++u)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) e[u][r] = __builtin_amdgcn_exp2f(s[qq][u][r]);
-                    unsigned ph[4], pl[4];
-                    split2u(e[0][0], e[0][1], ph[0], pl[0]);
-                    split2u(e[0][2], e[0][3], ph[1], pl[1]);
-                    split2u(e[1][0], e[1][1], ph[2], pl[2]);
-                    split2u(e[1][2], e[1][3], ph[3], pl[3]);
-                    bh4[qq] = u32x4{ph[0], ph[1], ph[2], ph[3]};
-                    bl4[qq] = u32x4{pl[0], pl[1], pl[2], pl[3]};
-                }
-            };
-            if constexpr (TFL_DIAG & 2) {  // diagnostic: no softmax VALU (P = the scores' bits)
-#pragma unroll
-                for (int qq = 0; qq < 2; ++qq) {
-                    bh4[qq] = u32x4{__float_as_uint(s[qq][0][0]), __float_as_uint(s[qq][0][1]),
-                                    __float_as_uint(s[qq][0][2]), __float_as_uint(s[qq][0][3])};
-                    bl4[qq] = u32x4{__float_as_uint(s[qq][1][0]), __float_as_uint(s[qq][1][1]),
-                                    __float_as_uint(s[qq][1][2]), __float_as_uint(s[qq][1][3])};
-                }
-            } else
-                exp_split();
-            if constexpr (!(TFL_DIAG & 2)) {
-                if (__builtin_amdgcn_ballot_w64(p_hi_exceeds(bh4[0], bh4[1])) != 0) {  // wave-uniform: move the base
-#pragma unroll
-                    for (int qq = 0; qq < 2; ++qq) {
-                        const float d = vmax(grp4_max(chunk_max(qq)), 0.f);
-                        m[qq] += d;
-                        const float corr = __builtin_amdgcn_exp2f(-d);
-                        lacc[qq] *= corr;
-#pragma unroll
-                        for (int t = 0; t < MT; ++t) acc[qq][t] *= corr;
-#pragma unroll
-                        for (int u = 0; u < 2; ++u)
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) s[qq][u][r] -= d;
-                    }
-                    exp_split();
-                }
-            }
-#pragma unroll
-            for (int qq = 0; qq < 2; ++qq) {
-                lacc[qq] = mfma(ones, bh4[qq], lacc[qq]);
-                lacc[qq] = mfma(ones, bl4[qq], lacc[qq]);
-            }
-            const unsigned char* vp = sb + j * CB + h * Q::HB + Q::KB + 16 * lane;
-#pragma unroll
-            for (int t = 0; t < MT * !(TFL_DIAG & 16); ++t) {
-                const u32x4 vh = *reinterpret_cast<const u32x4*>(vp + t * 2048);
-                const u32x4 vl = *reinterpret_cast<const u32x4*>(vp + t * 2048 + 1024);
-#pragma unroll
-                for (int qq = 0; qq < 2; ++qq) {
-                    acc[qq][t] = mfma(vh, bh4[qq], acc[qq][t]);
-                    acc[qq][t] = mfma(vh, bl4[qq], acc[qq][t]);
-                    acc[qq][t] = mfma(vl, bh4[qq], acc[qq][t]);
-                }
-            }
-            if constexpr ((TFL_DIAG & 16) != 0)  // keep P live
-#pragma unroll
-                for (int qq = 0; qq < 2; ++qq) asm volatile("" ::"v"(bh4[qq]), "v"(bl4[qq]));
-            return;
-        }
-        float cmax[2];
-#pragma unroll
-        for (int qq = 0; qq < 2; ++qq) cmax[qq] = chunk_max(qq);
-        if constexpr (MASKED) {
-#pragma unroll
-            for (int qq = 0; qq < 2; ++qq) {
-                const float mn = vmax(m[qq], grp4_max(cmax[qq]));  // finite: the chunk holds a key < N
-                const float corr = __builtin_amdgcn_exp2f(m[qq] - mn);  // m = -inf on the first chunk -> 0
-                lsum[qq] *= corr;
-                if constexpr (LEAN) lacc[qq] *= corr;
-#pragma unroll
-                for (int t = 0; t < MT; ++t) acc[qq][t] *= corr;
-                m[qq] = mn;
-            }
-        } else if constexpr (LEAN) {
-            // scores relative to the base already: move it (and them) only on
-            // the first chunk or when one exceeds it by more than 2^kLazyT
-            bool up = fresh;
-#pragma unroll
-            for (int qq = 0; qq < 2; ++qq) up = up || cmax[qq] > kLazyT;
-            if (__builtin_amdgcn_ballot_w64(up) != 0) {
-#pragma unroll
-                for (int qq = 0; qq < 2; ++qq) {
-                    const float cm = grp4_max(cmax[qq]);  // finite: the chunk holds a key < N
-                    const float d = fresh ? cm : vmax(cm, 0.f);
-                    m[qq] += d;
-                    if (!fresh) {
-                        const float corr = __builtin_amdgcn_exp2f(-d);
-                        lacc[qq] *= corr;
-#pragma unroll
-                        for (int t = 0; t < MT; ++t) acc[qq][t] *= corr;
-                    }
-#pragma unroll
-                    for (int u = 0; u < 2; ++u)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) s[qq][u][r] -= d;
-                }
-            }
+                for (int qq = 0; qq < 2; ++qq)
+                    sub_scores(s[qq], lean_base<false>(first, max8(s[qq]), m[qq], lacc[qq], acc[qq],
+                                                       [&](float v) { m[qq] = v; }));
+            });
         } else {
-            // lazy base (attention_split_kernel): moved only on the first chunk or
-            // when a score exceeds it by more than 2^kLazyT (wave-uniform)
-            bool up = fresh;
+            float cmax[2];
 #pragma unroll
-            for (int qq = 0; qq < 2; ++qq) up = up || cmax[qq] - m[qq] > kLazyT;
-            if (__builtin_amdgcn_ballot_w64(up) != 0) {
+            for (int qq = 0; qq < 2; ++qq) cmax[qq] = max8(s[qq]);
+            if constexpr (MASKED) {
 #pragma unroll
                 for (int qq = 0; qq < 2; ++qq) {
-                    const float cm = grp4_max(cmax[qq]);  // finite: the chunk holds a key < N
-                    const float mn = fresh ? cm : vmax(cm, m[qq]);
-                    if (!fresh) {
-                        const float corr = __builtin_amdgcn_exp2f(m[qq] - mn);
-                        lsum[qq] *= corr;
-#pragma unroll
-                        for (int t = 0; t < MT; ++t) acc[qq][t] *= corr;
-                    }
-                    m[qq] = mn;
+                    if constexpr (LEAN) masked_base(cmax[qq], m[qq], lacc[qq], acc[qq]);
+                    else masked_base(cmax[qq], m[qq], lsum[qq], acc[qq]);
                 }
+            } else {
+                bool up = fresh;
+#pragma unroll
+                for (int qq = 0; qq < 2; ++qq) up = up || cmax[qq] - m[qq] > kLazyT;
+                if (__builtin_amdgcn_ballot_w64(up) != 0) {  // wave-uniform: move the bases
+#pragma unroll
+                    for (int qq = 0; qq < 2; ++qq) lazy_base_abs(fresh, cmax[qq], m[qq], lsum[qq], acc[qq]);
+                }
+            }
+#pragma unroll
+            for (int qq = 0; qq < 2; ++qq) {
+                sub_scores(s[qq], m[qq]);
+                exp_scores<!LEAN>(s[qq], lsum[qq]);
+                p_fragments(s[qq], bh4[qq], bl4[qq]);
             }
         }
         fresh = false;
-        u32x4 bh4[2], bl4[2];
-#pragma unroll
-        for (int qq = 0; qq < 2; ++qq) {
-#pragma unroll
-            for (int u = 0; u < 2; ++u)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    if constexpr (LEAN && !MASKED) {
-                        s[qq][u][r] = __builtin_amdgcn_exp2f(s[qq][u][r]);
-                    } else {
-                        s[qq][u][r] = __builtin_amdgcn_exp2f(s[qq][u][r] - m[qq]);
-                        if constexpr (!LEAN) lsum[qq] += s[qq][u][r];
-                    }
-                }
-            // B = P^T: lane (query li) holds keys 4g + e (u = 0) and 16 + 4g + e (u = 1)
-            unsigned ph[4], pl[4];
-            split2u(s[qq][0][0], s[qq][0][1], ph[0], pl[0]);
-            split2u(s[qq][0][2], s[qq][0][3], ph[1], pl[1]);
-            split2u(s[qq][1][0], s[qq][1][1], ph[2], pl[2]);
-            split2u(s[qq][1][2], s[qq][1][3], ph[3], pl[3]);
-            bh4[qq] = u32x4{ph[0], ph[1], ph[2], ph[3]};
-            bl4[qq] = u32x4{pl[0], pl[1], pl[2], pl[3]};
-        }
         if constexpr (LEAN)
 #pragma unroll
-            for (int qq = 0; qq < 2; ++qq) {
-                lacc[qq] = mfma(ones, bh4[qq], lacc[qq]);
-                lacc[qq] = mfma(ones, bl4[qq], lacc[qq]);
-            }
-        const unsigned char* vp = sb + j * CB + h * Q::HB + Q::KB + 16 * lane;
-#pragma unroll
-        for (int t = 0; t < MT; ++t) {
-            const u32x4 vh = *reinterpret_cast<const u32x4*>(vp + t * 2048);
-            const u32x4 vl = *reinterpret_cast<const u32x4*>(vp + t * 2048 + 1024);
-#pragma unroll
-            for (int qq = 0; qq < 2; ++qq) {
-                acc[qq][t] = mfma(vh, bh4[qq], acc[qq][t]);
-                acc[qq][t] = mfma(vh, bl4[qq], acc[qq][t]);
-                acc[qq][t] = mfma(vl, bh4[qq], acc[qq][t]);
-            }
-        }
+            for (int qq = 0; qq < 2; ++qq) ones_sum(bh4[qq], bl4[qq], lacc[qq]);
+        VFrag<MT> v;
+        v.load_lds(sb + j * CB + h * Q::HB + Q::KB, lane);
+        pv_block<MT, 2>(v, bh4, bl4, acc);
     };
-
+    // step p from buffer p & 1 while p + 1 goes to the other buffer and p + 2
+    // is requested, one barrier per step.  A step's staging is issued before
+    // its K fragment reads: after them it measured +4.5 % on the decoder layers
+    // at B=128 T=2600 (profiles/r04/r04i_stage_order.txt).
     gload(0);
     lstore(0);
     if (1 < nsc) gload(1);
     lds_barrier();
 #pragma unroll 1
     for (int p = 0; p < nsc; ++p) {
-        // step p from buffer p & 1; p + 1 goes to the other buffer, p + 2 is requested
-        auto stage = [&] {
-            if (p + 1 < nsc) {
-                if constexpr (!(TFL_DIAG & 4)) lstore((p + 1) & 1);
-                else
-#pragma unroll
-                    for (int i = 0; i < PPT; ++i) asm volatile("" ::"v"(pre[i]));  // diagnostic: loads kept, no LDS stores
-            }
-            if (p + 2 < nsc && (!(TFL_DIAG & 1) || p < 2)) gload(p + 2);
-        };
-        const bool live = 2 * KC * p + KC * j < N;  // wave-uniform
-        if (TFL_STAGE_FIRST || !live) stage();
-        if (live) process(ring + (p & 1) * SB, p, stage);
+        if (p + 1 < nsc) lstore((p + 1) & 1);
+        if (p + 2 < nsc) gload(p + 2);
+        process(ring + (p & 1) * SB, p);
         lds_barrier();
     }
     TSTAMP(1);
@@ -1529,33 +1483,22 @@ __device__ __forceinline__ void attention_quarters(const unsigned char* __restri
                                                    int npad, unsigned char* A, unsigned char* U,
                                                    Between between) {
     using G = Geo<HD>;
-    constexpr int KS = G::KS, KSA = G::KSA, KT = G::KT, MT = G::MT, QKBLK = G::QKBLK, VCH = G::VCH, XW = G::XW;
+    constexpr int KS = G::KS, KT = G::KT, MT = G::MT, QKBLK = G::QKBLK, VCH = G::VCH, XW = G::XW;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 15, g = lane >> 4;
     const int h = wave / WPH, kq = wave - h * WPH;
     const int nch = npad / KC, nchl = (N + KC - 1) / KC;
     const size_t bh = (size_t)__builtin_amdgcn_readfirstlane(b * HEADS + h);
 
-    u32x4 qh[4][KSA], ql[4][KSA], qxh[4], qxl[4];
+    QFrag<HD> qf[4];  // xh: [q hi | q hi]
 #pragma unroll
-    for (int qq = 0; qq < 4; ++qq) {
-        const unsigned char* qp8 = qb + (bh * (npad / 16) + t0 / 16 + qq) * QKBLK + 16 * lane;
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            qh[qq][ks] = *reinterpret_cast<const u32x4*>(qp8 + 2048 * ks);
-            ql[qq][ks] = *reinterpret_cast<const u32x4*>(qp8 + 2048 * ks + 1024);
-        }
-        if constexpr (KT) {
-            const u32x4 z = u32x4{0u, 0u, 0u, 0u};
-            qxh[qq] = *reinterpret_cast<const u32x4*>(qp8 - 16 * lane + 16 * (lane & 31) + G::TAIL);  // both halves
-            qxl[qq] = lane < 32 ? *reinterpret_cast<const u32x4*>(qp8 + G::TAIL + 512) : z;
-        }
-    }
+    for (int qq = 0; qq < 4; ++qq) qf[qq].template load<true>(qb + (bh * (npad / 16) + t0 / 16 + qq) * QKBLK, lane);
     // chunk c's fragments through descriptors of its two K blocks / V^T chunk
     // (lane l reads 16 B at 16 l of each 1-KB piece: the layout the QKV
-    // epilogues write)
+    // epilogues write); the tail step as xh = [k hi | k lo], xl = [k hi | zeros]
     const int loff = 16 * lane, toff = tail_off(lane);
-    u32x4 kf[2][KSA][2], kx[2][2], vf[MT][2];
+    KFrag<HD> k[2];
+    VFrag<MT> v;
     auto load_k = [&](int c) {
         const auto rk = __builtin_amdgcn_make_buffer_rsrc(
             const_cast<unsigned char*>(kb) + (bh * (npad / 16) + (size_t)c * 2) * QKBLK, 0, 2 * QKBLK, 0x00020000);
@@ -1563,15 +1506,15 @@ __device__ __forceinline__ void attention_quarters(const unsigned char* __restri
         for (int u = 0; u < 2; ++u) {
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
-                kf[u][ks][0] = __builtin_bit_cast(
+                k[u].h[ks] = __builtin_bit_cast(
                     u32x4, __builtin_amdgcn_raw_buffer_load_b128(rk, loff, u * QKBLK + 2048 * ks, 0));
-                kf[u][ks][1] = __builtin_bit_cast(
+                k[u].l[ks] = __builtin_bit_cast(
                     u32x4, __builtin_amdgcn_raw_buffer_load_b128(rk, loff, u * QKBLK + 2048 * ks + 1024, 0));
             }
             if constexpr (KT) {
-                kx[u][0] = __builtin_bit_cast(
+                k[u].xh = __builtin_bit_cast(
                     u32x4, __builtin_amdgcn_raw_buffer_load_b128(rk, loff, u * QKBLK + G::TAIL, 0));
-                kx[u][1] = __builtin_bit_cast(  // hi | zeros
+                k[u].xl = __builtin_bit_cast(
                     u32x4, __builtin_amdgcn_raw_buffer_load_b128(rk, toff, u * QKBLK + G::TAIL, 0));
             }
         }
@@ -1581,8 +1524,8 @@ __device__ __forceinline__ void attention_quarters(const unsigned char* __restri
                                                           VCH, 0x00020000);
 #pragma unroll
         for (int t = 0; t < MT; ++t) {
-            vf[t][0] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rv, loff, t * 2048, 0));
-            vf[t][1] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rv, loff, t * 2048 + 1024, 0));
+            v.h[t] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rv, loff, t * 2048, 0));
+            v.l[t] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rv, loff, t * 2048 + 1024, 0));
         }
     };
     f32x4 acc[4][MT];
@@ -1608,7 +1551,7 @@ __device__ __forceinline__ void attention_quarters(const unsigned char* __restri
             m[qq] = -((float)hi + (float)lo);
             const unsigned w = (unsigned)__builtin_bit_cast(unsigned short, hi) |
                                ((unsigned)__builtin_bit_cast(unsigned short, lo) << 16);
-            if (g2) qxl[qq][0] = w;
+            if (g2) qf[qq].xl[0] = w;
         } else {
             m[qq] = mnew;
         }
@@ -1622,19 +1565,12 @@ __device__ __forceinline__ void attention_quarters(const unsigned char* __restri
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             f32x4 st[2] = {c0(Q0), c0(Q0 + 1)};
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-                for (int qq = 0; qq < 2; ++qq) {
-                    st[qq] = mfma(kf[u][ks][0], qh[Q0 + qq][ks], st[qq]);
-                    st[qq] = mfma(kf[u][ks][0], ql[Q0 + qq][ks], st[qq]);
-                    st[qq] = mfma(kf[u][ks][1], qh[Q0 + qq][ks], st[qq]);
-                }
+            qk_steps<HD, 2>(k[u], qf + Q0, st);
             if constexpr (KT)  // [k hi | k lo] . [q hi | q hi], then [k hi | (1, 1)] . [q lo | -m]
 #pragma unroll
                 for (int qq = 0; qq < 2; ++qq) {
-                    st[qq] = mfma(kx[u][0], qxh[Q0 + qq], st[qq]);
-                    st[qq] = mfma(kx[u][1], qxl[Q0 + qq], st[qq]);
+                    st[qq] = mfma(k[u].xh, qf[Q0 + qq].xh, st[qq]);
+                    st[qq] = mfma(k[u].xl, qf[Q0 + qq].xl, st[qq]);
                 }
 #pragma unroll
             for (int qq = 0; qq < 2; ++qq)
@@ -1648,75 +1584,22 @@ __device__ __forceinline__ void attention_quarters(const unsigned char* __restri
         const int k0 = c * KC;
         if (N - k0 < KC) {  // the chunk straddles N (wave-uniform)
 #pragma unroll
-            for (int u = 0; u < 2; ++u)
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-#pragma unroll
-                    for (int qq = 0; qq < 2; ++qq)
-                        s[qq][u][r] = k0 + 16 * u + 4 * g + r < N ? s[qq][u][r] : -INFINITY;
-        }
-        auto chunk_max = [&](int qq) {
-            return fmaxf(fmaxf(fmaxf(s[qq][0][0], s[qq][0][1]), fmaxf(s[qq][0][2], s[qq][0][3])),
-                         fmaxf(fmaxf(s[qq][1][0], s[qq][1][1]), fmaxf(s[qq][1][2], s[qq][1][3])));
-        };
-        if (first) {  // the wave's first chunk: the base is its maximum (wave-uniform)
-#pragma unroll
-            for (int qq = 0; qq < 2; ++qq) {
-                set_base(Q0 + qq, grp4_max(chunk_max(qq)));  // finite: the chunk holds a key < N
-#pragma unroll
-                for (int u = 0; u < 2; ++u)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) s[qq][u][r] -= m[Q0 + qq];
-            }
+            for (int qq = 0; qq < 2; ++qq) clip_scores(s[qq], k0, g, N);
         }
         u32x4 bh4[2], bl4[2];
         float esum[2];
-        auto exp_split = [&]() {
+        lean_step(
+            s, first, bh4, bl4,
+            [&](bool f1) {
 #pragma unroll
-            for (int qq = 0; qq < 2; ++qq) {
-                float e[2][4];
-#pragma unroll
-                for (int u = 0; u < 2; ++u)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) e[u][r] = __builtin_amdgcn_exp2f(s[qq][u][r]);
-                esum[qq] = ((e[0][0] + e[0][1]) + (e[0][2] + e[0][3])) + ((e[1][0] + e[1][1]) + (e[1][2] + e[1][3]));
-                unsigned ph[4], pl[4];
-                split2u(e[0][0], e[0][1], ph[0], pl[0]);
-                split2u(e[0][2], e[0][3], ph[1], pl[1]);
-                split2u(e[1][0], e[1][1], ph[2], pl[2]);
-                split2u(e[1][2], e[1][3], ph[3], pl[3]);
-                bh4[qq] = u32x4{ph[0], ph[1], ph[2], ph[3]};
-                bl4[qq] = u32x4{pl[0], pl[1], pl[2], pl[3]};
-            }
-        };
-        exp_split();
-        if (__builtin_amdgcn_ballot_w64(p_hi_exceeds(bh4[0], bh4[1])) != 0) {  // rare: move the base
-#pragma unroll
-            for (int qq = 0; qq < 2; ++qq) {
-                const float mold = m[Q0 + qq];
-                set_base(Q0 + qq, mold + vmax(grp4_max(chunk_max(qq)), 0.f));
-                const float d = m[Q0 + qq] - mold;
-                const float corr = __builtin_amdgcn_exp2f(-d);
-                lsum[Q0 + qq] *= corr;
-#pragma unroll
-                for (int t = 0; t < MT; ++t) acc[Q0 + qq][t] *= corr;
-#pragma unroll
-                for (int u = 0; u < 2; ++u)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) s[qq][u][r] -= d;
-            }
-            exp_split();
-        }
+                for (int qq = 0; qq < 2; ++qq)
+                    sub_scores(s[qq], lean_base<true>(f1, max8(s[qq]), m[Q0 + qq], lsum[Q0 + qq], acc[Q0 + qq],
+                                                      [&](float mnew) { set_base(Q0 + qq, mnew); }));
+            },
+            esum);
 #pragma unroll
         for (int qq = 0; qq < 2; ++qq) lsum[Q0 + qq] += esum[qq];
-#pragma unroll
-        for (int t = 0; t < MT; ++t)
-#pragma unroll
-            for (int qq = 0; qq < 2; ++qq) {
-                acc[Q0 + qq][t] = mfma(vf[t][0], bh4[qq], acc[Q0 + qq][t]);
-                acc[Q0 + qq][t] = mfma(vf[t][0], bl4[qq], acc[Q0 + qq][t]);
-                acc[Q0 + qq][t] = mfma(vf[t][1], bh4[qq], acc[Q0 + qq][t]);
-            }
+        pv_block<MT, 2>(v, bh4, bl4, acc + Q0);
     };
 
     const int nj = kq < nchl ? (nchl - kq + WPH - 1) / WPH : 0;  // this wave's chunks
@@ -1727,7 +1610,7 @@ __device__ __forceinline__ void attention_quarters(const unsigned char* __restri
         load_v(c);
         if constexpr (QT)  // lane group 2 of the second tail MFMA: A = (1, 1) (zeros loaded)
 #pragma unroll
-            for (int u = 0; u < 2; ++u) kx[u][1][0] |= g2 ? 0x3C003C00u : 0u;
+            for (int u = 0; u < 2; ++u) k[u].xl[0] |= g2 ? 0x3C003C00u : 0u;
         float s0[2][2][4], s2[2][2][4];
         qk(CI<0>{}, s0);
         smpv(CI<0>{}, c, fresh, s0);

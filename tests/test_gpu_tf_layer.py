@@ -28,7 +28,7 @@ def build_model(stage, dev):
     return m.to(dev).eval()
 
 
-@pytest.fixture(params=["auto", "1", "2", "4", "4q3", "4q12", "f4"])
+@pytest.fixture(params=["auto", "1", "2", "4", "4q0", "4q2", "4q3", "4q4", "4q12", "f4"])
 def rows_per_tile(request, monkeypatch):
     """The tile forms a default can pick: 16- and 32-row workgroup tiles with
     key-quarter attention, 64-row tiles with query-split attention (K / V
@@ -39,6 +39,11 @@ def rows_per_tile(request, monkeypatch):
     two-block form on the unmasked layers too (M2_TFL_QS2=3: what a layer
     whose scores may leave the f16 range runs, m2_layer_w::wide_scores);
     "4q12": M2_TFL_QS2=12 forced (the masked layers still fall back);
+    "4q0", "4q2", "4q4": the remaining forms the switch can select, which no
+    default picks on every layer - the plain one- and two-block forms
+    (M2_TFL_QS2=0, 2: the absolute lazy base) and the lean one-block form on
+    every layer (4; masked it runs the plain one-block softmax) - so every
+    form runs at every edge shape, masked and unmasked, at head_dim 32 and 48;
     "f4": 64-row tiles for the first (LN1 -> QKV) launch (M2_TFL_FIRST_RB,
     the default for very large grids)."""
     if request.param == "f4":
@@ -139,3 +144,48 @@ def test_large_grid_query_split_auto(gpu, stage):
     ref, ref_mask = orc.text_encoder(sd, cfg, ids, lens)
     assert maxabs(enc, ref) <= ENC_TOL
     assert torch.equal(mask.cpu(), ref_mask)
+
+
+@pytest.fixture(scope="module")
+def tiny_hd16():
+    """The tiny model of test_gpu_parity.py::test_tiny_model_api (hidden 32,
+    two heads: head_dim 16, KS = 0 - the Q / K blocks are the tail step alone)
+    with its inputs and the oracle's outputs, computed once."""
+    from models.tts_model import M2TTSModel
+    torch.manual_seed(3)
+    m = M2TTSModel(vocab_size=100, hidden_dim=32, mel_channels=32, text_encoder_layers=1, decoder_layers=1,
+                   num_heads=2, vocoder_channels=64).eval()
+    sd = {k: v.clone() for k, v in m.state_dict().items()}
+    cfg = orc.OracleConfig(vocab_size=100, hidden_dim=32, mel_channels=32, text_encoder_layers=1,
+                           decoder_layers=1, num_heads=2, vocoder_channels=64)
+    g = torch.Generator().manual_seed(33)
+    ids = torch.randint(0, 100, (3, 33), generator=g)
+    lens = torch.tensor([33, 0, 1])
+    x = torch.randn(2, 65, 32, generator=g)
+    ref = {"enc": orc.text_encoder(sd, cfg, ids, lens), "enc_nolen": orc.text_encoder(sd, cfg, ids, None),
+           "mel": orc.mel_decoder(sd, cfg, x)}
+    return m, ids, lens, x, ref
+
+
+@pytest.mark.parametrize("qs2", [None, "0", "2", "3", "4", "12"])
+def test_head_dim_16_on_64_row_tiles(gpu, tiny_hd16, qs2, monkeypatch):
+    """Head_dim 16 (hidden 32) on the 64-row tiles (M2_TFL_RB=4), every form
+    M2_TFL_QS2 selects and the default: the text encoder at B=3, S=33 (lengths
+    33, 0, 1, and no lengths) and the decoder at B=2, T=65 against the oracle.
+    The shapes cross the 16-row block, the 32-key chunk and the 64-key step,
+    and leave one tile wholly past the end."""
+    m, ids, lens, x, ref = tiny_hd16
+    monkeypatch.setenv("M2_TFL_RB", "4")
+    if qs2 is None:
+        monkeypatch.delenv("M2_TFL_QS2", raising=False)
+    else:
+        monkeypatch.setenv("M2_TFL_QS2", qs2)
+    m = m.to(gpu)
+    enc, mask = m.text_encoder(ids.to(gpu), lens.to(gpu))
+    assert maxabs(enc, ref["enc"][0]) <= MEL_MAXABS_TOL, maxabs(enc, ref["enc"][0])
+    assert torch.equal(mask.cpu(), ref["enc"][1])
+    enc, _ = m.text_encoder(ids.to(gpu), None)
+    assert maxabs(enc, ref["enc_nolen"][0]) <= MEL_MAXABS_TOL, maxabs(enc, ref["enc_nolen"][0])
+    mel = m.decoder(x.to(gpu))
+    assert mel.shape == ref["mel"].shape
+    assert maxabs(mel, ref["mel"]) <= MEL_MAXABS_TOL, maxabs(mel, ref["mel"])
