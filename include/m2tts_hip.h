@@ -271,6 +271,43 @@ int32_t m2_inference_back_dev(const m2_model* model, int32_t B, int32_t S, int32
                               size_t workspace_bytes, void* stream);
 int32_t m2_frames_wait(const m2_model* model, void* stream, int32_t* host_T);
 
+/* Ragged batches: every utterance as if synthesized alone.  frames [B] (int32,
+ * device) holds utterance b's own frame count T_b; T (>= every T_b; values are
+ * clamped to [1, T]) is the row stride of the [B,T,*] tensors.  Utterance b's
+ * valid region - mel[b, :T_b] and audio[b, :64 T_b] - is what the B=1 call at
+ * T_b frames computes (same kernels; the last 3 frames of a shorter
+ * utterance's audio are computed again at its own length: by a second call of
+ * the selected vocoder kernels on the batch's [B, 6]-frame end windows, or,
+ * for an utterance of fewer than 6 frames, in fp32 by direct convolution,
+ * within the parity tolerance of the MFMA kernels as the range policy's local
+ * redo is); everything past it is exactly 0.  A batch whose T_b all equal T
+ * gives the bits of the plain entry points.
+ *   m2_mel_decoder_ragged: x [B,T,H] (rows past T_b are not read) -> mel.
+ *   m2_vocoder_ragged: mel [B,M,T] / [B,T,M] (rows past T_b do not reach the
+ *     valid audio, and are left as they are) -> audio [B,1,64T].  Any vocoder
+ *     selection, also streamed (m2_vocoder_set_chunking).
+ *   m2_inference_back_ragged: m2_inference_back at T = max(1, T_max) of
+ *     m2_inference_front with T_b = max(1, total[b]) from the front buffer,
+ *     also written to out_frames [B] (int32, device).
+ * Workspaces: m2_mel_decoder_ragged as m2_mel_decoder; m2_vocoder_ragged
+ * m2_workspace_bytes(B,0,T) + m2_ragged_workspace_bytes(B) and
+ * m2_inference_back_ragged m2_inference_workspace_bytes(B,S,T) +
+ * m2_ragged_workspace_bytes(B) (the end windows' vocoder pass).  M2_E_SHAPE
+ * when the model's decoder does not run the one-launch layers (hidden_dim 32 /
+ * 64 / 96 with 2 heads, M2_TF_LAYER=0) or its vocoder is not a fused one: the
+ * caller then runs the utterances one by one. */
+size_t m2_ragged_workspace_bytes(const m2_model* model, int32_t B);
+int32_t m2_mel_decoder_ragged(const m2_model* model, const float* x, const int32_t* frames, int32_t B,
+                              int32_t T, float* out_mel, void* workspace, size_t workspace_bytes,
+                              void* stream);
+int32_t m2_vocoder_ragged(const m2_model* model, const float* mel, int32_t mel_layout,
+                          const int32_t* frames, int32_t B, int32_t T, float* out_audio,
+                          void* workspace, size_t workspace_bytes, void* stream);
+int32_t m2_inference_back_ragged(const m2_model* model, int32_t B, int32_t S, int32_t T,
+                                 const void* front, size_t front_bytes, float* out_mel,
+                                 float* out_audio, int32_t* out_frames, void* workspace,
+                                 size_t workspace_bytes, void* stream);
+
 /* ---- kernel-level entry points (for the components API and tests) ---------*/
 
 /* LightweightResBlock.forward (components.py:196-200) of vocoder stage k

@@ -78,6 +78,9 @@ struct m2_model {
     // policy 1 on the pipelined tails: the tail's in-launch local redo
     // instead of the guarded exact-f32 launch (vocoder_redo.h); device copy
     const m2::VocRedoW* redo_w = nullptr;
+    // the same table for the ragged entry points' end fix-up (vocoder_ragged.hip):
+    // present on every fused vocoder, also where no tail redo is wired
+    const m2::VocRedoW* ragged_w = nullptr;
     int range_policy = 0;
     // one-launch transformer layers: work-queue counters and the launch
     // sequence whose parity picks their set (one stream per model)

@@ -583,7 +583,7 @@ int32_t m2_model_create(const m2_config* cfg, const void* const* weights, int32_
         ok("hipMalloc(range flags)", hipMemsetAsync(m->rflag_dev, 0, 64, st)) &&
         // the local redo's weight table (range policy "fallback" on the pipelined tails, vocoder_redo.h):
         // the raw fp32 vocoder weights (rw), one device copy
-        (!m->tailp || (ok("hipMalloc(redo weights)", hipMalloc(&redo, sizeof(VocRedoW))) &&
+        (!(m->tailp || m->fused) || (ok("hipMalloc(redo weights)", hipMalloc(&redo, sizeof(VocRedoW))) &&
                        copy("upload redo weights", redo, &rw, sizeof(VocRedoW), hipMemcpyHostToDevice))) &&
         // work-queue counters of the one-launch transformer layers (TflQueue)
         // (+ 16 words: the count kernel's ticket of the device-T front half)
@@ -593,7 +593,8 @@ int32_t m2_model_create(const m2_config* cfg, const void* const* weights, int32_
         ok("hipHostMalloc(frame post)", hipHostMalloc(&m->fpost_host, 64, mapped | hipHostMallocPortable)) &&
         ok("hipHostGetDevicePointer", hipHostGetDevicePointer(reinterpret_cast<void**>(&m->fpost_dev), m->fpost_host, 0)) &&
         ok("hipStreamSynchronize", hipStreamSynchronize(st));
-    m->redo_w = static_cast<const VocRedoW*>(redo);
+    m->ragged_w = static_cast<const VocRedoW*>(redo);
+    m->redo_w = m->tailp ? m->ragged_w : nullptr;
     if (!g) return failed();
     std::memset(m->rflag_host, 0, 64);
     std::memset(m->fpost_host, 0, 64);
@@ -613,7 +614,7 @@ int32_t m2_model_destroy(m2_model* model) {
     if (model->rflag_dev) (void)hipFree(model->rflag_dev);
     if (model->tflq) (void)hipFree(model->tflq);
     if (model->fpost_host) (void)hipHostFree(model->fpost_host);
-    if (model->redo_w) (void)hipFree(const_cast<VocRedoW*>(model->redo_w));
+    if (model->ragged_w) (void)hipFree(const_cast<VocRedoW*>(model->ragged_w));
     hipError_t e = hipFree(model->buf);
     delete model;
     if (e != hipSuccess) return hip_status(e, "hipFree(model)");

@@ -133,6 +133,13 @@ int32_t launch_convT(const float*, const float*, const float*, int, int, int, in
                      float*, hipStream_t);
 int32_t launch_conv_general(const float*, const float*, const float*, const float*, const float*, const float*, int,
                             int, int, int, int, int, int, int, float*, hipStream_t);
+// ragged batches (vocoder_ragged.hip)
+int32_t launch_ragged_count(const int32_t*, int, int32_t*, hipStream_t);
+int32_t launch_ragged_zero(float*, const int32_t*, int, int, int, hipStream_t);
+int32_t launch_ragged_tail(const VocRedoW*, int, int, const float*, bool, const int32_t*, int, int, float*, hipStream_t);
+int ragged_window_frames();
+int32_t launch_ragged_gather(const float*, bool, const int32_t*, int, int, int, float*, hipStream_t);
+int32_t launch_ragged_scatter(const float*, const int32_t*, int, int, float*, hipStream_t);
 
 static thread_local std::string g_last_error;
 
@@ -338,7 +345,8 @@ bool tfl_use(const m2_model* m, const std::vector<m2_layer_w>& layers) {
 int32_t run_tfl(const m2_model* m, const std::vector<m2_layer_w>& layers, const float* x0, float* x, TfBufs& wb,
                 const int64_t* lengths, int B, int N, hipStream_t st, const float* fin_g = nullptr,
                 const float* fin_b = nullptr, const float* fin_W = nullptr, const float* fin_bias = nullptr,
-                int fin_N = 0, float* fin_out = nullptr, bool* fin_done = nullptr, const int32_t* dN = nullptr) {
+                int fin_N = 0, float* fin_out = nullptr, bool* fin_done = nullptr, const int32_t* dN = nullptr,
+                const int32_t* rows = nullptr) {
     const int H = m->cfg.hidden_dim, heads = m->cfg.num_heads, n = (int)layers.size();
     if (fin_done) *fin_done = false;
     const float* cur = x0;
@@ -363,7 +371,7 @@ int32_t run_tfl(const m2_model* m, const std::vector<m2_layer_w>& layers, const 
             z = fin_out;
         }
         const int32_t rc = launch_tfl_layer(w, B, N, H, heads, lengths != nullptr, lengths, cur, x, wb.tfl[l & 1], next,
-                                            wb.tfl[(l + 1) & 1], NN, z, tfl_queue(m), st, dN);
+                                            wb.tfl[(l + 1) & 1], NN, z, tfl_queue(m), st, dN, rows);
         if (rc) return tfl_reset(m, st, rc);
         if (next == 2 && fin_done) *fin_done = true;
         cur = x;
@@ -623,9 +631,11 @@ namespace {
 // The mel decoder on x [B, T, H]; with enc / cum given, x is first filled by
 // the length regulator's frame expansion of enc, fused into the first layer's
 // LN1 -> QKV launch when tf_first_fused (else a separate lr_expand launch).
+// rows (one-launch layers only): utterance b has rows[b] frames, T is the
+// row stride; out_mel's rows past rows[b] are then not written.
 int32_t mel_decoder(const m2_model* m, float* x, int32_t B, int32_t T, float* out_mel, void* workspace,
                     size_t workspace_bytes, hipStream_t st, const float* enc = nullptr, const int32_t* cum = nullptr,
-                    int32_t S = 0, const int32_t* dT = nullptr) {
+                    int32_t S = 0, const int32_t* dT = nullptr, const int32_t* rows = nullptr) {
     const int H = m->cfg.hidden_dim;
     Carve a(workspace, workspace_bytes);
     TfBufs wb;
@@ -637,6 +647,8 @@ int32_t mel_decoder(const m2_model* m, float* x, int32_t B, int32_t T, float* ou
     // layers with the mel projection fused into the last one)
     M2_CHECK_ARG(!dT || (tfl_use(m, m->dec) && tfl_proj_supported(H, m->cfg.mel_channels)),
                  "mel decoder: a device frame count needs the one-launch layers");
+    M2_CHECK_SHAPE(!rows || tfl_use(m, m->dec), "mel decoder: per-utterance frame counts need the one-launch layers "
+                                                "(hidden_dim 32 / 64 / 96 with 2 heads, M2_TF_LAYER not 0)");
     if (tfl_use(m, m->dec)) {
         const m2_layer_w& L0 = m->dec[0];
         TflFirst f;
@@ -656,11 +668,11 @@ int32_t mel_decoder(const m2_model* m, float* x, int32_t B, int32_t T, float* ou
             f.x_in = x;
         }
         if ((rc = launch_tfl_first(f, B, T, H, m->cfg.num_heads, false, x, L0.n1_w, L0.n1_b, L0.qkv_p, wb.tfl[0],
-                                   tfl_queue(m), st)))
+                                   tfl_queue(m), st, rows)))
             return tfl_reset(m, st, rc);
         bool projected = false;
         if ((rc = run_tfl(m, m->dec, x, wb.x, wb, nullptr, B, T, st, m->dec_nw, m->dec_nb, m->mel_p, m->mel_b,
-                          m->cfg.mel_channels, out_mel, &projected, dT)))
+                          m->cfg.mel_channels, out_mel, &projected, dT, rows)))
             return rc;
         if (projected) return M2_OK;
         return launch_ln_gemm(wb.x, m->dec_nw, m->dec_nb, m->mel_p, m->mel_b, ACT_NONE, B * T, H, m->cfg.mel_channels,
@@ -1096,6 +1108,65 @@ int32_t front_run(const m2_model* m, const int64_t* ids, const int64_t* lengths,
     return count(*f);
 }
 
+// Ragged batches need the kernels that take a per-utterance bound: the
+// one-launch layers (decoder) and the fused vocoder with its fp32 weight table
+// for the end fix-up (vocoder).  Otherwise M2_E_SHAPE: the caller runs the
+// utterances one by one.
+int32_t ragged_supported(const m2_model* m, bool decoder, bool vocoder, const char* what) {
+    if (decoder && !tfl_use(m, m->dec))
+        return fail(M2_E_SHAPE, (std::string(what) + ": per-utterance frame counts need the one-launch transformer "
+                                 "layers (hidden_dim 32 / 64 / 96 with 2 heads, split-f16 range, M2_TF_LAYER not 0)")
+                                    .c_str());
+    if (vocoder && !(m->fused && m->ragged_w))
+        return fail(M2_E_SHAPE, (std::string(what) + ": per-utterance frame counts need the fused vocoder "
+                                 "(unsupported (mel_channels, vocoder_channels) or M2_VOCODER_PERLAYER)").c_str());
+    return M2_OK;
+}
+
+// Scratch of the end-window pass for B utterances (the mel windows, their
+// audio, the vocoder intermediates of a window-long call): what the ragged
+// vocoder needs beside the plain call's workspace (m2_ragged_workspace_bytes).
+size_t ragged_extra_bytes(const m2_model* m, int B) {
+    const int W = ragged_window_frames();
+    Sizer s;
+    carve_chunked(s, m->cfg, B, W, W, nullptr);
+    return s.off + 256;
+}
+
+// The batched vocoder at T frames, then each utterance's end redone at its own
+// length frames[b] and everything past it cleared (vocoder_ragged.hip): one
+// more call of the selected vocoder kernels on the utterances' end windows,
+// the fp32 kernel for utterances shorter than a window.  The main pass may be
+// split-f16, exact-f32 or streamed: the fix-up only replaces its audio.
+// win: ragged_extra_bytes(m, B) of scratch for the window pass.
+int32_t vocoder_ragged(const m2_model* m, const float* mel, int32_t mel_layout, const int32_t* frames, int32_t B,
+                       int32_t T, float* out_audio, void* workspace, size_t workspace_bytes, void* win, size_t win_bytes,
+                       void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int32_t rc = vocoder_entry(m, mel, mel_layout, B, T, out_audio, workspace, workspace_bytes, stream);
+    if (rc || B == 0 || T == 0) return rc;
+    const int W = ragged_window_frames(), M = m->cfg.mel_channels;
+    if (T > W) {  // else no utterance is both shorter than T and a window long
+        ChunkBufs c;
+        Carve a(win, win_bytes);
+        carve_chunked(a, m->cfg, B, W, W, &c);
+        if (!a.ok) return fail(M2_E_WORKSPACE, "ragged vocoder: workspace too small (m2_ragged_workspace_bytes)");
+        if ((rc = launch_ragged_gather(mel, mel_layout == 1, frames, B, T, M, c.mel, st))) return rc;
+        const bool x3 = m->x3;
+        const int redo = device_redo_word(m, x3);
+        if ((rc = vocoder_run(m, c.mel, mel_layout, B, W, c.audio, c.voc, st, x3, redo))) return rc;
+        if (redo < 0 && (rc = range_fallback(m, st, x3, [&] {
+                             return vocoder_run(m, c.mel, mel_layout, B, W, c.audio, c.voc, st, false);
+                         })))
+            return rc;
+        if ((rc = launch_ragged_scatter(c.audio, frames, B, T, out_audio, st))) return rc;
+    }
+    if ((rc = launch_ragged_tail(m->ragged_w, M, m->cfg.vocoder_channels, mel, mel_layout == 1, frames, B, T, out_audio,
+                                 st)))
+        return rc;
+    return launch_ragged_zero(out_audio, frames, B, T, 64, st);
+}
+
 // The back half can run from a device-resident frame count with its grids
 // sized for T_cap frames: the one-launch decoder layers with the mel
 // projection fused into the last one, and the fused (unchunked) vocoder.
@@ -1107,9 +1178,10 @@ bool dev_back_ok(const m2_model* m, int32_t T_cap) {
 
 // expansion to T frames + decoder + vocoder; dT: T is the capacity and the
 // kernels take the frame count from the device word (dev_frames)
+// rows: a ragged batch - utterance b has rows[b] frames of the T (ragged_supported)
 int32_t back_run(const m2_model* m, int32_t B, int32_t S, int32_t T, const int32_t* dT, const void* front,
                  size_t front_bytes, float* out_mel, float* out_audio, void* workspace, size_t workspace_bytes,
-                 void* stream) {
+                 void* stream, const int32_t* rows = nullptr) {
     M2_CHECK_ARG(m && B >= 0 && S >= 0 && T >= 0, "m2_inference_back: bad argument");
     if (B == 0 || T == 0) return M2_OK;
     M2_CHECK_ARG(out_mel && out_audio, "m2_inference_back: null output");
@@ -1125,12 +1197,19 @@ int32_t back_run(const m2_model* m, int32_t B, int32_t S, int32_t T, const int32
     const size_t scratch = std::max(sz_tf.off, vocoder_ws_bytes(m, B, T));
     (void)w.take<char>(scratch);
     float* reg = w.take<float>((size_t)B * T * H);
+    const size_t win_bytes = rows ? ragged_extra_bytes(m, B) : 0;  // the ragged vocoder's window pass
+    char* win = rows ? w.take<char>(win_bytes) : nullptr;
     if (!w.ok) return fail(M2_E_WORKSPACE, "m2_inference_back: workspace too small");
     int32_t rc;
     // frame expansion + decoder (the expansion fused into the first layer's launch)
     if ((rc = mel_decoder(m, reg, B, T, out_mel, workspace, scratch, static_cast<hipStream_t>(stream), f.enc, f.cum,
-                          S, dT)))
+                          S, dT, rows)))
         return rc;
+    if (rows) {  // the mel past each utterance's end is zero before the vocoder reads it
+        if ((rc = launch_ragged_zero(out_mel, rows, B, T, m->cfg.mel_channels, static_cast<hipStream_t>(stream))))
+            return rc;
+        return vocoder_ragged(m, out_mel, 1, rows, B, T, out_audio, workspace, scratch, win, win_bytes, stream);
+    }
     return vocoder_entry(m, out_mel, 1, B, T, out_audio, workspace, scratch, stream, dT);
 }
 }  // namespace
@@ -1181,6 +1260,54 @@ int32_t m2_inference_back_dev(const m2_model* m, int32_t B, int32_t S, int32_t T
     M2_CHECK_ARG(dev_back_ok(m, T_cap), "m2_inference_back_dev: this model's back half needs the host-side frame "
                                         "count (m2_inference_dev_supported is 0)");
     return back_run(m, B, S, T_cap, dev_T, front, front_bytes, out_mel, out_audio, workspace, workspace_bytes, stream);
+}
+
+int32_t m2_mel_decoder_ragged(const m2_model* m, const float* x, const int32_t* frames, int32_t B, int32_t T,
+                              float* out_mel, void* workspace, size_t workspace_bytes, void* stream) {
+    M2_CHECK_ARG(m && x && frames && out_mel && B >= 0 && T >= 0, "m2_mel_decoder_ragged: bad argument");
+    if (int32_t rc = ragged_supported(m, true, false, "m2_mel_decoder_ragged")) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int32_t rc = mel_decoder(m, const_cast<float*>(x), B, T, out_mel, workspace, workspace_bytes, st, nullptr, nullptr,
+                             0, nullptr, frames);
+    if (rc) return rc;
+    return launch_ragged_zero(out_mel, frames, B, T, m->cfg.mel_channels, st);
+}
+
+int32_t m2_vocoder_ragged(const m2_model* m, const float* mel, int32_t mel_layout, const int32_t* frames, int32_t B,
+                          int32_t T, float* out_audio, void* workspace, size_t workspace_bytes, void* stream) {
+    M2_CHECK_ARG(m && mel && frames && out_audio && B >= 0 && T >= 0, "m2_vocoder_ragged: bad argument");
+    M2_CHECK_ARG(mel_layout == 0 || mel_layout == 1, "m2_vocoder_ragged: mel_layout must be 0 or 1");
+    if (int32_t rc = ragged_supported(m, false, true, "m2_vocoder_ragged")) return rc;
+    if (B == 0 || T == 0) return M2_OK;
+    // the window pass's scratch is the end of the workspace
+    const size_t extra = ragged_extra_bytes(m, B);
+    if (!workspace || workspace_bytes < extra) return fail(M2_E_WORKSPACE, "m2_vocoder_ragged: workspace too small");
+    const size_t main_bytes = (workspace_bytes - extra) / 256 * 256;
+    return vocoder_ragged(m, mel, mel_layout, frames, B, T, out_audio, workspace, main_bytes,
+                          static_cast<char*>(workspace) + main_bytes, workspace_bytes - main_bytes, stream);
+}
+
+size_t m2_ragged_workspace_bytes(const m2_model* m, int32_t B) {
+    if (!m || B < 0) return 0;
+    return ragged_extra_bytes(m, B);
+}
+
+int32_t m2_inference_back_ragged(const m2_model* m, int32_t B, int32_t S, int32_t T, const void* front,
+                                 size_t front_bytes, float* out_mel, float* out_audio, int32_t* out_frames,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
+    M2_CHECK_ARG(m && B >= 0 && S >= 0 && T >= 0, "m2_inference_back_ragged: bad argument");
+    if (int32_t rc = ragged_supported(m, true, true, "m2_inference_back_ragged")) return rc;
+    if (B == 0 || T == 0) return M2_OK;
+    M2_CHECK_ARG(out_mel && out_audio && out_frames, "m2_inference_back_ragged: null output");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    Carve a(const_cast<void*>(front), front_bytes);
+    FrontBufs f;
+    carve_front(a, B, S, m->cfg.hidden_dim, &f);
+    if (!a.ok) return fail(M2_E_WORKSPACE, "m2_inference_back_ragged: front buffer too small");
+    int32_t rc;
+    if ((rc = launch_ragged_count(f.tot, B, out_frames, st))) return rc;
+    return back_run(m, B, S, T, nullptr, front, front_bytes, out_mel, out_audio, workspace, workspace_bytes, stream,
+                    out_frames);
 }
 
 int32_t m2_frames_wait(const m2_model* m, void* stream, int32_t* host_T) {

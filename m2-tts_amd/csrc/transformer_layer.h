@@ -62,12 +62,17 @@ struct TflFirst {
 };
 int32_t launch_tfl_first(const TflFirst& f, int B, int N, int H, int heads, bool masked, float* x_out,
                          const float* g, const float* bln, const float* Wqkv, const TflBufs& out, TflQueue q,
-                         hipStream_t st);
+                         hipStream_t st, const int32_t* rows = nullptr);
 
 // One pre-LN layer x_out = layer(x_in) (x_out may alias x_in), attention from
 // `in`; then, on the same row tile: next == 1: the next layer's LN1 -> QKV
 // into `out`; next == 2: LN(y; gn, bn) . Wn^T + bn2 into z [B*N][NN].
 // masked: key padding mask from lengths (-1e9 fill, components.py:79-81).
+// rows (both launches; null: N for every utterance): utterance b has
+// clamp(rows[b], 1, N) rows and keys - a ragged batch.  N stays the row stride
+// of x, z and the masks and sizes npad and the grid; rows past the bound are
+// zeros in the attention buffers and are not written to x_out / z.  Not
+// combinable with dN.
 struct TflLayer {
     const float *Wo, *bo, *g2, *b2n, *W1, *b1, *W2, *b2;  // packed (pack_bfrag_split) / fp32
     const float *gn = nullptr, *bn = nullptr, *Wn = nullptr, *bn2 = nullptr;
@@ -77,6 +82,7 @@ struct TflLayer {
 };
 int32_t launch_tfl_layer(const TflLayer& w, int B, int N, int H, int heads, bool masked, const int64_t* lengths,
                          const float* x_in, float* x_out, const TflBufs& in, int next, const TflBufs& out,
-                         int NN, float* z, TflQueue q, hipStream_t st, const int32_t* dN = nullptr);
+                         int NN, float* z, TflQueue q, hipStream_t st, const int32_t* dN = nullptr,
+                         const int32_t* rows = nullptr);
 
 }  // namespace m2

@@ -420,6 +420,14 @@ __device__ __forceinline__ void claim_tile(int B, int ntile, unsigned* __restric
     *tile = __builtin_amdgcn_readfirstlane(it - (it / ntile) * ntile);
 }
 
+// The rows (and keys) of utterance b in a batch whose rows sit at stride N:
+// rows[b] clamped to [1, N] (a ragged batch, LArgs / FArgs::rows), else N.
+// b is wave-uniform (claim_tile), so the bound is a scalar load into an SGPR.
+__device__ __forceinline__ int row_bound(const int32_t* __restrict__ rows, int b, int N) {
+    if (!rows) return N;
+    return __builtin_amdgcn_readfirstlane(min(max(rows[b], 1), N));
+}
+
 // ---------------------------------------------------------------------------
 // The attention kit: what attention_tile, attention_qsplit2 and
 // attention_quarters below share, each piece written once.  A block is 16
@@ -1668,6 +1676,7 @@ __device__ __forceinline__ void attention_quarters(const unsigned char* __restri
 struct LArgs {
     int B, N, npad, ntile;
     const int32_t* dN;  // device frame count (dev_frames; N is then the capacity)
+    const int32_t* rows;  // per-utterance row / key bound [B] (null: N); N stays the row stride
     unsigned* qcnt;
     unsigned qseq;
     float sl2;  // scale * log2(e)
@@ -1728,9 +1737,10 @@ __global__ __launch_bounds__(512, 2) void layer_kernel(LArgs a) {
     int b, tile;
     claim_tile(a.B, a.ntile, a.qcnt, a.qseq, &item, &b, &tile);
     const int t0 = tile * TR, N = a.dN ? dev_frames(a.dN, a.N) : a.N;
+    const int Nb = row_bound(a.rows, b, N);  // rows and keys of this utterance; N: the row stride
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, i = lane & 15, gq = lane >> 4;
     const QkvOut qo{a.nq, a.nk, a.nv, a.npad, a.npad / KC, MASKED ? 1.f : a.sl2};
-    if (t0 >= N) {
+    if (t0 >= Nb) {
         if constexpr (NEXT == 1) zero_tile<H, HD, RB>(qo, b, t0);
         return;
     }
@@ -1749,43 +1759,43 @@ __global__ __launch_bounds__(512, 2) void layer_kernel(LArgs a) {
         for (int e = threadIdx.x; e < NN; e += NW * 64) vec[VBN2 + e] = a.bn2[e];
     TSTAMP_RT(14);
     TSTAMP(0);
-    int len = N;
-    if constexpr (MASKED) len = (int)max((int64_t)0, min(a.lengths[b], (int64_t)N));  // mask[b, s] = s < lengths[b]
+    int len = Nb;
+    if constexpr (MASKED) len = (int)max((int64_t)0, min(a.lengths[b], (int64_t)Nb));  // mask[b, s] = s < lengths[b]
     Strip<H> so;
     Strip<H> s1, s1b;  // FFN1 strips (ONE: both of this wave's, requested before the merge)
     f32x4 xres = f32x4{0.f, 0.f, 0.f, 0.f};
     [[maybe_unused]] f32x4 xres4[RB];  // form 12: the residual rows, requested before the merge
     if constexpr (ONE) {  // the out projection's residual rows (here: measured 0.4 us better than beside Wo)
-        if (wave < H / 16 && t0 + i < N)
+        if (wave < H / 16 && t0 + i < Nb)
             xres = *reinterpret_cast<const f32x4*>(a.x_in + ((size_t)b * N + t0 + i) * H + wave * 16 + 4 * gq);
     }
     if constexpr (QS) {
         if constexpr (QV == 12)
-            attention_quarters<H, HD>(a.q, a.k, a.v, b, t0, N, a.npad, A, U, [&] {
+            attention_quarters<H, HD>(a.q, a.k, a.v, b, t0, Nb, a.npad, A, U, [&] {
                 if (wave < F / 16) s1.load(a.W1, wave);  // both FFN1 strips of this wave
                 if (wave + NW < F / 16) s1b.load(a.W1, wave + NW);
                 if (wave < H / 16) {  // the out projection's strip and residual rows
                     so.load(a.Wo, wave);
 #pragma unroll
                     for (int rb = 0; rb < RB; ++rb)
-                        xres4[rb] = t0 + rb * 16 + i < N ? *reinterpret_cast<const f32x4*>(
+                        xres4[rb] = t0 + rb * 16 + i < Nb ? *reinterpret_cast<const f32x4*>(
                                                                a.x_in + ((size_t)b * N + t0 + rb * 16 + i) * H +
                                                                wave * 16 + 4 * gq)
                                                          : f32x4{0.f, 0.f, 0.f, 0.f};
                 }
             });
-        else if constexpr (QV == 3) attention_qsplit2<H, HD, MASKED, true>(a.q, a.k, a.v, b, t0, N, a.npad, len, a.sl2, A, U);
-        else if constexpr (QV == 2) attention_qsplit2<H, HD, MASKED>(a.q, a.k, a.v, b, t0, N, a.npad, len, a.sl2, A, U);
+        else if constexpr (QV == 3) attention_qsplit2<H, HD, MASKED, true>(a.q, a.k, a.v, b, t0, Nb, a.npad, len, a.sl2, A, U);
+        else if constexpr (QV == 2) attention_qsplit2<H, HD, MASKED>(a.q, a.k, a.v, b, t0, Nb, a.npad, len, a.sl2, A, U);
         // (lean one-block form for the unmasked decoder only: masked, its MFMA
         // row sums moved the stage1 encoder's error at B=128 S=130 from under
         // to just over the tile tests' 2e-5 bound, for no measured gain)
-        else if constexpr (QV == 4) attention_qsplit<H, HD, MASKED, !MASKED>(a.q, a.k, a.v, b, t0, N, a.npad, len, a.sl2, A, U);
-        else attention_qsplit<H, HD, MASKED>(a.q, a.k, a.v, b, t0, N, a.npad, len, a.sl2, A, U);
+        else if constexpr (QV == 4) attention_qsplit<H, HD, MASKED, !MASKED>(a.q, a.k, a.v, b, t0, Nb, a.npad, len, a.sl2, A, U);
+        else attention_qsplit<H, HD, MASKED>(a.q, a.k, a.v, b, t0, Nb, a.npad, len, a.sl2, A, U);
         if (QV != 12 && wave < H / 16) so.load(a.Wo, wave);
         __syncthreads();
         TSTAMP(2);
     } else {
-        attention_tile<H, HD, MASKED, RB>(a.q, a.k, a.v, b, t0, N, a.npad, len, a.sl2, A, xs, [&] {
+        attention_tile<H, HD, MASKED, RB>(a.q, a.k, a.v, b, t0, Nb, a.npad, len, a.sl2, A, xs, [&] {
             if (wave < H / 16) so.load(a.Wo, wave);
             if constexpr (ONE) {
                 if (wave < F / 16) s1.load(a.W1, wave);
@@ -1807,7 +1817,7 @@ __global__ __launch_bounds__(512, 2) void layer_kernel(LArgs a) {
             f32x4 x = f32x4{0.f, 0.f, 0.f, 0.f};
             if constexpr (ONE) x = xres;
             else if constexpr (QV == 12) x = xres4[rb];
-            else if (t0 + rr < N) x = *reinterpret_cast<const f32x4*>(a.x_in + (row0 + rr) * H + col);
+            else if (t0 + rr < Nb) x = *reinterpret_cast<const f32x4*>(a.x_in + (row0 + rr) * H + col);
             *reinterpret_cast<f32x4*>(O + rr * frs(H) + col) = x + acc[rb];
         }
     }
@@ -1870,7 +1880,7 @@ __global__ __launch_bounds__(512, 2) void layer_kernel(LArgs a) {
         for (int rb = 0; rb < RB; ++rb) {
             const int rr = rb * 16 + i;
             const f32x4 y = *reinterpret_cast<const f32x4*>(O + rr * frs(H) + col) + acc[rb];
-            if (t0 + rr < N) *reinterpret_cast<f32x4*>(a.x_out + (row0 + rr) * H + col) = y;
+            if (t0 + rr < Nb) *reinterpret_cast<f32x4*>(a.x_out + (row0 + rr) * H + col) = y;
             if constexpr (NEXT != 0) *reinterpret_cast<f32x4*>(O + rr * frs(H) + col) = y;
         }
     }
@@ -1883,9 +1893,9 @@ __global__ __launch_bounds__(512, 2) void layer_kernel(LArgs a) {
         __syncthreads();
         TSTAMP(7);
         if constexpr (PRE) {
-            qkv_phase_pre<H, HD, RB>(A, sq, qo, b, t0, N);
+            qkv_phase_pre<H, HD, RB>(A, sq, qo, b, t0, Nb);
         } else {
-            qkv_phase<H, HD, RB>(A, a.Wn, sn, qo, b, t0, N);
+            qkv_phase<H, HD, RB>(A, a.Wn, sn, qo, b, t0, Nb);
         }
         TSTAMP(8);
         TSTAMP_RT(15);
@@ -1910,7 +1920,7 @@ __global__ __launch_bounds__(512, 2) void layer_kernel(LArgs a) {
 #pragma unroll
             for (int rb = 0; rb < RB; ++rb) {
                 const int rr = rb * 16 + i;
-                if (t0 + rr < N) *reinterpret_cast<f32x4*>(a.z + (row0 + rr) * NN + col) = acc[rb];
+                if (t0 + rr < Nb) *reinterpret_cast<f32x4*>(a.z + (row0 + rr) * NN + col) = acc[rb];
             }
             if (nb + NW < NN / 16) sn = nxt;
         }
@@ -1929,6 +1939,7 @@ enum { SRC_X = 0, SRC_EMBED = 1, SRC_EXPAND = 2 };
 struct FArgs {
     int B, N, npad, ntile;
     const int32_t* dN;  // device frame count (dev_frames; N is then the capacity)
+    const int32_t* rows;  // per-utterance row / key bound [B] (null: N); N stays the row stride
     unsigned* qcnt;
     unsigned qseq;
     float sl2;
@@ -1978,9 +1989,10 @@ __global__ __launch_bounds__(fk_nw(RB) * 64, FK_MINW) void first_kernel(FArgs a)
     int b, tile;
     claim_tile(a.B, a.ntile, a.qcnt, a.qseq, &item, &b, &tile);
     const int t0 = tile * TR, N = a.dN ? dev_frames(a.dN, a.N) : a.N;
+    const int Nb = row_bound(a.rows, b, N);  // rows of this utterance; N: the row stride
     const int wave = threadIdx.x >> 6;
     const QkvOut qo{a.q, a.k, a.v, a.npad, a.npad / KC, MASKED ? 1.f : a.sl2};
-    if (t0 >= N) {
+    if (t0 >= Nb) {
         zero_tile<H, HD, RB, FNW>(qo, b, t0);
         return;
     }
@@ -2009,7 +2021,7 @@ __global__ __launch_bounds__(fk_nw(RB) * 64, FK_MINW) void first_kernel(FArgs a)
             const int32_t* c = in_lds ? cs : cg;
             const int t = t0 + threadIdx.x;
             int v = -1;
-            if (t < N && t < c[a.S]) {
+            if (t < Nb && t < c[a.S]) {
                 int lo = 0, hi = a.S - 1;
                 while (lo < hi) {
                     const int mid = (lo + hi) >> 1;
@@ -2026,7 +2038,7 @@ __global__ __launch_bounds__(fk_nw(RB) * 64, FK_MINW) void first_kernel(FArgs a)
         const int r = idx / H4, c = (idx - r * H4) * 4, t = t0 + r;
         const size_t row = (size_t)b * N + t;
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (t < N) {
+        if (t < Nb) {
             if constexpr (SRC == SRC_X) {
                 v = *reinterpret_cast<const float4*>(a.x_in + row * H + c);
             } else if constexpr (SRC == SRC_EMBED) {
@@ -2049,8 +2061,8 @@ __global__ __launch_bounds__(fk_nw(RB) * 64, FK_MINW) void first_kernel(FArgs a)
     __syncthreads();
     ln_rows<H, TR, FNW * 64>(O, A, vec, vec + H);
     __syncthreads();
-    if constexpr (ONE) qkv_phase_pre<H, HD>(A, sqa, qo, b, t0, N);
-    else qkv_phase<H, HD, RB, FNW>(A, a.W, sq, qo, b, t0, N);
+    if constexpr (ONE) qkv_phase_pre<H, HD>(A, sqa, qo, b, t0, Nb);
+    else qkv_phase<H, HD, RB, FNW>(A, a.W, sq, qo, b, t0, Nb);
 }
 
 }  // namespace tfl
@@ -2143,7 +2155,7 @@ float tfl_sl2(int H) {
 
 int32_t launch_tfl_first(const TflFirst& f, int B, int N, int H, int heads, bool masked, float* x_out,
                          const float* g, const float* bln, const float* Wqkv, const TflBufs& out, TflQueue q,
-                         hipStream_t st) {
+                         hipStream_t st, const int32_t* rows) {
     M2_CHECK_SHAPE(tfl_supported(H, heads), "tfl: unsupported (hidden_dim, heads)");
     M2_CHECK_ARG(q.cnt, "tfl: no work-queue counters");
     // every launch must run: its workgroups zero the NEXT launch's work-queue
@@ -2179,7 +2191,9 @@ int32_t launch_tfl_first(const TflFirst& f, int B, int N, int H, int heads, bool
     a.enc = f.enc;
     a.cum = f.cum;
     a.S = f.S;
+    M2_CHECK_ARG(!(f.dN && rows), "tfl: a device frame count and per-utterance rows do not combine");
     a.dN = f.dN;
+    a.rows = rows;
     a.post = f.dN ? f.post : nullptr;
     a.post_seq = f.post_seq;
     a.x_out = x_out;
@@ -2214,7 +2228,7 @@ int32_t launch_tfl_first(const TflFirst& f, int B, int N, int H, int heads, bool
 
 int32_t launch_tfl_layer(const TflLayer& w, int B, int N, int H, int heads, bool masked, const int64_t* lengths,
                          const float* x_in, float* x_out, const TflBufs& in, int next, const TflBufs& out, int NN,
-                         float* z, TflQueue q, hipStream_t st, const int32_t* dN) {
+                         float* z, TflQueue q, hipStream_t st, const int32_t* dN, const int32_t* rows) {
     M2_CHECK_SHAPE(tfl_supported(H, heads), "tfl: unsupported (hidden_dim, heads)");
     M2_CHECK_ARG(!masked || lengths, "tfl: masked attention needs lengths");
     M2_CHECK_ARG(q.cnt, "tfl: no work-queue counters");
@@ -2226,7 +2240,9 @@ int32_t launch_tfl_layer(const TflLayer& w, int B, int N, int H, int heads, bool
     tfl::LArgs a{};
     a.B = B;
     a.N = N;
+    M2_CHECK_ARG(!(dN && rows), "tfl: a device frame count and per-utterance rows do not combine");
     a.dN = dN;
+    a.rows = rows;
     a.npad = tfl_npad(N);
     const int rb = masked && sw().tfl_rb_masked     ? sw().tfl_rb_masked
                    : !masked && sw().tfl_rb_unmasked ? sw().tfl_rb_unmasked

@@ -11,6 +11,12 @@ torch.load runs with ``weights_only=True``; a checkpoint whose config is a
 pickled DictConfig is refused by that loader, and is only unpickled with the
 explicit ``--trust-checkpoint`` opt-in (trusted local files only), or its
 config can be given with ``--config configs/stage1_poc.yaml`` instead.
+
+Beyond the reference: ``--text-file FILE --output-dir DIR`` synthesizes one
+text per line (blank lines skipped) in batches of ``--batch-size`` through
+``M2TTSModel.inference_ragged`` - every text as if synthesized alone - and
+writes ``DIR/00000.wav``, ``DIR/00001.wav``, ... each trimmed to its own
+length.
 """
 from __future__ import annotations
 
@@ -18,7 +24,7 @@ import argparse
 import logging
 import sys
 from pathlib import Path
-from typing import Any, Optional
+from typing import Any, List, Optional
 
 import torch
 
@@ -121,9 +127,39 @@ def synthesize_text(text: str, model: M2TTSModel, text_processor: TextProcessor,
     return mel, audio
 
 
+def read_texts(path: Path) -> List[str]:
+    """One text per line; blank lines are skipped."""
+    with open(path, encoding="utf-8") as f:
+        return [line.strip() for line in f if line.strip()]
+
+
+def synthesize_texts(texts: List[str], model: M2TTSModel, text_processor: TextProcessor, device: torch.device,
+                     duration_scale: float = 1.0, batch_size: int = 32) -> List[torch.Tensor]:
+    """The audio of each text ([64 T_b] tensors, in order): one
+    inference_ragged call per batch_size texts, each text processed as
+    synthesize_text does and trimmed to its own frame count."""
+    from models.tts_model import unpad
+    out = []
+    for i in range(0, len(texts), batch_size):
+        tds = [text_processor.process_text(t, max_length=256) for t in texts[i:i + batch_size]]
+        ids = torch.LongTensor([td["phoneme_ids"] for td in tds]).to(device)
+        lens = torch.LongTensor([td["length"] for td in tds]).to(device)
+        with torch.no_grad():
+            mel, audio, frames = model.inference_ragged(ids, lens, duration_scale=duration_scale)
+        logger.info(f"Batch of {len(tds)}: frames {frames.tolist()}")
+        out.extend(a for _, a in unpad(mel, audio, frames))
+    return out
+
+
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="M2 TTS Text Synthesis (MI355X)")
-    p.add_argument("--text", type=str, required=True, help="Text to synthesize")
+    src = p.add_mutually_exclusive_group(required=True)
+    src.add_argument("--text", type=str, help="Text to synthesize")
+    src.add_argument("--text-file", type=str, default=None,
+                     help="File with one text per line (blank lines skipped); needs --output-dir")
+    p.add_argument("--output-dir", type=str, default=None,
+                   help="Directory for 00000.wav, 00001.wav, ... of --text-file")
+    p.add_argument("--batch-size", type=int, default=32, help="Texts per inference call of --text-file")
     p.add_argument("--checkpoint", type=str, required=True, help="Path to model checkpoint")
     p.add_argument("--output", type=str, default="output.wav", help="Output audio file path")
     p.add_argument("--duration-scale", type=float, default=1.0, help="Duration scaling factor (1.0 = normal speed)")
@@ -135,12 +171,28 @@ def build_parser() -> argparse.ArgumentParser:
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.text_file is not None and args.output_dir is None:
+        parser.error("--text-file needs --output-dir")
+    if args.text_file is None and args.output_dir is not None:
+        parser.error("--output-dir goes with --text-file")
+    if args.batch_size < 1:
+        parser.error("--batch-size must be positive")
     device = setup_device()
     logger.info(f"Using device: {device}")
     model = load_model(Path(args.checkpoint), device, Path(args.config) if args.config else None,
                        args.trust_checkpoint)
     processor = TextProcessor()
+    if args.text_file is not None:
+        out_dir = Path(args.output_dir)
+        out_dir.mkdir(parents=True, exist_ok=True)
+        audios = synthesize_texts(read_texts(Path(args.text_file)), model, processor, device, args.duration_scale,
+                                  args.batch_size)
+        for i, a in enumerate(audios):
+            save_audio(a.cpu().numpy(), out_dir / f"{i:05d}.wav", args.sample_rate)
+        logger.info(f"{len(audios)} files saved to: {out_dir}")
+        return
     _, audio = synthesize_text(args.text, model, processor, device, args.duration_scale)
     if audio is not None and audio.size(0) > 0:
         audio_np = audio[0, 0].cpu().numpy()

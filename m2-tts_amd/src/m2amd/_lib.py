@@ -103,6 +103,11 @@ _SIGNATURES = {
                                        c_vp]),
     "m2_inference_back_dev": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_size, c_vp, c_vp, c_vp, c_size,
                                       c_vp]),
+    "m2_ragged_workspace_bytes": (c_size, [c_vp, c_i32]),
+    "m2_mel_decoder_ragged": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_size, c_vp]),
+    "m2_vocoder_ragged": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp, c_size, c_vp]),
+    "m2_inference_back_ragged": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_size, c_vp, c_vp, c_vp, c_vp, c_size,
+                                         c_vp]),
 }
 
 # act codes (m2_common.h Act)
@@ -112,8 +117,11 @@ _lib = None
 _load_error = None
 
 
+M2_E_SHAPE = -2  # status codes (m2tts_hip.h) a caller acts on
+
+
 class M2Error(RuntimeError):
-    pass
+    status = None  # the library's status code, when the error came from a call
 
 
 def load(path: Path = None):
@@ -152,7 +160,9 @@ def exported_symbols():
 def check(rc: int, what: str = ""):
     if rc != 0:
         msg = _lib.m2_last_error().decode(errors="replace") if _lib is not None else ""
-        raise M2Error(f"{what or 'm2 call'} failed (status {rc}): {msg}")
+        err = M2Error(f"{what or 'm2 call'} failed (status {rc}): {msg}")
+        err.status = rc
+        raise err
 
 
 def call(name: str, *args):

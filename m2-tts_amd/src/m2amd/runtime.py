@@ -16,7 +16,7 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from . import _lib
-from .ops import f32c, require_device, stream_handle
+from .ops import expand_frames, f32c, frame_counts_sync, require_device, stream_handle
 
 Tensor = torch.Tensor
 
@@ -199,6 +199,88 @@ class HipModel:
         _lib.call("m2_inference_back", self.handle, B, S, T, front.data_ptr(), front.numel(), mel.data_ptr(),
                   audio.data_ptr(), ws.data_ptr(), ws.numel(), stream_handle(self.device))
         return mel, audio
+
+    # ------------------------------------------------------------ ragged batches
+    def inference_ragged(self, ids: Tensor, lengths: Optional[Tensor], scale: float,
+                         durations: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor]:
+        """Every utterance of the batch as if synthesized alone: (mel
+        [B,T_max,M], audio [B,1,64 T_max], frames int32 [B]) with utterance b
+        valid up to frames[b] and exactly zero behind.  Predicted durations:
+        m2_inference_front, then m2_inference_back_ragged.  Explicit
+        ``durations`` ([B,S], used as forward's target_durations): the stage
+        calls with m2_mel_decoder_ragged / m2_vocoder_ragged.  Raises M2Error
+        with status M2_E_SHAPE when the model's kernels take no per-utterance
+        frame count."""
+        if durations is None:
+            state, tmax = self.inference_front(ids, lengths, scale)
+            B, S, front = state[:3]
+            T = max(1, tmax)  # tts_model.py:158-160
+            mel = torch.empty(B, T, self.M, device=self.device, dtype=torch.float32)
+            audio = torch.empty(B, 1, 64 * T, device=self.device, dtype=torch.float32)
+            frames = torch.empty(B, device=self.device, dtype=torch.int32)
+            ws = self._scratch("_ws", self._size("m2_inference_workspace_bytes", B, S, T) +
+                               self._size("m2_ragged_workspace_bytes", B))
+            _lib.call("m2_inference_back_ragged", self.handle, B, S, T, front.data_ptr(), front.numel(),
+                      mel.data_ptr(), audio.data_ptr(), frames.data_ptr(), ws.data_ptr(), ws.numel(),
+                      stream_handle(self.device))
+            return mel, audio, frames
+        require_device(durations, what="M2TTSModel")
+        enc, _ = self.text_encoder(ids, lengths)
+        B, S, _ = enc.shape
+        if tuple(durations.shape) != (B, S):
+            raise ValueError(f"inference_ragged: durations must be [B, S] = {(B, S)}, got {tuple(durations.shape)}")
+        cum, tot, _, tmax = frame_counts_sync(durations, 1.0)
+        T = max(1, tmax)
+        frames = tot.clamp(min=1)
+        st = stream_handle(self.device)
+        mel = torch.empty(B, T, self.M, device=self.device, dtype=torch.float32)
+        audio = torch.empty(B, 1, 64 * T, device=self.device, dtype=torch.float32)
+        if B == 0:
+            return mel, audio, frames
+        reg = expand_frames(enc, cum, T)
+        ws = self._ragged_workspace(B, T)
+        _lib.call("m2_mel_decoder_ragged", self.handle, reg.data_ptr(), frames.data_ptr(), B, T, mel.data_ptr(),
+                  ws.data_ptr(), ws.numel(), st)
+        _lib.call("m2_vocoder_ragged", self.handle, mel.data_ptr(), 1, frames.data_ptr(), B, T, audio.data_ptr(),
+                  ws.data_ptr(), ws.numel(), st)
+        return mel, audio, frames
+
+    def decoder_ragged(self, x: Tensor, frames: Tensor) -> Tensor:
+        """m2_mel_decoder_ragged: x [B,T,H], frames int32 [B] -> mel [B,T,M],
+        utterance b decoded over its first frames[b] rows, zeros behind."""
+        x = f32c(x)
+        frames = self._frames(frames, x.shape[0])
+        B, T, _ = x.shape
+        mel = torch.empty(B, T, self.M, device=self.device, dtype=torch.float32)
+        ws = self.workspace(B, 0, T)
+        _lib.call("m2_mel_decoder_ragged", self.handle, x.data_ptr(), frames.data_ptr(), B, T, mel.data_ptr(),
+                  ws.data_ptr(), ws.numel(), stream_handle(self.device))
+        return mel
+
+    def vocoder_ragged(self, mel: Tensor, frames: Tensor, layout_btm: bool) -> Tensor:
+        """m2_vocoder_ragged: mel [B,M,T] (layout_btm False) or [B,T,M] ->
+        audio [B,1,64T], utterance b vocoded as a frames[b]-frame mel, zeros
+        behind 64 frames[b]."""
+        mel = f32c(mel)
+        frames = self._frames(frames, mel.shape[0])
+        B = mel.shape[0]
+        T = mel.shape[1] if layout_btm else mel.shape[2]
+        audio = torch.empty(B, 1, 64 * T, device=self.device, dtype=torch.float32)
+        ws = self._ragged_workspace(B, T)
+        _lib.call("m2_vocoder_ragged", self.handle, mel.data_ptr(), 1 if layout_btm else 0, frames.data_ptr(), B, T,
+                  audio.data_ptr(), ws.data_ptr(), ws.numel(), stream_handle(self.device))
+        return audio
+
+    def _ragged_workspace(self, B: int, T: int) -> Tensor:
+        """The stage workspace plus the ragged vocoder's end-window pass."""
+        return self._scratch("_ws", self._size("m2_workspace_bytes", B, 0, T) +
+                             self._size("m2_ragged_workspace_bytes", B))
+
+    def _frames(self, frames: Tensor, B: int) -> Tensor:
+        require_device(frames, what="frames")
+        if tuple(frames.shape) != (B,):
+            raise ValueError(f"frames must be [B] = [{B}], got {tuple(frames.shape)}")
+        return frames.to(torch.int32).contiguous()
 
     # ------------------------------------------------- device-side frame count
     def dev_supported(self, T_cap: int) -> bool:

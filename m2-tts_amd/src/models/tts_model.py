@@ -23,12 +23,12 @@ from __future__ import annotations
 
 import logging
 import weakref
-from typing import Any, Dict, Optional, Tuple
+from typing import Any, Dict, List, Optional, Tuple
 
 import torch
 import torch.nn as nn
 
-from m2amd import ops, runtime
+from m2amd import _lib, ops, runtime
 from m2amd.runtime import HandleCache, make_config
 
 from .components import (LightweightResBlock, PositionalEncoding, TransformerEncoderLayer, VariancePredictor,
@@ -40,6 +40,21 @@ Tensor = torch.Tensor
 UPSAMPLE_RATES = (4, 4, 2, 2)   # reference tts_model.py:244
 VOCODER_HALO = 3                # receptive field of one audio sample, mel frames per side (m2_vocoder_halo_frames)
 _HANDLES: "weakref.WeakKeyDictionary[nn.Module, HandleCache]" = weakref.WeakKeyDictionary()
+
+
+def unpad(mel: Tensor, audio: Tensor, frames: Tensor) -> List[Tuple[Tensor, Tensor]]:
+    """The utterances of an ``inference_ragged`` result without their padding:
+    a list of (mel_b [T_b, M], audio_b [64 T_b]) views, T_b = frames[b].  Pure
+    indexing (one host read of ``frames``), on any device."""
+    if mel.dim() != 3 or audio.dim() != 3 or audio.shape[1] != 1 or audio.shape[2] != 64 * mel.shape[1]:
+        raise ValueError(f"unpad: expected mel [B,T,M] and audio [B,1,64T], got {tuple(mel.shape)} and "
+                         f"{tuple(audio.shape)}")
+    counts = [int(t) for t in frames.tolist()]
+    if len(counts) != mel.shape[0] or audio.shape[0] != mel.shape[0]:
+        raise ValueError(f"unpad: {len(counts)} frame counts for a batch of {mel.shape[0]}")
+    if any(t < 0 or t > mel.shape[1] for t in counts):
+        raise ValueError(f"unpad: frame counts {counts} outside [0, {mel.shape[1]}]")
+    return [(mel[b, :t], audio[b, 0, :64 * t]) for b, t in enumerate(counts)]
 
 
 def _owner_handle(stage: nn.Module, attr: str, device: torch.device):
@@ -313,6 +328,56 @@ class M2TTSModel(nn.Module):
         with torch.no_grad():
             mel, audio = self._hip(phoneme_ids.device).inference(phoneme_ids, phoneme_lengths, duration_scale)
         return mel, audio
+
+    def inference_ragged(self, phoneme_ids: Tensor, phoneme_lengths: Optional[Tensor] = None,
+                         duration_scale: float = 1.0,
+                         durations: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor]:
+        """A batch of independent requests: (mel [B,T_max,M], audio
+        [B,1,64 T_max], frames int64 [B]).  frames[b] = T_b is utterance b's own
+        frame count, max(1, sum_s int(d[b,s])) with d = ``durations`` ([B,S],
+        used as forward's target_durations) or duration_pred * duration_scale;
+        mel[b, :T_b] and audio[b, 0, :64 T_b] are what the single-utterance
+        call on the same S columns returns (within the parity tolerance: tile
+        forms differ between a batch and a single call), everything behind is
+        exactly 0.  With equal T_b the result is inference()'s, bit for bit.
+        ``unpad`` splits the result.  inference() and forward() keep the
+        reference's batch-coupled semantics (every utterance decoded over
+        T_max rows)."""
+        self._eval_if_training()
+        ops.require_device(phoneme_ids, phoneme_lengths, durations, what="M2TTSModel")
+        with torch.no_grad():
+            hm = self._hip(phoneme_ids.device)
+            try:
+                mel, audio, frames = hm.inference_ragged(phoneme_ids, phoneme_lengths, duration_scale, durations)
+            except ops.M2Error as e:
+                if e.status != _lib.M2_E_SHAPE:
+                    raise
+                if not self.__dict__.get("_m2_ragged_warned"):
+                    self.__dict__["_m2_ragged_warned"] = True
+                    logger.warning(f"inference_ragged: running the utterances one by one ({e})")
+                mel, audio, frames = self._ragged_one_by_one(phoneme_ids, phoneme_lengths, duration_scale, durations)
+        return mel, audio, frames.to(torch.int64)
+
+    def _ragged_one_by_one(self, ids: Tensor, lengths: Optional[Tensor], scale: float, durations: Optional[Tensor]):
+        """inference_ragged by its definition: B single-utterance calls,
+        assembled into the zero-padded outputs."""
+        outs = []
+        for b in range(ids.shape[0]):
+            lb = lengths[b:b + 1] if lengths is not None else None
+            if durations is None:
+                outs.append(self.inference(ids[b:b + 1], lb, scale))
+            else:
+                r = self(ids[b:b + 1], lb, target_durations=durations[b:b + 1])
+                outs.append((r["mel_output"], r["audio_output"]))
+        dev = ids.device
+        frames = torch.tensor([m.shape[1] for m, _ in outs], dtype=torch.int64, device=dev)
+        T = max([m.shape[1] for m, _ in outs], default=1)
+        mel = torch.zeros(len(outs), T, self._m2_cfg.mel_channels, device=dev, dtype=torch.float32)
+        audio = torch.zeros(len(outs), 1, 64 * T, device=dev, dtype=torch.float32)
+        for b, (m, a) in enumerate(outs):
+            mel[b, :m.shape[1]] = m[0]
+            audio[b, 0, :a.shape[2]] = a[0, 0]
+        return mel, audio, frames
 
     def get_model_size(self) -> Dict[str, Any]:
         """Parameter counts per component (reference tts_model.py:440-459)."""
