@@ -467,6 +467,78 @@ int32_t m2_eval_dct_table(int32_t n_mels, double* out_host);
 int32_t m2_eval_mcd(const float* pred, const float* target, const int32_t* cols, const double* table, int32_t B,
                     int32_t n_mels, int32_t Tp, int32_t Tt, int32_t pred_transposed, double* out, void* stream);
 
+/* ---- training losses, forward values (src/training/losses.py) ---------------
+ * No gradients.  Per-utterance rows of double sums as above, columns named by
+ * m2_loss_column_count(kind) / m2_loss_column_name(kind, i): kind 0 =
+ * m2_loss_spectral, 1 = m2_disc_losses.  Fixed-order reductions: equal inputs
+ * give equal bits, and a batched row equals the row of the utterance alone.
+ *
+ * m2_conv1d_strided: y = leaky(conv1d(x; w [Cout, Cin/groups, k], b (or NULL),
+ * stride, zero padding, groups), slope), leaky(v) = v > 0 ? v : slope v
+ * (slope 1: no activation; the discriminators use 0.2).  x [B,Cin,L] ->
+ * y [B,Cout,(L + 2 padding - k)/stride + 1]; groups divides both channel
+ * counts.  Cout >= 16 with (Cin/groups) k >= 32 runs on the exact-f32 MFMA.
+ * m2_avg_pool1d: F.avg_pool1d(x [B,C,L], k, stride k) -> [B,C,L/k] (the tail
+ * samples are dropped).
+ *
+ * m2_disc: the discriminators of one MultiScaleDiscriminator (losses.py:59-117,
+ * seven Conv1d each), packed once from `weights`: n_scales * 14 device
+ * pointers in state_dict order (weight, bias per layer; PyTorch layouts).
+ * Scale s reads avg_pool1d(x, scales[s]).
+ *   m2_disc_layer_shape: channels and length of layer `layer` (0..6) of scale
+ *     index s for audio of L samples.
+ *   m2_disc_layer: one packed layer on its own: x [B,Cin,L] (the previous
+ *     layer's output, or the pooled audio for layer 0) -> y [B,Cout,len],
+ *     LeakyReLU(0.2) applied to x for layer > 0, none to y.
+ *   m2_disc_forward: x [B,1,L] -> logits: the last layers' outputs
+ *     [B,1,len(s,6)], scale after scale; features (or NULL): the six other
+ *     layers' outputs [B,C,len(s,l)] before the LeakyReLU(0.2), as the
+ *     reference collects them (losses.py:109-112; the next layer's loader
+ *     applies the slope), scale-major, layer-minor, each contiguous.
+ *   m2_disc_losses: real and/or fake [B,1,L] (NULL: absent, its sums are 0) ->
+ *     out [B, K].  Per scale: s<i>_real_err_sq = sum (D(real) - 1)^2,
+ *     s<i>_real_sq, s<i>_fake_err_sq, s<i>_fake_sq, s<i>_logits (their count);
+ *     per scale and layer: s<i>_l<j>_abs_diff = sum |f_fake - f_real|,
+ *     s<i>_l<j>_count.  Three scales.  No feature map leaves the workspace.
+ *   Both walk the batch in slices whose activations fit m2_disc_set_slice_bytes
+ *   (default, and 0: 1 GiB - B = 32 utterances of 32000 samples in one slice;
+ *   at least one utterance per slice); the workspace queries follow it.
+ *
+ * m2_loss_spectral: pred, target [B,L] through torch.stft(n_fft, hop,
+ * center=True, pad_mode='reflect', periodic Hann) of the handle's n_fft and
+ * hop (L > n_fft/2).  Per utterance mag_abs = sum | |P| - |T| |, phase_abs =
+ * sum |angle P - angle T|, bins, mel_log_abs = sum over frames and the
+ * n_weights weights w_j (device floats, or NULL with 0) of |ln(w_j sum_f |P| +
+ * 1e-8) - ln(w_j sum_f |T| + 1e-8)| (PerceptualLoss._mel_features: its filter
+ * rows are constant), frames.  spec_pred / spec_target (or NULL): the
+ * complex64 spectra [B, frames, n_fft/2+1] the sums were taken from; DC and
+ * Nyquist bins have imaginary part +0. */
+typedef struct m2_disc m2_disc;
+int32_t m2_loss_column_count(int32_t kind);
+const char* m2_loss_column_name(int32_t kind, int32_t index);
+int32_t m2_conv1d_strided(const float* x, const float* w, const float* b, int32_t ksize, int32_t stride,
+                          int32_t padding, int32_t groups, float leaky_slope, int32_t B, int32_t Cin, int32_t Cout,
+                          int32_t L, float* y, void* stream);
+int32_t m2_avg_pool1d(const float* x, int32_t ksize, int32_t B, int32_t C, int32_t L, float* y, void* stream);
+int32_t m2_disc_create(const float* const* weights, int32_t count, const int32_t* scales, int32_t n_scales,
+                       void* stream, m2_disc** out);
+int32_t m2_disc_destroy(m2_disc* disc);
+int32_t m2_disc_set_slice_bytes(m2_disc* disc, size_t bytes);
+int32_t m2_disc_layer_shape(const m2_disc* disc, int32_t L, int32_t scale_index, int32_t layer, int32_t* channels,
+                            int32_t* length);
+int32_t m2_disc_layer(const m2_disc* disc, int32_t scale_index, int32_t layer, const float* x, int32_t B, int32_t L,
+                      float* y, void* stream);
+size_t m2_disc_forward_workspace_bytes(const m2_disc* disc, int32_t B, int32_t L);
+int32_t m2_disc_forward(const m2_disc* disc, const float* x, int32_t B, int32_t L, float* logits, float* features,
+                        void* workspace, size_t workspace_bytes, void* stream);
+size_t m2_disc_losses_workspace_bytes(const m2_disc* disc, int32_t B, int32_t L);
+int32_t m2_disc_losses(const m2_disc* disc, const float* real, const float* fake, int32_t B, int32_t L, double* out,
+                       void* workspace, size_t workspace_bytes, void* stream);
+size_t m2_loss_spectral_workspace_bytes(const m2_dsp* dsp, int32_t B, int32_t L);
+int32_t m2_loss_spectral(const m2_dsp* dsp, const float* pred, const float* target, int32_t B, int32_t L,
+                         const float* mel_weights, int32_t n_weights, double* out, void* spec_pred, void* spec_target,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- measurement ----------------------------------------------------------
  * Kernel timing with HIP events recorded on the launch stream around each of
  * the fused vocoder's kernels (bench.py's roofline).  enable: allocate event

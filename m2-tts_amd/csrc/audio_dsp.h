@@ -1,5 +1,6 @@
-// What the audio kernels share (audio_dsp.hip, eval_metrics.hip): the frame
-// workgroup size, the in-LDS FFT, the frame loader and the m2_dsp handle.
+// What the audio kernels share (audio_dsp.hip, eval_metrics.hip, losses.hip):
+// the frame workgroup size, the in-LDS FFT, the frame loaders with their
+// padding modes, the fixed-order workgroup sum and the m2_dsp handle.
 #pragma once
 
 #include "m2_common.h"
@@ -36,16 +37,50 @@ __device__ float2* fft_lds(float2* a, float2* b, const float2* __restrict__ tw) 
     return x;
 }
 
-// Frame t of utterance b: samples t*hop - N/2 + n (centre padding, zero
-// outside [0, L)) times the window, into LDS as complex.
-template <int N>
+// Sample index of a centre-padded frame: i itself inside [0, L); outside, -1
+// (a zero sample: librosa pad_mode='constant', the default) or, REFLECT, the
+// mirrored index (torch.stft pad_mode='reflect'; needs L > N / 2).
+template <bool REFLECT>
+__device__ __forceinline__ int pad_index(int i, int L) {
+    if (i >= 0 && i < L) return i;
+    if (!REFLECT) return -1;
+    return i < 0 ? -i : 2 * (L - 1) - i;
+}
+
+// Frame t of utterance b: samples t*hop - N/2 + n (centre padding) times the
+// window, into LDS as complex.
+template <int N, bool REFLECT = false>
 __device__ void load_frame(const float* __restrict__ y, int L, int hop, int t, const float* __restrict__ win, float2* a) {
     const int s0 = t * hop - N / 2;
     for (int n = threadIdx.x; n < N; n += NT) {
-        const int i = s0 + n;
-        a[n] = make_float2((i >= 0 && i < L) ? y[i] * win[n] : 0.f, 0.f);
+        const int i = pad_index<REFLECT>(s0 + n, L);
+        a[n] = make_float2(i >= 0 ? y[i] * win[n] : 0.f, 0.f);
     }
     __syncthreads();
+}
+
+// load_frame for a pair: pred in the real part, target in the imaginary part.
+template <int N, bool REFLECT = false>
+__device__ void load_pair_frame(const float* __restrict__ p, const float* __restrict__ q, int L, int hop, int t,
+                                const float* __restrict__ win, float2* a) {
+    const int s0 = t * hop - N / 2;
+    for (int n = threadIdx.x; n < N; n += NT) {
+        const int i = pad_index<REFLECT>(s0 + n, L);
+        a[n] = make_float2(i >= 0 ? p[i] * win[n] : 0.f, i >= 0 ? q[i] * win[n] : 0.f);
+    }
+    __syncthreads();
+}
+
+// Sum over the workgroup in a fixed order; every thread must call it.
+__device__ __forceinline__ double block_sum(double v, double* red) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    __syncthreads();
+    if (lane == 0) red[wv] = v;
+    __syncthreads();
+    v = red[0];
+    for (int i = 1; i < nw; ++i) v += red[i];
+    return v;
 }
 
 }  // namespace dsp

@@ -32,6 +32,7 @@
 namespace m2 {
 namespace eval {
 
+using dsp::block_sum;
 using dsp::NT;
 
 constexpr int kFramePart = 5;   // per frame: err^2, ref^2, log^2, centroid, bandwidth
@@ -48,32 +49,6 @@ const char* const kMcdCols[] = {"mcd_sum", "frames"};
 constexpr int kAudioK = sizeof(kAudioCols) / sizeof(kAudioCols[0]);
 constexpr int kPairK = sizeof(kPairCols) / sizeof(kPairCols[0]);
 constexpr int kMcdK = sizeof(kMcdCols) / sizeof(kMcdCols[0]);
-
-// Sum over the workgroup in a fixed order; every thread must call it.
-__device__ double block_sum(double v, double* red) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    __syncthreads();
-    if (lane == 0) red[wv] = v;
-    __syncthreads();
-    v = red[0];
-    for (int i = 1; i < nw; ++i) v += red[i];
-    return v;
-}
-
-// load_frame for a pair: pred in the real part, target in the imaginary
-// part, both zero outside [0, L).
-template <int N>
-__device__ void load_pair_frame(const float* __restrict__ p, const float* __restrict__ q, int L, int hop, int t,
-                                const float* __restrict__ win, float2* a) {
-    const int s0 = t * hop - N / 2;
-    for (int n = threadIdx.x; n < N; n += NT) {
-        const int i = s0 + n;
-        const bool in = i >= 0 && i < L;
-        a[n] = make_float2(in ? p[i] * win[n] : 0.f, in ? q[i] * win[n] : 0.f);
-    }
-    __syncthreads();
-}
 
 // grid (frames of the un-cut pred, B); part [B, frames, kFramePart].
 template <int N>
@@ -92,7 +67,7 @@ __global__ __launch_bounds__(NT) void eval_frame_kernel(const float* __restrict_
     const bool own = !paired || (Lp > L && t * hop + N / 2 > L);
     double err = 0.0, ref = 0.0, lsd = 0.0;
     if (paired) {
-        load_pair_frame<N>(p, target + (size_t)u * Lt, L, hop, t, win, a);
+        dsp::load_pair_frame<N>(p, target + (size_t)u * Lt, L, hop, t, win, a);
         const float2* Z = dsp::fft_lds<N, false>(a, b, tw);
         for (int f = threadIdx.x; f < F; f += NT) {
             const float2 zf = Z[f], zn = Z[(N - f) & (N - 1)];

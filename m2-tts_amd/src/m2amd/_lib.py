@@ -91,6 +91,22 @@ _SIGNATURES = {
     "m2_eval_dct_table": (c_i32, [c_i32, ctypes.POINTER(ctypes.c_double)]),
     "m2_eval_mcd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "m2_transformer_path": (c_i32, [c_vp]),
+    "m2_loss_column_count": (c_i32, [c_i32]),
+    "m2_loss_column_name": (ctypes.c_char_p, [c_i32, c_i32]),
+    "m2_conv1d_strided": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_i32, c_i32, c_i32, c_i32, c_vp,
+                                  c_vp]),
+    "m2_avg_pool1d": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    "m2_disc_create": (c_i32, [ctypes.POINTER(c_vp), c_i32, ctypes.POINTER(c_i32), c_i32, c_vp, ctypes.POINTER(c_vp)]),
+    "m2_disc_destroy": (c_i32, [c_vp]),
+    "m2_disc_set_slice_bytes": (c_i32, [c_vp, c_size]),
+    "m2_disc_layer_shape": (c_i32, [c_vp, c_i32, c_i32, c_i32, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32)]),
+    "m2_disc_layer": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp]),
+    "m2_disc_forward_workspace_bytes": (c_size, [c_vp, c_i32, c_i32]),
+    "m2_disc_forward": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_size, c_vp]),
+    "m2_disc_losses_workspace_bytes": (c_size, [c_vp, c_i32, c_i32]),
+    "m2_disc_losses": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_size, c_vp]),
+    "m2_loss_spectral_workspace_bytes": (c_size, [c_vp, c_i32, c_i32]),
+    "m2_loss_spectral": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_size, c_vp]),
     "m2_front_bytes": (c_size, [c_vp, c_i32, c_i32]),
     "m2_inference_workspace_bytes": (c_size, [c_vp, c_i32, c_i32, c_i32]),
     "m2_inference_front": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_vp, c_size, c_vp, c_size, c_vp, c_vp]),

@@ -135,6 +135,41 @@ class Dsp:
                   0 if q is None else q.shape[1], out.data_ptr(), ws.data_ptr(), ws.numel(), stream_handle(y.device))
         return out
 
+    def loss_spectral(self, pred: Tensor, target: Tensor, mel_weights: Optional[Tensor] = None,
+                      spectra: bool = False):
+        """The sums behind SpectralLoss.stft_loss and PerceptualLoss (losses.py:21-47,
+        180-205) for pred, target [B, L] under torch.stft's framing (centre,
+        reflect padding) at this handle's n_fft and hop -> float64 [B, K] on the
+        device, columns ``loss_columns("spectral")`` (m2_loss_spectral).  With
+        ``spectra`` also the complex64 spectra [B, F, T] of pred and of target
+        the sums were taken from."""
+        y, q = self._audio(pred), self._audio(target)
+        if y.shape != q.shape:
+            raise ValueError(f"loss_spectral: pred {tuple(y.shape)} and target {tuple(q.shape)} differ")
+        B, L = y.shape
+        if L <= self.n_fft // 2:
+            raise RuntimeError(f"loss_spectral: reflect padding of n_fft {self.n_fft} needs more than "
+                               f"{self.n_fft // 2} samples, got {L}")
+        w = None
+        if mel_weights is not None:
+            require_device(mel_weights, what="m2 dsp")
+            w = mel_weights.float().contiguous()
+        out = torch.empty(B, len(loss_columns("spectral")), device=y.device, dtype=torch.float64)
+        sp = st = None
+        if spectra:
+            sp = torch.empty(B, self.frames(L), self.F, 2, device=y.device, dtype=torch.float32)
+            st = torch.empty_like(sp)
+        need = int(_lib.load().m2_loss_spectral_workspace_bytes(self.handle, B, L))
+        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=y.device)
+        _lib.call("m2_loss_spectral", self.handle, y.data_ptr(), q.data_ptr(), B, L,
+                  None if w is None else w.data_ptr(), 0 if w is None else w.numel(), out.data_ptr(),
+                  None if sp is None else sp.data_ptr(), None if st is None else st.data_ptr(), ws.data_ptr(),
+                  ws.numel(), stream_handle(y.device))
+        if spectra:
+            return out, torch.view_as_complex(sp).transpose(1, 2), torch.view_as_complex(st).transpose(1, 2)
+        return out
+
+
 
 _CACHE: Dict[Tuple, Dsp] = {}
 
@@ -161,6 +196,20 @@ def eval_columns(kind: str) -> Tuple[str, ...]:
         lib, k = _lib.load(), _EVAL_KINDS[kind]
         cols = _EVAL_COLUMNS[kind] = tuple(lib.m2_eval_column_name(k, i).decode()
                                            for i in range(lib.m2_eval_column_count(k)))
+    return cols
+
+
+_LOSS_KINDS = {"spectral": 0, "disc": 1}
+_LOSS_COLUMNS: Dict[str, Tuple[str, ...]] = {}
+
+
+def loss_columns(kind: str) -> Tuple[str, ...]:
+    """Column names of the rows of Dsp.loss_spectral ("spectral") and ops.Discriminators.losses ("disc")."""
+    cols = _LOSS_COLUMNS.get(kind)
+    if cols is None:
+        lib, k = _lib.load(), _LOSS_KINDS[kind]
+        cols = _LOSS_COLUMNS[kind] = tuple(lib.m2_loss_column_name(k, i).decode()
+                                           for i in range(lib.m2_loss_column_count(k)))
     return cols
 
 

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes
 import math
+import weakref
 from typing import Optional
 
 import torch
@@ -118,6 +119,145 @@ def conv_transpose1d(x: Tensor, weight: Tensor, bias: Tensor, rate: int, *, act:
     _lib.call("m2_conv_transpose1d", _ptr(x), _ptr(f32c(weight)), _ptr(f32c(bias)), rate, act, B, Cin, Cout, L,
               _ptr(y), stream_handle(x.device))
     return y
+
+
+def conv1d_strided(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None, *, stride: int = 1, padding: int = 0,
+                   groups: int = 1, leaky_slope: float = 1.0) -> Tensor:
+    """leaky(F.conv1d(x, weight [Cout, Cin/groups, k], bias, stride, padding, groups=groups), slope)
+    (m2_conv1d_strided; slope 1.0: no activation), x [B,Cin,L] -> [B,Cout,(L + 2 padding - k)//stride + 1]."""
+    require_device(x, weight, bias, what="conv1d_strided")
+    x = f32c(x)
+    B, Cin, L = x.shape
+    Cout, Cg, K = weight.shape
+    if groups < 1 or Cin % groups or Cout % groups or Cg * groups != Cin:
+        raise ValueError(f"conv1d_strided: weight {tuple(weight.shape)} and groups {groups} do not fit x {tuple(x.shape)}")
+    Lo = (L + 2 * padding - K) // stride + 1
+    y = torch.empty(B, Cout, max(Lo, 0), device=x.device, dtype=torch.float32)
+    _lib.call("m2_conv1d_strided", _ptr(x), _ptr(f32c(weight)), None if bias is None else _ptr(f32c(bias)), K,
+              int(stride), int(padding), int(groups), float(leaky_slope), B, Cin, Cout, L, _ptr(y),
+              stream_handle(x.device))
+    return y
+
+
+def avg_pool1d(x: Tensor, kernel_size: int) -> Tensor:
+    """F.avg_pool1d(x [B,C,L], k, stride=k) -> [B,C,L//k] (m2_avg_pool1d)."""
+    require_device(x, what="avg_pool1d")
+    x = f32c(x)
+    B, C, L = x.shape
+    y = torch.empty(B, C, L // kernel_size, device=x.device, dtype=torch.float32)
+    _lib.call("m2_avg_pool1d", _ptr(x), int(kernel_size), B, C, L, _ptr(y), stream_handle(x.device))
+    return y
+
+
+class Discriminators:
+    """The packed discriminators of one MultiScaleDiscriminator on one device
+    (m2_disc_*): ``tensors`` are its state_dict values in order (weight, bias
+    of the seven convs of every scale)."""
+
+    LAYERS = 7
+    # Cin, Cout, k, stride, padding, groups (losses.py:69-91)
+    LAYER_TABLE = ((1, 64, 15, 1, 7, 1), (64, 128, 41, 4, 20, 4), (128, 256, 41, 4, 20, 16), (256, 512, 41, 4, 20, 64),
+                   (512, 1024, 41, 4, 20, 256), (1024, 1024, 5, 1, 2, 1), (1024, 1, 3, 1, 1, 1))
+
+    def __init__(self, tensors, scales, device: torch.device):
+        lib = _lib.load()
+        self.device = torch.device(device)
+        self.scales = [int(s) for s in scales]
+        keep = []
+        for t in tensors:
+            require_device(t, what="discriminator weight")
+            keep.append(f32c(t.detach()))
+        ptrs = (ctypes.c_void_p * len(keep))(*[t.data_ptr() for t in keep])
+        sc = (ctypes.c_int32 * len(self.scales))(*self.scales)
+        h = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            _lib.check(lib.m2_disc_create(ptrs, len(keep), sc, len(self.scales), stream_handle(self.device),
+                                          ctypes.byref(h)), "m2_disc_create")
+        self.handle = h
+        self._finalizer = weakref.finalize(self, lib.m2_disc_destroy, h)
+
+    def set_slice_bytes(self, nbytes: int):
+        """Bound the activations one batch slice of forward / losses may take (0: the default, 1 GiB)."""
+        _lib.call("m2_disc_set_slice_bytes", self.handle, int(nbytes))
+
+    def shapes(self, L: int):
+        """[(channels, length)] of the seven layers of every scale for audio of L samples."""
+        lib = _lib.load()
+        c, n = ctypes.c_int32(), ctypes.c_int32()
+        out = []
+        for s in range(len(self.scales)):
+            row = []
+            for layer in range(self.LAYERS):
+                _lib.check(lib.m2_disc_layer_shape(self.handle, L, s, layer, ctypes.byref(c), ctypes.byref(n)),
+                           "m2_disc_layer_shape")
+                row.append((c.value, n.value))
+            out.append(row)
+        return out
+
+    def layer(self, scale_index: int, layer: int, x: Tensor) -> Tensor:
+        """One packed layer (m2_disc_layer): x [B,Cin,L], the previous layer's output (the
+        LeakyReLU(0.2) between them is applied here) or the pooled audio -> [B,Cout,len]."""
+        require_device(x, what="discriminator")
+        x = f32c(x)
+        B, _, L = x.shape
+        c = self.LAYER_TABLE[layer]
+        if x.shape[1] != c[0]:
+            raise ValueError(f"discriminator layer {layer}: {c[0]} input channels, got {x.shape[1]}")
+        n = (L + 2 * c[4] - c[2]) // c[3] + 1
+        y = torch.empty(B, c[1], n, device=x.device, dtype=torch.float32)
+        _lib.call("m2_disc_layer", self.handle, int(scale_index), int(layer), _ptr(x), B, L, _ptr(y),
+                  stream_handle(x.device))
+        return y
+
+    def _audio(self, x: Tensor) -> Tensor:
+        require_device(x, what="discriminator")
+        if x.dim() != 3 or x.shape[1] != 1:
+            raise ValueError(f"discriminator: audio must be [B, 1, L], got {tuple(x.shape)}")
+        return f32c(x.detach().float())
+
+    def forward(self, x: Tensor, features: bool = True):
+        """x [B,1,L] -> (logits per scale, the six feature maps per scale or None)."""
+        x = self._audio(x)
+        B, _, L = x.shape
+        shapes = self.shapes(L)
+        logits = torch.empty(B * sum(row[-1][1] for row in shapes), device=x.device, dtype=torch.float32)
+        feats = None
+        if features:
+            feats = torch.empty(B * sum(c * n for row in shapes for c, n in row[:-1]), device=x.device,
+                                dtype=torch.float32)
+        need = int(_lib.load().m2_disc_forward_workspace_bytes(self.handle, B, L))
+        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=x.device)
+        _lib.call("m2_disc_forward", self.handle, _ptr(x), B, L, _ptr(logits), _ptr(feats), _ptr(ws), ws.numel(),
+                  stream_handle(x.device))
+        outs, maps, lo, fo = [], [], 0, 0
+        for row in shapes:
+            n = row[-1][1]
+            outs.append(logits[lo:lo + B * n].view(B, 1, n))
+            lo += B * n
+            if features:
+                m = []
+                for c, n in row[:-1]:
+                    m.append(feats[fo:fo + B * c * n].view(B, c, n))
+                    fo += B * c * n
+                maps.append(m)
+        return outs, (maps if features else None)
+
+    def losses(self, real: Optional[Tensor], fake: Optional[Tensor]) -> Tensor:
+        """The logit and feature-matching sums of real and/or fake [B,1,L] ->
+        float64 [B, K] on the device, columns ``dsp.loss_columns("disc")``."""
+        real = None if real is None else self._audio(real)
+        fake = None if fake is None else self._audio(fake)
+        ref = real if real is not None else fake
+        if real is not None and fake is not None and real.shape != fake.shape:
+            raise ValueError(f"discriminator: real {tuple(real.shape)} and fake {tuple(fake.shape)} differ")
+        B, _, L = ref.shape
+        lib = _lib.load()
+        out = torch.zeros(B, lib.m2_loss_column_count(1), device=ref.device, dtype=torch.float64)
+        need = int(lib.m2_disc_losses_workspace_bytes(self.handle, B, L))
+        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=ref.device)
+        _lib.call("m2_disc_losses", self.handle, _ptr(real), _ptr(fake), B, L, _ptr(out), _ptr(ws), ws.numel(),
+                  stream_handle(ref.device))
+        return out
 
 
 def embed_positional(ids: Tensor, emb: Tensor, pe: Tensor, scale: float) -> Tensor:

@@ -1,0 +1,381 @@
+"""Loss functions of M2 TTS training, stage 2 (reference src/training/losses.py).
+
+Same class names, constructor signatures, defaults, attribute names,
+state_dict keys and returned dict keys as the reference, computed on the GPU:
+the discriminators' convolutions, the STFTs and every reduction run in the
+m2_disc_* / m2_loss_spectral / m2_eval_pair_stats kernels (m2amd.ops,
+m2amd.dsp), which write per-utterance rows of double sums; a few torch ops on
+the device turn those rows into the reference's means, so a call needs no host
+synchronisation.
+
+**Forward values only.**  Every returned value is a 0-dim float32 tensor on the
+inputs' device with ``requires_grad=False``: the values carry no autograd
+graph, the same contract M2TTSModel.forward has in this tree.  They score a
+checkpoint with the objective it was trained on; ``backward()`` through them
+is not available, and the trainers are not part of this package.
+
+The discriminators' parameters live in plain ``nn.Conv1d`` modules built in the
+reference's order, so ``torch.manual_seed(s); CombinedTTSLoss()`` gives the
+reference's weights bit for bit and the reference's checkpoints load.  Packed
+copies are cached per device and rebuilt when a parameter changes
+(``load_state_dict``, ``.to``, an optimizer step).
+
+Like the rest of the product path there is no CPU fallback: CPU tensors raise
+RuntimeError (the module itself imports and constructs anywhere).
+"""
+from __future__ import annotations
+
+import logging
+from typing import Dict, Optional, Tuple
+
+import torch
+import torch.nn as nn
+
+logger = logging.getLogger(__name__)
+
+Tensor = torch.Tensor
+SAMPLE_RATE = 22050  # names the m2_dsp tables; no loss depends on it
+
+
+def _require(*tensors, what: str):
+    from m2amd.ops import require_device
+    require_device(*tensors, what=what)
+
+
+def _audio_pair(pred: Tensor, target: Tensor, what: str) -> Tuple[Tensor, Tensor]:
+    """pred, target [B, 1, L] (or [B, L]) -> float32 [B, L] each."""
+    _require(pred, target, what=what)
+    p = pred.detach().float().reshape(pred.shape[0], -1)
+    t = target.detach().float().reshape(target.shape[0], -1)
+    if p.shape != t.shape:
+        raise RuntimeError(f"{what}: pred audio {tuple(pred.shape)} and target audio {tuple(target.shape)} differ")
+    return p, t
+
+
+def _spectral_rows(p: Tensor, t: Tensor, n_fft: int, hop: int, cache: Optional[dict]) -> Dict[str, Tensor]:
+    """Batch sums (0-dim float64) of Dsp.loss_spectral's columns; ``cache`` shares a
+    framing between SpectralLoss and PerceptualLoss within one call."""
+    key = (n_fft, hop)
+    if cache is not None and key in cache:
+        return cache[key]
+    from m2amd.dsp import get_dsp, loss_columns
+    d = get_dsp(SAMPLE_RATE, n_fft, hop, n_fft, device=p.device)
+    sums = d.loss_spectral(p, t, PerceptualLoss.mel_weights(p.device, n_fft // 2 + 1)).sum(0)
+    rows = {name: sums[i] for i, name in enumerate(loss_columns("spectral"))}
+    if cache is not None:
+        cache[key] = rows
+    return rows
+
+
+class SpectralLoss(nn.Module):
+    """Multi-scale spectral loss: per n_fft, mean | |P| - |T| | + 0.1 mean |angle P - angle T|
+    over torch.stft(hop n_fft * factor, Hann, centre, reflect padding), averaged over the sizes."""
+
+    def __init__(self, n_fft_list=[512, 1024, 2048], hop_length_factor=0.25):
+        super().__init__()
+        self.n_fft_list = n_fft_list
+        self.hop_length_factor = hop_length_factor
+
+    def _stft_loss(self, p: Tensor, t: Tensor, n_fft: int, cache: Optional[dict]) -> Tensor:
+        r = _spectral_rows(p, t, n_fft, int(n_fft * self.hop_length_factor), cache)
+        return r["mag_abs"] / r["bins"] + r["phase_abs"] / r["bins"] * 0.1
+
+    def stft_loss(self, pred_audio, target_audio, n_fft):
+        """The loss of one STFT size."""
+        with torch.no_grad():
+            p, t = _audio_pair(pred_audio, target_audio, "SpectralLoss")
+            return self._stft_loss(p, t, n_fft, None).float()
+
+    def _value(self, p: Tensor, t: Tensor, cache: Optional[dict]) -> Tensor:
+        total = 0
+        for n_fft in self.n_fft_list:
+            total = total + self._stft_loss(p, t, n_fft, cache)
+        return total / len(self.n_fft_list)
+
+    def forward(self, pred_audio, target_audio):
+        with torch.no_grad():
+            p, t = _audio_pair(pred_audio, target_audio, "SpectralLoss")
+            return self._value(p, t, None).float()
+
+
+class MultiScaleDiscriminator(nn.Module):
+    """Multi-scale discriminator: seven Conv1d per scale, scale i on avg_pool1d(x, scales[i])."""
+
+    def __init__(self, scales=[1, 2, 4]):
+        super().__init__()
+        self.scales = scales
+        self.discriminators = nn.ModuleList([
+            self._make_discriminator() for _ in scales
+        ])
+
+    def _make_discriminator(self):
+        return nn.Sequential(
+            nn.Conv1d(1, 64, 15, 1, padding=7),
+            nn.LeakyReLU(0.2),
+            nn.Conv1d(64, 128, 41, 4, padding=20, groups=4),
+            nn.LeakyReLU(0.2),
+            nn.Conv1d(128, 256, 41, 4, padding=20, groups=16),
+            nn.LeakyReLU(0.2),
+            nn.Conv1d(256, 512, 41, 4, padding=20, groups=64),
+            nn.LeakyReLU(0.2),
+            nn.Conv1d(512, 1024, 41, 4, padding=20, groups=256),
+            nn.LeakyReLU(0.2),
+            nn.Conv1d(1024, 1024, 5, 1, padding=2),
+            nn.LeakyReLU(0.2),
+            nn.Conv1d(1024, 1, 3, 1, padding=1),
+        )
+
+    def _handle(self, device: torch.device):
+        """The packed discriminators on ``device``, rebuilt when a parameter changed."""
+        from m2amd.ops import Discriminators
+        from m2amd.runtime import state_key
+        key = state_key(self)
+        handles = self.__dict__.setdefault("_m2_handles", {})
+        ent = handles.get(device)
+        if ent is not None and ent[0] == key:
+            return ent[1]
+        tensors = list(self.state_dict(keep_vars=True).values())
+        _require(*tensors, what="MultiScaleDiscriminator")
+        if any(t.device != device for t in tensors):
+            raise RuntimeError(f"MultiScaleDiscriminator: parameters on {tensors[0].device}, audio on {device}")
+        h = Discriminators(tensors, self.scales, device)
+        handles[device] = (key, h)
+        return h
+
+    def forward(self, x):
+        """x [B, 1, L] -> (logits per scale, the six pre-activation feature maps per scale)."""
+        _require(x, what="MultiScaleDiscriminator")
+        with torch.no_grad():
+            return self._handle(x.device).forward(x, features=True)
+
+    def _sums(self, real: Optional[Tensor], fake: Optional[Tensor]) -> Dict[str, Tensor]:
+        """Batch sums (0-dim float64) of the m2_disc_losses columns."""
+        from m2amd.dsp import loss_columns
+        ref = real if real is not None else fake
+        _require(real, fake, what="AdversarialLoss")
+        sums = self._handle(ref.device).losses(real, fake).sum(0)
+        return {name: sums[i] for i, name in enumerate(loss_columns("disc"))}
+
+
+class AdversarialLoss(nn.Module):
+    """GAN-based adversarial loss (least squares), values only."""
+
+    def __init__(self):
+        super().__init__()
+        self.discriminator = MultiScaleDiscriminator()
+
+    def _mse(self, c: Dict[str, Tensor], col: str) -> Tensor:
+        n = len(self.discriminator.scales)
+        return sum(c[f"s{s}_{col}"] / c[f"s{s}_logits"] for s in range(n))
+
+    def _generator(self, c) -> Tensor:
+        return self._mse(c, "fake_err_sq") / len(self.discriminator.scales)
+
+    def _feature_matching(self, c) -> Tensor:
+        n, layers = len(self.discriminator.scales), 6  # len(real_features) * len(real_features[0])
+        total = sum(c[f"s{s}_l{j}_abs_diff"] / c[f"s{s}_l{j}_count"] for s in range(n) for j in range(layers))
+        return total / (n * layers)
+
+    def discriminator_loss(self, real_audio, fake_audio):
+        with torch.no_grad():
+            c = self.discriminator._sums(real_audio, fake_audio)
+            return ((self._mse(c, "real_err_sq") + self._mse(c, "fake_sq")) / len(self.discriminator.scales)).float()
+
+    def generator_loss(self, fake_audio):
+        with torch.no_grad():
+            return self._generator(self.discriminator._sums(None, fake_audio)).float()
+
+    def feature_matching_loss(self, real_audio, fake_audio):
+        with torch.no_grad():
+            return self._feature_matching(self.discriminator._sums(real_audio, fake_audio)).float()
+
+
+class PerceptualLoss(nn.Module):
+    """Perceptual loss on the reference's "mel" features: its filter rows are
+    constant (row j holds w_j in every bin, w_0 = 0), so a feature is
+    ln(w_j sum_f |X| + 1e-8) of a frame's magnitude sum."""
+
+    _WEIGHTS: Dict[Tuple, Tensor] = {}
+
+    def __init__(self, model_type="mel"):
+        super().__init__()
+        self.model_type = model_type
+        self.feature_extractor = self._mel_features
+
+    @classmethod
+    def mel_weights(cls, device, freq_bins: int = 513, n_mels: int = 80) -> Tensor:
+        """The filter rows' values, by the reference's float32 expressions."""
+        key = (torch.device(device), freq_bins, n_mels)
+        w = cls._WEIGHTS.get(key)
+        if w is None:
+            f = torch.linspace(0, 1, n_mels, dtype=torch.float32).unsqueeze(1).expand(n_mels, freq_bins)
+            f = f / (f.sum(dim=1, keepdim=True) + 1e-8)
+            w = cls._WEIGHTS[key] = f[:, 0].contiguous().to(device)
+        return w
+
+    def _mel_features(self, audio, n_mels=80):
+        """ln(mel + 1e-8) [B, n_mels, T] of audio [B, 1, L]: torch.stft(1024, 256) magnitudes, summed per frame."""
+        _require(audio, what="PerceptualLoss")
+        from m2amd.dsp import get_dsp
+        with torch.no_grad():
+            y = audio.detach().float().reshape(audio.shape[0], -1)
+            _, spec, _ = get_dsp(SAMPLE_RATE, 1024, 256, 1024, device=y.device).loss_spectral(y, y, spectra=True)
+            mag = spec.abs().sum(dim=1, keepdim=True)
+            return torch.log(self.mel_weights(y.device, 513, n_mels).view(1, -1, 1) * mag + 1e-8)
+
+    def _value(self, p: Tensor, t: Tensor, cache: Optional[dict]) -> Tensor:
+        r = _spectral_rows(p, t, 1024, 256, cache)
+        return r["mel_log_abs"] / (r["frames"] * 80)
+
+    def forward(self, pred_audio, target_audio):
+        with torch.no_grad():
+            p, t = _audio_pair(pred_audio, target_audio, "PerceptualLoss")
+            return self._value(p, t, None).float()
+
+
+class CombinedTTSLoss(nn.Module):
+    """Combined loss of stage 2 TTS training, values only (see the module docstring)."""
+
+    def __init__(
+        self,
+        mel_loss_weight: float = 1.0,
+        duration_loss_weight: float = 0.1,
+        adversarial_loss_weight: float = 0.25,
+        feature_matching_weight: float = 2.0,
+        spectral_loss_weight: float = 1.0,
+        perceptual_loss_weight: float = 0.5,
+        use_discriminator: bool = True
+    ):
+        super().__init__()
+        self.mel_loss_weight = mel_loss_weight
+        self.duration_loss_weight = duration_loss_weight
+        self.adversarial_loss_weight = adversarial_loss_weight
+        self.feature_matching_weight = feature_matching_weight
+        self.spectral_loss_weight = spectral_loss_weight
+        self.perceptual_loss_weight = perceptual_loss_weight
+
+        self.spectral_loss = SpectralLoss()
+        self.perceptual_loss = PerceptualLoss()
+        if use_discriminator:
+            self.adversarial_loss = AdversarialLoss()
+        else:
+            self.adversarial_loss = None
+        self.training_step = 0
+
+    @staticmethod
+    def _mel_loss(mel_pred: Tensor, mel_target: Tensor, mel_lengths) -> Tensor:
+        """mel_pred [B, Tp, M] against mel_target [B, M, Tt]: with lengths the mean over
+        utterances of the L1 mean of the first min(len, Tp, Tt) frames; else the L1 mean."""
+        from m2amd.dsp import eval_columns, pair_stats
+        if mel_pred.dim() != 3 or mel_target.dim() != 3 or mel_pred.shape[0] != mel_target.shape[0] or \
+                mel_pred.shape[2] != mel_target.shape[1]:
+            raise RuntimeError(f"CombinedTTSLoss: mel_pred {tuple(mel_pred.shape)} must be [B, T, M] for mel_target "
+                               f"{tuple(mel_target.shape)} [B, M, T]")
+        Tp, Tt = mel_pred.shape[1], mel_target.shape[2]
+        cols = None
+        if mel_lengths is not None:
+            T = min(Tp, Tt)
+            mel_pred, mel_target = mel_pred[:, :T], mel_target[:, :, :T]
+            cols = torch.as_tensor(mel_lengths).to(mel_pred.device).reshape(-1).clamp(min=0, max=T).to(torch.int32)
+        elif Tp != Tt:
+            raise RuntimeError(f"CombinedTTSLoss: {Tp} predicted and {Tt} target frames, and no mel_lengths")
+        rows = pair_stats(mel_pred.detach(), mel_target.detach(), transposed=True, cols=cols)
+        names = eval_columns("pair")
+        s, n = rows[:, names.index("abs_diff")], rows[:, names.index("count")]
+        return (s / n).mean() if cols is not None else s.sum() / n.sum()
+
+    @staticmethod
+    def _duration_loss(pred: Tensor, target: Tensor) -> Tensor:
+        from m2amd.dsp import eval_columns, pair_stats
+        p, t = torch.broadcast_tensors(pred.detach().float(), target.detach().float().to(pred.device))
+        rows = pair_stats(p.reshape(1, 1, -1), t.reshape(1, 1, -1))
+        names = eval_columns("pair")
+        return rows[0, names.index("sq_diff")] / rows[0, names.index("count")]
+
+    def forward(
+        self,
+        mel_pred: torch.Tensor,
+        mel_target: torch.Tensor,
+        duration_pred: torch.Tensor,
+        duration_target: torch.Tensor,
+        audio_pred: Optional[torch.Tensor] = None,
+        audio_target: Optional[torch.Tensor] = None,
+        mel_lengths: Optional[torch.Tensor] = None,
+        optimize_discriminator: bool = False
+    ) -> Dict[str, torch.Tensor]:
+        """
+        Args:
+            mel_pred: predicted mel spectrogram [batch, time, mel_dim]
+            mel_target: target mel spectrogram [batch, mel_dim, time]
+            duration_pred, duration_target: durations [batch, text_len]
+            audio_pred, audio_target: waveforms [batch, 1, audio_len]
+            mel_lengths: actual mel lengths [batch]
+            optimize_discriminator: compute the discriminator loss instead of the generator's
+
+        Returns:
+            the loss components by name, 0-dim float32 tensors without a graph
+        """
+        _require(mel_pred, mel_target, duration_pred, duration_target, audio_pred, audio_target,
+                 what="CombinedTTSLoss")
+        with torch.no_grad():
+            v: Dict[str, Tensor] = {}  # float64 on the device
+            v["mel_loss"] = self._mel_loss(mel_pred, mel_target, mel_lengths)
+            v["duration_loss"] = self._duration_loss(duration_pred, duration_target)
+            if audio_pred is not None and audio_target is not None:
+                p, t = _audio_pair(audio_pred, audio_target, "CombinedTTSLoss")
+                cache: dict = {}
+                v["spectral_loss"] = self.spectral_loss._value(p, t, cache)
+                v["perceptual_loss"] = self.perceptual_loss._value(p, t, cache)
+                if self.adversarial_loss is not None:
+                    adv = self.adversarial_loss
+                    real, fake = t.unsqueeze(1), p.unsqueeze(1)
+                    if optimize_discriminator:
+                        c = adv.discriminator._sums(real, fake)
+                        v["discriminator_loss"] = (adv._mse(c, "real_err_sq") + adv._mse(c, "fake_sq")) / \
+                            len(adv.discriminator.scales)
+                    else:
+                        # one pass over each signal serves both terms (the reference runs fake twice)
+                        c = adv.discriminator._sums(real, fake)
+                        v["generator_loss"] = adv._generator(c)
+                        v["feature_matching_loss"] = adv._feature_matching(c)
+
+            if optimize_discriminator and "discriminator_loss" in v:
+                total = v["discriminator_loss"]
+            else:
+                total = self.mel_loss_weight * v["mel_loss"] + self.duration_loss_weight * v["duration_loss"]
+                for name, weight in (("spectral_loss", self.spectral_loss_weight),
+                                     ("perceptual_loss", self.perceptual_loss_weight),
+                                     ("generator_loss", self.adversarial_loss_weight),
+                                     ("feature_matching_loss", self.feature_matching_weight)):
+                    if name in v:
+                        total = total + weight * v[name]
+            v["total_loss"] = total
+            losses = {k: x.float() for k, x in v.items()}
+        self.training_step += 1
+        return losses
+
+    def get_discriminator_parameters(self):
+        """Discriminator parameters, for a separate optimizer."""
+        if self.adversarial_loss is not None:
+            return self.adversarial_loss.discriminator.parameters()
+        return []
+
+
+class EarlyStopping:
+    """Early stopping utility for training (host Python)."""
+
+    def __init__(self, patience: int = 10000, min_delta: float = 0.001):
+        self.patience = patience
+        self.min_delta = min_delta
+        self.best_loss = float('inf')
+        self.wait = 0
+
+    def __call__(self, val_loss: float) -> bool:
+        """True if training should stop: ``patience`` calls in a row without an
+        improvement of more than ``min_delta`` on the best loss."""
+        if val_loss < self.best_loss - self.min_delta:
+            self.best_loss = val_loss
+            self.wait = 0
+        else:
+            self.wait += 1
+        return self.wait >= self.patience

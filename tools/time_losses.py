@@ -1,0 +1,84 @@
+#!/usr/bin/env python3
+"""Time the training losses on the GPU with HIP events.
+
+    python tools/time_losses.py [--batch 32] [--length 32000] [--frames 500] [--mels 64] [--phonemes 100]
+
+Prints one JSON line: milliseconds per CombinedTTSLoss call in generator and in
+discriminator mode, per spectral / discriminator part, and for the two heaviest
+packed layers of scale 1 (the grouped 64 -> 128 k = 41 stride-4 layer and the
+dense 1024 -> 1024 k = 5 layer) their time and FLOP/time as a fraction of the
+fp32 MFMA peak (157.3 TFLOP/s).  Each figure is the median of --iters timed
+calls after --warmup untimed ones.
+"""
+import argparse
+import json
+import statistics
+import sys
+from pathlib import Path
+
+import torch
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT / "m2-tts_amd" / "src"))
+
+PEAK_F32_MFMA = 157.3e12
+
+
+def timed(fn, warmup, iters):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(iters):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    return statistics.median(ms)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--length", type=int, default=32000)
+    ap.add_argument("--frames", type=int, default=500)
+    ap.add_argument("--mels", type=int, default=64)
+    ap.add_argument("--phonemes", type=int, default=100)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--iters", type=int, default=10)
+    args = ap.parse_args()
+
+    from training.losses import CombinedTTSLoss
+    dev = torch.device("cuda", 0)
+    torch.manual_seed(0)
+    loss = CombinedTTSLoss().eval().to(dev)
+    B, L, T, M, S = args.batch, args.length, args.frames, args.mels, args.phonemes
+    kw = dict(mel_pred=torch.randn(B, T, M, device=dev), mel_target=torch.randn(B, M, T, device=dev),
+              duration_pred=torch.rand(B, S, device=dev) + 0.5, duration_target=torch.rand(B, S, device=dev) + 0.5,
+              audio_target=torch.tanh(torch.randn(B, 1, L, device=dev)),
+              mel_lengths=torch.full((B,), T, device=dev))
+    kw["audio_pred"] = torch.tanh(torch.atanh(kw["audio_target"] * 0.999) + 0.1 * torch.randn(B, 1, L, device=dev))
+    out = {"batch": B, "length": L, "frames": T, "mels": M, "phonemes": S, "iters": args.iters}
+    out["generator_ms"] = timed(lambda: loss(**kw, optimize_discriminator=False), args.warmup, args.iters)
+    out["discriminator_ms"] = timed(lambda: loss(**kw, optimize_discriminator=True), args.warmup, args.iters)
+    out["spectral_and_perceptual_ms"] = timed(
+        lambda: (loss.spectral_loss(kw["audio_pred"], kw["audio_target"]),
+                 loss.perceptual_loss(kw["audio_pred"], kw["audio_target"])), args.warmup, args.iters)
+    disc = loss.adversarial_loss.discriminator
+    out["discriminator_sums_ms"] = timed(lambda: disc._sums(kw["audio_target"], kw["audio_pred"]), args.warmup,
+                                         args.iters)
+    h = disc._handle(dev)
+    shapes = h.shapes(L)[0]
+    for name, layer in (("grouped_64_128_k41", 1), ("dense_1024_1024_k5", 5)):
+        cin, cout, k, _, _, groups = h.LAYER_TABLE[layer]
+        x = torch.randn(B, cin, shapes[layer - 1][1], device=dev)
+        ms = timed(lambda: h.layer(0, layer, x), args.warmup, args.iters)
+        flop = 2.0 * cout * (cin // groups) * k * shapes[layer][1] * B
+        out[name] = {"ms": ms, "gflop": flop / 1e9, "fraction_of_f32_mfma_peak": flop / (ms * 1e-3) / PEAK_F32_MFMA}
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
