@@ -429,15 +429,12 @@ __device__ __forceinline__ int row_bound(const int32_t* __restrict__ rows, int b
 }
 
 // ---------------------------------------------------------------------------
-// The attention kit: what attention_tile, attention_qsplit2 and
-// attention_quarters below share, each piece written once.  A block is 16
+// The attention kit: what attention_tile, attention_qsplit, attention_qsplit2
+// and attention_quarters below share, each piece written once.  A block is 16
 // queries (or 16 keys), a chunk 32 keys (two key blocks u = 0, 1); a chunk's
 // scores of one query block are s[u][r]: key k0 + 16 u + 4 g + r of query li
 // (lane = 16 g + li), base 2.  The bodies differ in their wave mapping, their
 // loop schedule, their choice of the rules below and their merge.
-// (attention_qsplit still spells the same steps out by hand: rebuilt on the
-// kit it returned NaN at head_dim 16, bit-equal at 32 and 48, cause not found;
-// tests/test_gpu_tf_layer.py::test_head_dim_16_on_64_row_tiles pins it.)
 template <int V>
 struct CI {  // a compile-time index passed by value
     static constexpr int value = V;
@@ -914,10 +911,11 @@ __device__ __forceinline__ void attention_tile(const unsigned char* __restrict__
 // per 16 or 32 queries and is bound by the CU's L2 read rate (~37 B/clk,
 // tools/probe/l2bw.hip); this one reads it once per 64 queries and then from
 // LDS.  Per 64 keys: the QK^T MFMAs of both chunks (four independent
-// accumulators), one softmax update, the PV MFMAs; two LDS buffers and one
-// register set - keys 64 (p + 2) are in flight from L2 while p is computed and
-// p + 1 goes to LDS; one barrier per 64 keys.  Leaves the normalised rows in A
-// (split, stride srs(H)); `ring` is 2 * 2 chunks.
+// accumulators), one softmax update, the PV MFMAs.  The staging is KvStage
+// below, shared with attention_qsplit2: two LDS buffers and one register set -
+// keys 64 (p + 2) are in flight from L2 while p is computed and p + 1 goes to
+// LDS; one barrier per 64 keys.  Leaves the normalised rows in A (split,
+// stride srs(H)); `ring` is 2 * 2 chunks.
 template <int HD>
 struct QsGeo {
     using G = Geo<HD>;
@@ -940,291 +938,155 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t wave_rsrc(const unsigned char*
     return __builtin_amdgcn_make_buffer_rsrc(p, 0, 0x7ffffff0, 0x00020000);
 }
 
-// LEAN (M2_TFL_QS2=4): the lean softmax of attention_qsplit2 (C = -m
-// accumulators when unmasked, row sums by MFMA on an all-ones fragment).
+// The K / V^T staging of the query-split bodies: the workgroup's 512 threads
+// move both heads' fragments of one 64-key step from L2 to one of the ring's
+// two LDS buffers, PPT 16-B pieces per thread.  Piece i of step 0 is
+// [chunk][head][K blocks | V^T chunk], read through a buffer descriptor of its
+// region (a wave's 1-KB piece lies in one K or V^T region: the region bytes
+// are multiples of 1 KB), so a step's loads take the per-lane offset from a
+// fixed VGPR and the step's advance from an SGPR - no 64-bit address
+// arithmetic per step.
+template <int HD>
+struct KvStage {
+    using G = Geo<HD>;
+    using Q = QsGeo<HD>;
+    static constexpr int PPT = Q::PPT;
+    __amdgpu_buffer_rsrc_t rsrc[PPT];
+    int sstep[PPT];  // bytes from one 64-key step to the next for that piece
+    u32x4 pre[PPT];  // the step on its way from L2 to LDS
+    unsigned char* ring;
+
+    __device__ __forceinline__ KvStage(const unsigned char* __restrict__ kb, const unsigned char* __restrict__ vb, int b,
+                                       int npad, unsigned char* ring_)
+        : ring(ring_) {
+        const int nch = npad / KC;
+#pragma unroll
+        for (int i = 0; i < PPT; ++i) {
+            const int o = 16 * ((int)threadIdx.x + NW * 64 * i), j = o / Q::CB, oc = o - j * Q::CB, hh = oc / Q::HB,
+                      r = oc - hh * Q::HB;
+            const size_t bh = (size_t)b * HEADS + hh;
+            const bool isk = r < Q::KB;
+            const unsigned char* base = isk ? kb + (bh * (npad / 16) + 2 * j) * G::QKBLK + (r & ~1023)
+                                            : vb + (bh * nch + j) * G::VCH + ((r - Q::KB) & ~1023);
+            rsrc[i] = wave_rsrc(base);
+            sstep[i] = __builtin_amdgcn_readfirstlane(isk ? 4 * G::QKBLK : 2 * G::VCH);
+        }
+    }
+    __device__ __forceinline__ void gload(int p) {
+#pragma unroll
+        for (int i = 0; i < PPT; ++i)
+            pre[i] = __builtin_bit_cast(
+                u32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc[i], 16 * ((int)threadIdx.x & 63), p * sstep[i], 0));
+    }
+    __device__ __forceinline__ void lstore(int buf) {
+#pragma unroll
+        for (int i = 0; i < PPT; ++i)
+            *reinterpret_cast<u32x4*>(ring + buf * Q::SB + 16 * ((int)threadIdx.x + NW * 64 * i)) = pre[i];
+    }
+    // process(buffer, p) for the nsc 64-key steps: step p from buffer p & 1
+    // while p + 1 goes to the other buffer and p + 2 is requested, one barrier
+    // per step.  A step's staging is issued before its K fragment reads: after
+    // them it measured +4.5 % on the decoder layers at B=128 T=2600
+    // (profiles/r04/r04i_stage_order.txt).
+    template <typename Process>
+    __device__ __forceinline__ void run(int nsc, Process process) {
+        gload(0);
+        lstore(0);
+        if (1 < nsc) gload(1);
+        lds_barrier();
+#pragma unroll 1
+        for (int p = 0; p < nsc; ++p) {
+            if (p + 1 < nsc) lstore((p + 1) & 1);
+            if (p + 2 < nsc) gload(p + 2);
+            process(ring + (p & 1) * Q::SB, p);
+            lds_barrier();
+        }
+    }
+};
+
+// LEAN (M2_TFL_QS2=4, unmasked only): the lean softmax of attention_qsplit2
+// (C = -m accumulators, row sums by MFMA on an all-ones fragment), the two
+// score sets of lean_step being the two chunks of the block's 64-key step.
 template <int H, int HD, bool MASKED, bool LEAN = false>
 __device__ __forceinline__ void attention_qsplit(const unsigned char* __restrict__ qb, const unsigned char* __restrict__ kb,
                                                  const unsigned char* __restrict__ vb, int b, int t0, int N, int npad,
                                                  int len, float sl2, unsigned char* A, unsigned char* ring) {
+    static_assert(!(LEAN && MASKED), "the lean one-block form is unmasked");
     using G = Geo<HD>;
     using Q = QsGeo<HD>;
-    constexpr int KS = G::KS, KSA = G::KSA, KT = G::KT, MT = G::MT, QKBLK = G::QKBLK, CB = Q::CB, SB = Q::SB;
-    constexpr int PPT = Q::PPT;
+    constexpr int MT = G::MT, QKBLK = G::QKBLK, CB = Q::CB;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 15, g = lane >> 4;
     const int h = wave / WPH, qblk = wave - h * WPH;
-    const int nch = npad / KC, nsc = (N + 2 * KC - 1) / (2 * KC);  // layout chunks (even), 64-key steps
+    const int nsc = (N + 2 * KC - 1) / (2 * KC);  // 64-key steps
 
-    // B = Q^T fragments of this wave's 16 queries
-    u32x4 qh[KSA], ql[KSA], qxh, qxl;
-    {
-        const unsigned char* qp =
-            qb + ((size_t)(b * HEADS + h) * (npad / 16) + t0 / 16 + qblk) * QKBLK + 16 * lane;
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            qh[ks] = *reinterpret_cast<const u32x4*>(qp + 2048 * ks);
-            ql[ks] = *reinterpret_cast<const u32x4*>(qp + 2048 * ks + 1024);
-        }
-        if constexpr (KT) {
-            const u32x4 z = u32x4{0u, 0u, 0u, 0u};
-            qxh = lane < 32 ? *reinterpret_cast<const u32x4*>(qp + G::TAIL) : z;
-            qxl = lane < 32 ? *reinterpret_cast<const u32x4*>(qp + G::TAIL + 512) : z;
-        }
-    }
-    // the global source of piece i (16 B) of 64-key step 0: [chunk][head][K blocks | V^T chunk],
-    // through a buffer descriptor of its region (a wave's 1-KB piece lies in
-    // one K or V^T region): per-lane offset fixed, the step's advance scalar
-    __amdgpu_buffer_rsrc_t rsrc[PPT];
-    int sstep[PPT];  // bytes from one 64-key step to the next for that piece
-#pragma unroll
-    for (int i = 0; i < PPT; ++i) {
-        const int o = 16 * (tid + NW * 64 * i), j = o / CB, oc = o - j * CB, hh = oc / Q::HB, r = oc - hh * Q::HB;
-        const size_t bh = (size_t)b * HEADS + hh;
-        const bool isk = r < Q::KB;
-        const unsigned char* base = isk ? kb + (bh * (npad / 16) + 2 * j) * QKBLK + (r & ~1023)
-                                        : vb + (bh * nch + j) * G::VCH + ((r - Q::KB) & ~1023);
-        rsrc[i] = wave_rsrc(base);
-        sstep[i] = __builtin_amdgcn_readfirstlane(isk ? 4 * QKBLK : 2 * G::VCH);
-    }
-    u32x4 pre[PPT];
-    auto gload = [&](int p) {
-#pragma unroll
-        for (int i = 0; i < PPT; ++i)
-            pre[i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc[i], 16 * lane, p * sstep[i], 0));
-    };
-    auto lstore = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < PPT; ++i) *reinterpret_cast<u32x4*>(ring + buf * SB + 16 * (tid + NW * 64 * i)) = pre[i];
-    };
+    QFrag<HD> qf;  // this wave's 16 queries
+    qf.load(qb + ((size_t)(b * HEADS + h) * (npad / 16) + t0 / 16 + qblk) * QKBLK, lane);
+    KvStage<HD> stage(kb, vb, b, npad, ring);
 
-    f32x4 acc[MT], lacc = f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 acc[1][MT], lacc = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int t = 0; t < MT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int t = 0; t < MT; ++t) acc[0][t] = f32x4{0.f, 0.f, 0.f, 0.f};
     float m = MASKED ? -INFINITY : 0.f, lsum = 0.f;
-    bool fresh = true;
-    const u32x4 ones = u32x4{0x3C003C00u, 0x3C003C00u, 0x3C003C00u, 0x3C003C00u};  // f16 1.0 x 8
+    bool fresh = true;  // no step processed yet (wave-uniform)
 
     // keys 64 p + 32 j + 16 u + 4 g + r, j = chunk of the step, u = 16-key block
-    auto process = [&](const unsigned char* sb, int p) {
+    stage.run(nsc, [&](const unsigned char* sb, int p) {
         float s[2][2][4];
+        const float c0 = (LEAN && !fresh) ? -m : 0.f;  // lean: scores relative to the base
 #pragma unroll
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
-                const unsigned char* kp = sb + j * CB + h * Q::HB + u * QKBLK + 16 * lane;
-                const float c0 = (LEAN && !MASKED && !fresh) ? -m : 0.f;
-                f32x4 st = f32x4{c0, c0, c0, c0};
+                KFrag<HD> k;
+                k.load_lds(sb + j * CB + h * Q::HB + u * QKBLK, lane);
+                f32x4 st[1] = {f32x4{c0, c0, c0, c0}};
+                qk_block<HD, 1>(k, &qf, st);
 #pragma unroll
-                for (int ks = 0; ks < KS; ++ks) {
-                    const u32x4 kh = *reinterpret_cast<const u32x4*>(kp + 2048 * ks);
-                    const u32x4 kl = *reinterpret_cast<const u32x4*>(kp + 2048 * ks + 1024);
-                    st = mfma(kh, qh[ks], st);
-                    st = mfma(kh, ql[ks], st);
-                    st = mfma(kl, qh[ks], st);
-                }
-                if constexpr (KT) {  // lanes of groups 2, 3 read other tail bytes: their Q operand is zero
-                    const u32x4 kxh = *reinterpret_cast<const u32x4*>(kp + G::TAIL);
-                    const u32x4 kxl = *reinterpret_cast<const u32x4*>(kp + G::TAIL + 512 - 512 * (lane >> 5));
-                    st = mfma(kxh, qxh, st);
-                    st = mfma(kxh, qxl, st);
-                    st = mfma(kxl, qxh, st);
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r) s[j][u][r] = st[r];
+                for (int r = 0; r < 4; ++r) s[j][u][r] = st[0][r];
             }
         const int k0 = p * 2 * KC;
         if constexpr (MASKED) {
 #pragma unroll
-            for (int j = 0; j < 2; ++j)
+            for (int j = 0; j < 2; ++j) mask_scores(s[j], k0 + KC * j, g, len, N, sl2);
+        } else if (N - k0 < 2 * KC) {  // the last step (wave-uniform)
 #pragma unroll
-                for (int u = 0; u < 2; ++u)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int key = k0 + 32 * j + 16 * u + 4 * g + r;
-                        s[j][u][r] = key < len ? s[j][u][r] * sl2 : (key < N ? kMaskFill * kLog2e : -INFINITY);
-                    }
-        } else if (N - k0 < 2 * KC) {  // the last step: keys past N score -inf (wave-uniform)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int u = 0; u < 2; ++u)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        s[j][u][r] = k0 + 32 * j + 16 * u + 4 * g + r < N ? s[j][u][r] : -INFINITY;
+            for (int j = 0; j < 2; ++j) clip_scores(s[j], k0 + KC * j, g, N);
         }
-        auto step_max = [&]() {
-            float c = s[0][0][0];
+        // finite: the step's first chunk has a live key
+        auto step_max = [&]() { return fmaxf(max8(s[0]), max8(s[1])); };
+        u32x4 bh4[2], bl4[2];
+        if constexpr (LEAN) {
+            lean_step(s, fresh, bh4, bl4, [&](bool first) {
+                const float d = lean_base<false>(first, step_max(), m, lacc, acc[0], [&](float v) { m = v; });
 #pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int u = 0; u < 2; ++u)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) c = fmaxf(c, s[j][u][r]);
-            return c;
-        };
-        if constexpr (LEAN && !MASKED) {
-            // as attention_qsplit2's lean form: the base from the first step's
-            // maximum, later moves detected on the f16 hi halves of P
-            if (fresh) {  // wave-uniform
-                const float cm = grp4_max(step_max());  // finite: the step's first chunk has a live key
-                m = cm;
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int u = 0; u < 2; ++u)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) s[j][u][r] -= cm;
-                fresh = false;
-            }
-            u32x4 bh4[2], bl4[2];
-            auto exp_split = [&]() {
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    float e[2][4];
-#pragma unroll
-                    for (int u = 0; u < 2; ++u)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) e[u][r] = __builtin_amdgcn_exp2f(s[j][u][r]);
-                    unsigned ph[4], pl[4];
-                    split2u(e[0][0], e[0][1], ph[0], pl[0]);
-                    split2u(e[0][2], e[0][3], ph[1], pl[1]);
-                    split2u(e[1][0], e[1][1], ph[2], pl[2]);
-                    split2u(e[1][2], e[1][3], ph[3], pl[3]);
-                    bh4[j] = u32x4{ph[0], ph[1], ph[2], ph[3]};
-                    bl4[j] = u32x4{pl[0], pl[1], pl[2], pl[3]};
-                }
-            };
-            exp_split();
-            if (__builtin_amdgcn_ballot_w64(p_hi_exceeds(bh4[0], bh4[1])) != 0) {  // wave-uniform: move the base
-                const float d = vmax(grp4_max(step_max()), 0.f);
-                m += d;
-                const float corr = __builtin_amdgcn_exp2f(-d);
-                lacc *= corr;
-#pragma unroll
-                for (int t = 0; t < MT; ++t) acc[t] *= corr;
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int u = 0; u < 2; ++u)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) s[j][u][r] -= d;
-                exp_split();
-            }
+                for (int j = 0; j < 2; ++j) sub_scores(s[j], d);
+            });
+        } else {
+            const float cmax = step_max();
+            if constexpr (MASKED) masked_base(cmax, m, lsum, acc[0]);
+            else if (__builtin_amdgcn_ballot_w64(fresh || cmax - m > kLazyT) != 0)  // wave-uniform: move the base
+                lazy_base_abs(fresh, cmax, m, lsum, acc[0]);
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-                lacc = mfma(ones, bh4[j], lacc);
-                lacc = mfma(ones, bl4[j], lacc);
-                const unsigned char* vp = sb + j * CB + h * Q::HB + Q::KB + 16 * lane;
-#pragma unroll
-                for (int t = 0; t < MT; ++t) {
-                    const u32x4 vh = *reinterpret_cast<const u32x4*>(vp + t * 2048);
-                    const u32x4 vl = *reinterpret_cast<const u32x4*>(vp + t * 2048 + 1024);
-                    acc[t] = mfma(vh, bh4[j], acc[t]);
-                    acc[t] = mfma(vh, bl4[j], acc[t]);
-                    acc[t] = mfma(vl, bh4[j], acc[t]);
-                }
+                sub_scores(s[j], m);
+                exp_scores(s[j], lsum);
+                p_fragments(s[j], bh4[j], bl4[j]);
             }
-            return;
         }
-        const float cmax = step_max();
-        if constexpr (MASKED) {
-            const float mn = vmax(m, grp4_max(cmax));
-            const float corr = __builtin_amdgcn_exp2f(m - mn);
-            lsum *= corr;
-            if constexpr (LEAN) lacc *= corr;
-#pragma unroll
-            for (int t = 0; t < MT; ++t) acc[t] *= corr;
-            m = mn;
-        } else if constexpr (LEAN) {
-            // scores relative to the base already (attention_qsplit2's LEAN form)
-            if (__builtin_amdgcn_ballot_w64(fresh || cmax > kLazyT) != 0) {
-                const float cm = grp4_max(cmax);  // finite: the step's first chunk has a live key
-                const float d = fresh ? cm : vmax(cm, 0.f);
-                m += d;
-                if (!fresh) {
-                    const float corr = __builtin_amdgcn_exp2f(-d);
-                    lacc *= corr;
-#pragma unroll
-                    for (int t = 0; t < MT; ++t) acc[t] *= corr;
-                }
-#pragma unroll
-                for (int jj = 0; jj < 2; ++jj)
-#pragma unroll
-                    for (int u = 0; u < 2; ++u)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) s[jj][u][r] -= d;
-            }
-            fresh = false;
-        } else {
-            // lazy base (attention_split_kernel): move it only on the first step or
-            // when a score exceeds it by more than 2^kLazyT (wave-uniform)
-            const float rel = cmax - m;
-            if (__builtin_amdgcn_ballot_w64(fresh || rel > kLazyT) != 0) {
-                const float cm = grp4_max(cmax);  // finite: the step's first chunk has a live key
-                const float mn = fresh ? cm : vmax(cm, m);
-                if (!fresh) {
-                    const float corr = __builtin_amdgcn_exp2f(m - mn);
-                    lsum *= corr;
-#pragma unroll
-                    for (int t = 0; t < MT; ++t) acc[t] *= corr;
-                }
-                m = mn;
-            }
-            fresh = false;
-        }
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int u = 0; u < 2; ++u)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    if constexpr (LEAN && !MASKED) {
-                        s[j][u][r] = __builtin_amdgcn_exp2f(s[j][u][r]);
-                    } else {
-                        s[j][u][r] = __builtin_amdgcn_exp2f(s[j][u][r] - m);
-                        if constexpr (!LEAN) lsum += s[j][u][r];
-                    }
-                }
+        fresh = false;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            unsigned ph[4], pl[4];
-            split2u(s[j][0][0], s[j][0][1], ph[0], pl[0]);
-            split2u(s[j][0][2], s[j][0][3], ph[1], pl[1]);
-            split2u(s[j][1][0], s[j][1][1], ph[2], pl[2]);
-            split2u(s[j][1][2], s[j][1][3], ph[3], pl[3]);
-            const u32x4 bh4 = u32x4{ph[0], ph[1], ph[2], ph[3]}, bl4 = u32x4{pl[0], pl[1], pl[2], pl[3]};
-            if constexpr (LEAN) {
-                lacc = mfma(ones, bh4, lacc);
-                lacc = mfma(ones, bl4, lacc);
-            }
-            const unsigned char* vp = sb + j * CB + h * Q::HB + Q::KB + 16 * lane;
-#pragma unroll
-            for (int t = 0; t < MT; ++t) {
-                const u32x4 vh = *reinterpret_cast<const u32x4*>(vp + t * 2048);
-                const u32x4 vl = *reinterpret_cast<const u32x4*>(vp + t * 2048 + 1024);
-                acc[t] = mfma(vh, bh4, acc[t]);
-                acc[t] = mfma(vh, bl4, acc[t]);
-                acc[t] = mfma(vl, bh4, acc[t]);
-            }
+            if constexpr (LEAN) ones_sum(bh4[j], bl4[j], lacc);
+            VFrag<MT> v;
+            v.load_lds(sb + j * CB + h * Q::HB + Q::KB, lane);
+            pv_block<MT, 1>(v, &bh4[j], &bl4[j], acc);
         }
-    };
-
-    gload(0);
-    lstore(0);
-    if (1 < nsc) gload(1);
-    lds_barrier();
+    });
     // (Head 0's waves at a higher issue priority than the head-1 wave of the
     // same query block on their SIMD, so that one wave's MFMA phase could fall
     // on the other's softmax phase: no change at B=64 T=500, B=16 T=2600 or
     // stage1 B=32, in-process A/B, profiles/r03/ab/r03x_ab.txt.)
-#pragma unroll 1
-    for (int p = 0; p < nsc; ++p) {
-        // step p from buffer p & 1; p + 1 goes to the other buffer, p + 2 is requested
-        if (p + 1 < nsc) lstore((p + 1) & 1);
-        if (p + 2 < nsc) gload(p + 2);
-        process(ring + (p & 1) * SB, p);
-        lds_barrier();
-    }
     TSTAMP(1);
     if constexpr (LEAN) {
         lsum = lacc[0];  // complete over the keys already
@@ -1235,12 +1097,12 @@ __device__ __forceinline__ void attention_qsplit(const unsigned char* __restrict
     const float inv = 1.0f / lsum;
 #pragma unroll
     for (int t = 0; t < MT; ++t)
-        put_split4<H>(A + (16 * qblk + li) * srs(H) + 2 * (h * HD + 16 * t + 4 * g), acc[t][0] * inv, acc[t][1] * inv,
-                      acc[t][2] * inv, acc[t][3] * inv);
+        put_split4<H>(A + (16 * qblk + li) * srs(H) + 2 * (h * HD + 16 * t + 4 * g), acc[0][t][0] * inv,
+                      acc[0][t][1] * inv, acc[0][t][2] * inv, acc[0][t][3] * inv);
 }
 
-// The same 64-row tile with each wave on TWO 16-query blocks and ONE 32-key
-// chunk of every 64-key step: wave w = (head w / 4, query pair (w / 2) % 2,
+// The same 64-row tile and the same staging (KvStage) with each wave on TWO
+// 16-query blocks and ONE 32-key chunk of every 64-key step: wave w = (head w / 4, query pair (w / 2) % 2,
 // chunk w % 2).  Every K / V^T fragment a wave reads from LDS then feeds the
 // MFMAs of both query blocks, so the workgroup reads half the LDS bytes per
 // step of attention_qsplit (8 waves x one chunk instead of 8 waves x both
@@ -1262,7 +1124,7 @@ __device__ __forceinline__ void attention_qsplit2(const unsigned char* __restric
                                                   int len, float sl2, unsigned char* A, unsigned char* ring) {
     using G = Geo<HD>;
     using Q = QsGeo<HD>;
-    constexpr int MT = G::MT, QKBLK = G::QKBLK, CB = Q::CB, SB = Q::SB, PPT = Q::PPT;
+    constexpr int MT = G::MT, QKBLK = G::QKBLK, CB = Q::CB, SB = Q::SB;
     constexpr int RW = 2 + 4 * MT;  // merge record floats per lane
     static_assert(NW * RW * 64 * 4 <= 2 * SB, "merge records fit the ring");
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1274,34 +1136,7 @@ __device__ __forceinline__ void attention_qsplit2(const unsigned char* __restric
 #pragma unroll
     for (int qq = 0; qq < 2; ++qq)
         qf[qq].load(qb + ((size_t)(b * HEADS + h) * (npad / 16) + t0 / 16 + 2 * qp + qq) * QKBLK, lane);
-    // the global source of piece i (16 B) of 64-key step 0: [chunk][head][K blocks | V^T chunk],
-    // through a buffer descriptor of its region (a wave's 1-KB piece lies in
-    // one K or V^T region: the region bytes are multiples of 1 KB), so a
-    // step's loads take the per-lane offset from a fixed VGPR and the step's
-    // advance from an SGPR - no 64-bit address arithmetic per step
-    const int nch = npad / KC;
-    __amdgpu_buffer_rsrc_t rsrc[PPT];
-    int sstep[PPT];  // bytes from one 64-key step to the next for that piece
-#pragma unroll
-    for (int i = 0; i < PPT; ++i) {
-        const int o = 16 * (tid + NW * 64 * i), jj = o / CB, oc = o - jj * CB, hh = oc / Q::HB, r = oc - hh * Q::HB;
-        const size_t bh = (size_t)b * HEADS + hh;
-        const bool isk = r < Q::KB;
-        const unsigned char* base = isk ? kb + (bh * (npad / 16) + 2 * jj) * QKBLK + (r & ~1023)
-                                        : vb + (bh * nch + jj) * G::VCH + ((r - Q::KB) & ~1023);
-        rsrc[i] = wave_rsrc(base);
-        sstep[i] = __builtin_amdgcn_readfirstlane(isk ? 4 * QKBLK : 2 * G::VCH);
-    }
-    u32x4 pre[PPT];
-    auto gload = [&](int p) {
-#pragma unroll
-        for (int i = 0; i < PPT; ++i)
-            pre[i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc[i], 16 * lane, p * sstep[i], 0));
-    };
-    auto lstore = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < PPT; ++i) *reinterpret_cast<u32x4*>(ring + buf * SB + 16 * (tid + NW * 64 * i)) = pre[i];
-    };
+    KvStage<HD> stage(kb, vb, b, npad, ring);
 
     f32x4 acc[2][MT], lacc[2];
     float m[2], lsum[2];
@@ -1316,7 +1151,7 @@ __device__ __forceinline__ void attention_qsplit2(const unsigned char* __restric
     bool fresh = true;  // no chunk processed yet (wave-uniform)
 
     // keys 64 p + 32 j + 16 u + 4 g + r of query li of block qq
-    auto process = [&](const unsigned char* sb, int p) {
+    stage.run(nsc, [&](const unsigned char* sb, int p) {
         const int k0 = p * 2 * KC + j * KC;
         if (k0 >= N) return;  // the chunk lies wholly past N (wave-uniform)
         float s[2][2][4];
@@ -1384,22 +1219,7 @@ __device__ __forceinline__ void attention_qsplit2(const unsigned char* __restric
         VFrag<MT> v;
         v.load_lds(sb + j * CB + h * Q::HB + Q::KB, lane);
         pv_block<MT, 2>(v, bh4, bl4, acc);
-    };
-    // step p from buffer p & 1 while p + 1 goes to the other buffer and p + 2
-    // is requested, one barrier per step.  A step's staging is issued before
-    // its K fragment reads: after them it measured +4.5 % on the decoder layers
-    // at B=128 T=2600 (profiles/r04/r04i_stage_order.txt).
-    gload(0);
-    lstore(0);
-    if (1 < nsc) gload(1);
-    lds_barrier();
-#pragma unroll 1
-    for (int p = 0; p < nsc; ++p) {
-        if (p + 1 < nsc) lstore((p + 1) & 1);
-        if (p + 2 < nsc) gload(p + 2);
-        process(ring + (p & 1) * SB, p);
-        lds_barrier();
-    }
+    });
     TSTAMP(1);
     if (fresh) {  // this wave saw no key
 #pragma unroll
