@@ -482,7 +482,7 @@ int32_t m2_dsp_destroy(m2_dsp* d) {
 int32_t m2_dsp_frames(const m2_dsp* d, int32_t L) { return d && L >= 0 ? frames_of(d, L) : -1; }
 
 int32_t m2_stft(const m2_dsp* d, const float* audio, int32_t B, int32_t L, void* out_spec, void* stream) {
-    M2_CHECK_ARG(d && audio && out_spec && B >= 0 && L > 0, "m2_stft: bad argument");
+    M2_CHECK_ARG(d && B >= 0 && L > 0 && (B == 0 || (audio && out_spec)), "m2_stft: bad argument");
     if (B == 0) return M2_OK;
     const int T = frames_of(d, L);
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -499,7 +499,7 @@ int32_t m2_stft(const m2_dsp* d, const float* audio, int32_t B, int32_t L, void*
 }
 
 int32_t m2_mel_spectrogram(const m2_dsp* d, const float* audio, int32_t B, int32_t L, float* out_mel, void* stream) {
-    M2_CHECK_ARG(d && audio && out_mel && B >= 0 && L > 0, "m2_mel_spectrogram: bad argument");
+    M2_CHECK_ARG(d && B >= 0 && L > 0 && (B == 0 || (audio && out_mel)), "m2_mel_spectrogram: bad argument");
     if (B == 0) return M2_OK;
     const int T = frames_of(d, L);
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -524,7 +524,8 @@ size_t m2_mel_to_magnitude_workspace_bytes(const m2_dsp* d, int32_t B, int32_t T
 
 int32_t m2_mel_to_magnitude(const m2_dsp* d, const float* mel, int32_t B, int32_t T, int32_t nnls_iters,
                             float* out_mag, void* workspace, size_t workspace_bytes, void* stream) {
-    M2_CHECK_ARG(d && mel && out_mag && B >= 0 && T >= 0 && nnls_iters >= 0, "m2_mel_to_magnitude: bad argument");
+    M2_CHECK_ARG(d && B >= 0 && T >= 0 && nnls_iters >= 0 && (B == 0 || T == 0 || (mel && out_mag)),
+                 "m2_mel_to_magnitude: bad argument");
     if (B == 0 || T == 0) return M2_OK;
     Carve c(workspace, workspace_bytes);
     float* pg = c.take<float>((size_t)B * T);
@@ -550,10 +551,10 @@ size_t m2_griffin_lim_workspace_bytes(const m2_dsp* d, int32_t B, int32_t T) {
 int32_t m2_griffin_lim(const m2_dsp* d, const float* mel, const float* mag, const void* init_angles, int32_t B,
                        int32_t T, int32_t n_iter, float momentum, int32_t nnls_iters, float* out_audio,
                        void* workspace, size_t workspace_bytes, void* stream) {
-    M2_CHECK_ARG(d && (mel || mag) && init_angles && out_audio && B >= 0 && T >= 1 && n_iter >= 0 && nnls_iters >= 0,
-                 "m2_griffin_lim: bad argument");
-    M2_CHECK_SHAPE(T >= 2, "m2_griffin_lim: need at least 2 frames");
+    M2_CHECK_ARG(d && B >= 0 && T >= 1 && n_iter >= 0 && nnls_iters >= 0, "m2_griffin_lim: bad argument");
+    M2_CHECK_SHAPE(T >= 2, "m2_griffin_lim: need at least 2 frames");  // before the pointers: T = 1 has no output
     if (B == 0) return M2_OK;
+    M2_CHECK_ARG((mel || mag) && init_angles && out_audio, "m2_griffin_lim: bad argument");
     const int N = d->n_fft, F = N / 2 + 1, Lout = d->hop * (T - 1);
     Carve c(workspace, workspace_bytes);
     float* S = c.take<float>((size_t)B * T * F);

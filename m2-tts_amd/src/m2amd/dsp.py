@@ -20,6 +20,12 @@ from .ops import require_device, stream_handle
 Tensor = torch.Tensor
 
 
+def _rows(t: Tensor, *tail: int) -> Tensor:
+    """t as [B, *tail]; B may be 0, which reshape(-1, ...) cannot infer."""
+    n = math.prod(tail)
+    return t.reshape(t.numel() // n if n else 0, *tail)
+
+
 class Dsp:
     """Tables for one (sample_rate, n_fft, hop, win_length, n_mels, fmin, fmax) on one device."""
 
@@ -46,7 +52,7 @@ class Dsp:
         require_device(audio, what="m2 dsp")
         if audio.dtype != torch.float32:
             audio = audio.float()
-        return audio.reshape(-1, audio.shape[-1]).contiguous()
+        return _rows(audio, audio.shape[-1]).contiguous()
 
     def stft(self, audio: Tensor) -> Tensor:
         """librosa.stft(center=True, pad_mode='constant', window='hann') -> complex64 [B, F, T]."""
@@ -71,7 +77,7 @@ class Dsp:
         mel in the normalised range); ``nnls_iters`` projected-gradient steps
         per frame for a block that would iterate (m2_mel_to_magnitude)."""
         require_device(mel, what="m2 mel_to_magnitude")
-        m = mel.float().reshape(-1, self.n_mels, mel.shape[-1]).contiguous()
+        m = _rows(mel.float(), self.n_mels, mel.shape[-1]).contiguous()
         B, T = m.shape[0], m.shape[2]
         out = torch.empty(B, T, self.F, device=m.device, dtype=torch.float32)
         n = int(_lib.load().m2_mel_to_magnitude_workspace_bytes(self.handle, B, T))
@@ -98,11 +104,11 @@ class Dsp:
         src = mel if mel is not None else mag
         require_device(src, what="m2 griffin_lim")
         if mel is not None:
-            m = mel.float().reshape(-1, self.n_mels, mel.shape[-1]).contiguous()
+            m = _rows(mel.float(), self.n_mels, mel.shape[-1]).contiguous()
             B, T = m.shape[0], m.shape[2]
             mg = None
         else:
-            mg = mag.float().reshape(-1, self.F, mag.shape[-1]).transpose(1, 2).contiguous()
+            mg = _rows(mag.float(), self.F, mag.shape[-1]).transpose(1, 2).contiguous()
             B, T = mg.shape[0], mg.shape[1]
             m = None
         if init_angles is None:

@@ -27,6 +27,13 @@ in /root/reference to check it against).  What it restates:
       init='random') and istft; finally / max|audio|.
   The random phase init of griffinlim is an input here (init_angles), so a
   run is reproducible and the GPU path can be checked on the same angles.
+
+The defaults round to float32 where librosa does (window, frames, filter
+product, dB): the operation's definition.  stft, istft, mel_power,
+power_to_db, compute_mel_spectrogram and griffin_lim also take
+dtype=np.float64: the same operations with nothing rounded below double, from
+the same float32 signal and float32 filter matrix - the high-precision
+reference the kernels are held to (tests/test_gpu_dsp_edges.py).
 """
 from __future__ import annotations
 
@@ -36,10 +43,22 @@ AMIN = 1e-10
 TOP_DB = 80.0
 
 
-def hann_periodic(n: int) -> np.ndarray:
+def hann_periodic(n: int, dtype=np.float32) -> np.ndarray:
     """scipy.signal.get_window('hann', n, fftbins=True)."""
     k = np.arange(n, dtype=np.float64)
-    return (0.5 - 0.5 * np.cos(2.0 * np.pi * k / n)).astype(np.float32)
+    return (0.5 - 0.5 * np.cos(2.0 * np.pi * k / n)).astype(dtype)
+
+
+def _complex_of(dtype):
+    return np.complex128 if np.dtype(dtype) == np.float64 else np.complex64
+
+
+def padded_window(n_fft: int, win_length: int, dtype=np.float32) -> np.ndarray:
+    """The periodic Hann of win_length centred in n_fft (librosa pad_center)."""
+    win = np.zeros(n_fft, dtype=dtype)
+    lpad = (n_fft - win_length) // 2
+    win[lpad:lpad + win_length] = hann_periodic(win_length, dtype)
+    return win
 
 
 def hz_to_mel(f):
@@ -75,32 +94,43 @@ def mel_filterbank(sr: int, n_fft: int, n_mels: int, fmin: float, fmax: float) -
     return w.astype(np.float32)
 
 
-def stft(y: np.ndarray, n_fft: int, hop: int, win_length: int) -> np.ndarray:
+def stft(y: np.ndarray, n_fft: int, hop: int, win_length: int, dtype=np.float32) -> np.ndarray:
     """librosa.stft(center=True, pad_mode='constant', window='hann') of a 1-D
-    float32 signal -> complex64 [n_fft//2+1, frames]."""
-    win = np.zeros(n_fft, dtype=np.float32)
-    lpad = (n_fft - win_length) // 2
-    win[lpad:lpad + win_length] = hann_periodic(win_length)
-    yp = np.pad(y.astype(np.float32), n_fft // 2, mode="constant")
+    signal -> complex [n_fft//2+1, frames].  dtype float32 (the default)
+    rounds the window, the windowed frames and the spectrum to single
+    precision where librosa does; dtype float64 is the high-precision
+    reference of the same operation: nothing is rounded below double."""
+    win = padded_window(n_fft, win_length, dtype)
+    yp = np.pad(y.astype(dtype), n_fft // 2, mode="constant")
     n_frames = 1 + (len(yp) - n_fft) // hop
     idx = np.arange(n_fft)[None, :] + hop * np.arange(n_frames)[:, None]
     frames = yp[idx] * win[None, :]
-    return np.fft.rfft(frames.astype(np.float64), axis=1).astype(np.complex64).T
+    return np.fft.rfft(frames.astype(np.float64), axis=1).astype(_complex_of(dtype)).T
 
 
-def istft(S: np.ndarray, n_fft: int, hop: int, win_length: int, length=None) -> np.ndarray:
+def window_sumsquare(n_frames: int, n_fft: int, hop: int, win_length: int, dtype=np.float32) -> np.ndarray:
+    """The overlap-added squared window over the untrimmed n_fft + hop
+    (n_frames - 1) samples (librosa.filters.window_sumsquare)."""
+    w2 = padded_window(n_fft, win_length, dtype) ** 2
+    wss = np.zeros(n_fft + hop * (n_frames - 1), dtype=dtype)
+    for t in range(n_frames):
+        wss[t * hop:t * hop + n_fft] += w2
+    return wss
+
+
+def istft(S: np.ndarray, n_fft: int, hop: int, win_length: int, length=None, dtype=np.float32) -> np.ndarray:
     """librosa.istft(center=True, window='hann'): windowed inverse frames,
     overlap-add, divided by the window's sum of squares where it exceeds
-    tiny(float32), then the n_fft // 2 centre padding trimmed."""
-    win = np.zeros(n_fft, dtype=np.float32)
-    lpad = (n_fft - win_length) // 2
-    win[lpad:lpad + win_length] = hann_periodic(win_length)
+    tiny(float32), then the n_fft // 2 centre padding trimmed.  dtype float64:
+    the same in double throughout (the threshold stays tiny(float32), a
+    constant of the operation)."""
+    win = padded_window(n_fft, win_length, dtype)
     n_frames = S.shape[1]
-    frames = np.fft.irfft(S.T.astype(np.complex128), n=n_fft, axis=1).astype(np.float32) * win[None, :]
+    frames = np.fft.irfft(S.T.astype(np.complex128), n=n_fft, axis=1).astype(dtype) * win[None, :]
     out_len = n_fft + hop * (n_frames - 1)
-    y = np.zeros(out_len, dtype=np.float32)
-    wss = np.zeros(out_len, dtype=np.float32)
-    w2 = win.astype(np.float32) ** 2
+    y = np.zeros(out_len, dtype=dtype)
+    wss = np.zeros(out_len, dtype=dtype)
+    w2 = win ** 2
     for t in range(n_frames):
         y[t * hop:t * hop + n_fft] += frames[t]
         wss[t * hop:t * hop + n_fft] += w2
@@ -114,24 +144,40 @@ def istft(S: np.ndarray, n_fft: int, hop: int, win_length: int, length=None) -> 
     return y
 
 
-def power_to_db(S: np.ndarray) -> np.ndarray:
+def power_to_db(S: np.ndarray, dtype=np.float32) -> np.ndarray:
     """librosa.power_to_db(S, ref=np.max, amin=1e-10, top_db=80)."""
-    S = np.asarray(S, dtype=np.float32)
+    S = np.asarray(S, dtype=dtype)
     ref = np.max(S)
     log_spec = 10.0 * np.log10(np.maximum(AMIN, S))
     log_spec -= 10.0 * np.log10(np.maximum(AMIN, ref))
-    return np.maximum(log_spec, log_spec.max() - TOP_DB).astype(np.float32)
+    return np.maximum(log_spec, log_spec.max() - TOP_DB).astype(dtype)
+
+
+def mel_power(audio, sample_rate=22050, n_fft=1024, hop_length=256, win_length=1024, n_mels=64, fmin=0, fmax=None,
+              dtype=np.float32) -> np.ndarray:
+    """librosa.feature.melspectrogram(power=2.0) -> [n_mels, frames]: the
+    filter matrix (float32 values at either dtype: what librosa and the
+    kernel both hold) times |STFT|^2."""
+    if fmax is None:
+        fmax = sample_rate // 2
+    S = np.abs(stft(np.asarray(audio, dtype=np.float32), n_fft, hop_length, win_length, dtype=dtype)) ** 2
+    return mel_filterbank(sample_rate, n_fft, n_mels, fmin, fmax).astype(dtype) @ S.astype(dtype)
+
+
+def normalise_db(db: np.ndarray) -> np.ndarray:
+    """audio.py:93-96: 2 (x - min) / (max - min) - 1, in db's dtype (0 / 0 =
+    NaN throughout when every element is equal, as the reference's)."""
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return (2 * (db - db.min()) / (db.max() - db.min()) - 1).astype(db.dtype)
 
 
 def compute_mel_spectrogram(audio, sample_rate=22050, n_fft=1024, hop_length=256, win_length=1024, n_mels=64,
-                            fmin=0, fmax=None) -> np.ndarray:
-    """src/utils/audio.py:45-98 -> [n_mels, frames] float32 in [-1, 1]."""
-    if fmax is None:
-        fmax = sample_rate // 2
-    S = np.abs(stft(np.asarray(audio, dtype=np.float32), n_fft, hop_length, win_length)) ** 2
-    mel = mel_filterbank(sample_rate, n_fft, n_mels, fmin, fmax) @ S.astype(np.float32)
-    db = power_to_db(mel)
-    return (2 * (db - db.min()) / (db.max() - db.min()) - 1).astype(np.float32)
+                            fmin=0, fmax=None, dtype=np.float32) -> np.ndarray:
+    """src/utils/audio.py:45-98 -> [n_mels, frames] in [-1, 1]; float32
+    rounded as librosa rounds, or with dtype float64 the same operation in
+    double from the float32 signal and the float32 filter matrix on."""
+    mel = mel_power(audio, sample_rate, n_fft, hop_length, win_length, n_mels, fmin, fmax, dtype)
+    return normalise_db(power_to_db(mel, dtype))
 
 
 MAX_MEM_BLOCK = 2 ** 8 * 2 ** 10  # librosa.util.utils.MAX_MEM_BLOCK (256 KiB)
@@ -191,19 +237,23 @@ def nnls_objective(A, X, B) -> float:
 
 
 def griffin_lim(S: np.ndarray, init_angles: np.ndarray, n_iter: int, n_fft: int, hop: int, win_length: int,
-                momentum: float = 0.99) -> np.ndarray:
+                momentum: float = 0.99, dtype=np.float32) -> np.ndarray:
     """librosa.griffinlim(S, n_iter, momentum, init='random') with the random
-    phases given as init_angles (complex unit values, S.shape)."""
-    angles = init_angles.astype(np.complex64).copy()
+    phases given as init_angles (complex unit values, S.shape).  dtype
+    float64: every transform and the phase update in double, from the given
+    (float32) magnitudes and (complex64) phases."""
+    ctype = _complex_of(dtype)
+    S = S.astype(dtype)
+    angles = init_angles.astype(ctype).copy()
     eps = np.finfo(np.float32).tiny
     rebuilt = np.zeros_like(angles)
     for _ in range(n_iter):
         tprev = rebuilt
-        inverse = istft(S * angles, n_fft, hop, win_length)
-        rebuilt = stft(inverse, n_fft, hop, win_length)
+        inverse = istft(S * angles, n_fft, hop, win_length, dtype=dtype)
+        rebuilt = stft(inverse, n_fft, hop, win_length, dtype=dtype)
         angles = rebuilt - (momentum / (1 + momentum)) * tprev
-        angles = (angles / (np.abs(angles) + eps)).astype(np.complex64)
-    return istft(S * angles, n_fft, hop, win_length)
+        angles = (angles / (np.abs(angles) + eps)).astype(ctype)
+    return istft(S * angles, n_fft, hop, win_length, dtype=dtype)
 
 
 def mel_to_audio(mel_spec, init_angles, sample_rate=22050, n_fft=1024, hop_length=256, win_length=1024, n_iter=32,

@@ -1,8 +1,15 @@
 """GPU: mel features and Griffin-Lim (reference src/utils/audio.py:45-151, SURVEY
 8f row f4) against the CPU restatement of librosa 0.10 in oracle/audio_oracle.py.
 librosa itself is not installed here, so parity with the reference's library is
-UNPINNED; these tests pin the GPU kernels to the restatement:
-  STFT                exact to fp32 rounding (relative 2e-6 of the frame energy)
+UNPINNED; these tests pin the GPU kernels to the restatement, at ONE handle
+(22050 Hz, n_fft 1024, hop 256, win 1024, 64 mels, fmin 0), on batches of one
+or two rows and signals several frames long whose noise floor keeps the
+dynamic range under 80 dB.  The other FFT sizes, a window shorter than the
+FFT, hops that do not divide n_fft, 80 and 40 bands, fmin / fmax / another
+sample rate, power_to_db's clamps, signals of one frame or one sample, batched
+NNLS and Griffin-Lim and the two-frame minimum are test_gpu_dsp_edges.py's,
+against a float64 reference.
+  STFT                fp32 rounding: within 2e-6 * 32 of the largest magnitude
   mel features        normalised log-mel within 1e-3 (max-abs, in [-1, 1] units)
   griffinlim          same magnitudes and start phases -> same audio within 1e-3
   mel_to_stft (NNLS)  librosa.util.nnls's minimiser itself (scipy L-BFGS-B on the
