@@ -402,6 +402,35 @@ int32_t m2_dsp_frames(const m2_dsp* dsp, int32_t L);
 int32_t m2_stft(const m2_dsp* dsp, const float* audio, int32_t B, int32_t L, void* out_spec, void* stream);
 int32_t m2_mel_spectrogram(const m2_dsp* dsp, const float* audio, int32_t B, int32_t L, float* out_mel,
                            void* stream);
+/* compute_mel_spectrogram over a ragged batch: B utterances of unequal length
+ * packed back to back, each featurized as if alone (the dB reference, the
+ * top_db floor and the min/max are per utterance and taken over all of its
+ * frames), written as the padded batch a collate function builds.
+ *   samples: sample_format M2_SAMPLES_F32 (float32) or M2_SAMPLES_I16 (PCM16,
+ *     read as (float)s / 32768.f); utterance b is samples[offsets[b],
+ *     offsets[b + 1]), L_b of them, frames T_b = 1 + L_b / hop;
+ *   offsets: int64 [B + 1] from 0, on the device, and the same values on the
+ *     host in offsets_host: shapes and grids come from the host copy, so the
+ *     call neither counts on the device nor synchronises;
+ *   normalize != 0: x / max|x| per utterance in float32 when the peak is
+ *     > 0, else unchanged (load_audio(normalize=True), audio.py:34-36);
+ *   max_frames > 0: only each utterance's first max_frames frames are stored
+ *     (the statistics still cover all T_b frames); 0 stores all;
+ *   out_mel [B, n_mels, T_out]: utterance b's min(T_b, max_frames) frames,
+ *     every column behind them exactly 0; out_frames int32 [B]: that count.
+ * Utterance b equals, bit for bit, the leading columns of m2_mel_spectrogram
+ * of its float32 signal alone, and two calls give equal bits (the only
+ * atomic is an integer max).  M2_E_SHAPE: an L_b of 0, a T_out smaller than
+ * the largest stored count, or total samples or n_mels x total frames
+ * reaching 2^31 (split the corpus into several calls).
+ * Scratch: m2_mel_features_ragged_workspace_bytes(B, total samples). */
+#define M2_SAMPLES_F32 0
+#define M2_SAMPLES_I16 1
+size_t m2_mel_features_ragged_workspace_bytes(const m2_dsp* dsp, int32_t B, int64_t total_samples);
+int32_t m2_mel_features_ragged(const m2_dsp* dsp, const void* samples, int32_t sample_format,
+                               const int64_t* offsets, const int64_t* offsets_host, int32_t B,
+                               int32_t normalize, int32_t max_frames, float* out_mel, int32_t T_out,
+                               int32_t* out_frames, void* workspace, size_t workspace_bytes, void* stream);
 /* mel_to_stft alone (librosa.feature.inverse.mel_to_stft, power 2, as
  * audio.py:138 reaches it): mel [B, n_mels, T] -> magnitudes out_mag
  * [B, T, n_fft/2+1] = sqrt(librosa.util.nnls(mel_basis, db_to_power)).

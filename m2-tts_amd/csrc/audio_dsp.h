@@ -1,6 +1,7 @@
 // What the audio kernels share (audio_dsp.hip, eval_metrics.hip, losses.hip):
 // the frame workgroup size, the in-LDS FFT, the frame loaders with their
-// padding modes, the fixed-order workgroup sum and the m2_dsp handle.
+// padding modes, the mel-band and dB bodies that the plain and the ragged
+// feature kernels both run, the workgroup reductions and the m2_dsp handle.
 #pragma once
 
 #include "m2_common.h"
@@ -47,16 +48,23 @@ __device__ __forceinline__ int pad_index(int i, int L) {
     return i < 0 ? -i : 2 * (L - 1) - i;
 }
 
-// Frame t of utterance b: samples t*hop - N/2 + n (centre padding) times the
-// window, into LDS as complex.
-template <int N, bool REFLECT = false>
-__device__ void load_frame(const float* __restrict__ y, int L, int hop, int t, const float* __restrict__ win, float2* a) {
+// Frame t of an utterance whose sample i is fetch(i): samples
+// t*hop - N/2 + n (centre padding) times the window, into LDS as complex.
+template <int N, bool REFLECT = false, class Fetch>
+__device__ __forceinline__ void load_frame_with(Fetch fetch, int L, int hop, int t, const float* __restrict__ win,
+                                                float2* a) {
     const int s0 = t * hop - N / 2;
     for (int n = threadIdx.x; n < N; n += NT) {
         const int i = pad_index<REFLECT>(s0 + n, L);
-        a[n] = make_float2(i >= 0 ? y[i] * win[n] : 0.f, 0.f);
+        a[n] = make_float2(i >= 0 ? fetch(i) * win[n] : 0.f, 0.f);
     }
     __syncthreads();
+}
+
+// load_frame_with over a float32 signal y[0, L).
+template <int N, bool REFLECT = false>
+__device__ void load_frame(const float* __restrict__ y, int L, int hop, int t, const float* __restrict__ win, float2* a) {
+    load_frame_with<N, REFLECT>([y](int i) { return y[i]; }, L, hop, t, win, a);
 }
 
 // load_frame for a pair: pred in the real part, target in the imaginary part.
@@ -82,6 +90,69 @@ __device__ __forceinline__ double block_sum(double v, double* red) {
     for (int i = 1; i < nw; ++i) v += red[i];
     return v;
 }
+
+// Maximum or minimum over the workgroup (order-independent); every thread
+// must call it.
+__device__ __forceinline__ float block_reduce(float v, bool is_max, float* red) {
+    for (int o = 32; o > 0; o >>= 1) {
+        const float w = __shfl_xor(v, o);
+        v = is_max ? fmaxf(v, w) : fminf(v, w);
+    }
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    __syncthreads();
+    if (lane == 0) red[wv] = v;
+    __syncthreads();
+    v = red[0];
+    for (int i = 1; i < nw; ++i) v = is_max ? fmaxf(v, red[i]) : fminf(v, red[i]);
+    return v;
+}
+
+// The mel branch of an STFT frame: power of the spectrum X (f <= N/2) into
+// P, then band m = sum_f W[m, f] P[f] over its bins [lo[m], hi[m]) to
+// dst[m * stride].  The plain and the ragged frame kernels both run this.
+template <int N>
+__device__ __forceinline__ void mel_bands(const float2* X, float* P, const float* __restrict__ W,
+                                          const int* __restrict__ lo, const int* __restrict__ hi, int n_mels,
+                                          float* __restrict__ dst, size_t stride) {
+    constexpr int F = N / 2 + 1;
+    for (int f = threadIdx.x; f < F; f += NT) P[f] = X[f].x * X[f].x + X[f].y * X[f].y;
+    __syncthreads();
+    for (int m = threadIdx.x; m < n_mels; m += NT) {
+        float s = 0.f;
+        for (int f = lo[m]; f < hi[m]; ++f) s += W[(size_t)m * F + f] * P[f];
+        dst[(size_t)m * stride] = s;
+    }
+}
+
+// power_to_db(ref=max, amin=1e-10, top_db=80) over one utterance's n mel
+// powers x, in place, by one workgroup; the floored dB values stay in x and
+// the [-1, 1] normalisation of one of them is db_unit(v, lo, sc).
+struct DbRange {
+    float lo, sc;
+};
+__device__ __forceinline__ DbRange db_floor(float* __restrict__ x, size_t n, float* red) {
+    float mx = -INFINITY;
+    for (size_t i = threadIdx.x; i < n; i += blockDim.x) mx = fmaxf(mx, x[i]);
+    const float ref = block_reduce(mx, true, red);
+    const float off = 10.f * log10f(fmaxf(1e-10f, ref));
+    float lmax = -INFINITY;
+    for (size_t i = threadIdx.x; i < n; i += blockDim.x) {
+        const float v = 10.f * log10f(fmaxf(1e-10f, x[i])) - off;
+        x[i] = v;
+        lmax = fmaxf(lmax, v);
+    }
+    const float floor_db = block_reduce(lmax, true, red) - 80.f;
+    float vmin = INFINITY, vmax2 = -INFINITY;
+    for (size_t i = threadIdx.x; i < n; i += blockDim.x) {
+        const float v = fmaxf(x[i], floor_db);
+        x[i] = v;
+        vmin = fminf(vmin, v);
+        vmax2 = fmaxf(vmax2, v);
+    }
+    const float lo = block_reduce(vmin, false, red), hi = block_reduce(vmax2, true, red);
+    return DbRange{lo, 2.f / (hi - lo)};
+}
+__device__ __forceinline__ float db_unit(float v, DbRange r) { return (v - r.lo) * r.sc - 1.f; }
 
 }  // namespace dsp
 }  // namespace m2

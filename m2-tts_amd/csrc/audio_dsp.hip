@@ -14,12 +14,18 @@
 //     contiguous bin range) -> [n_mels, frames]; then one workgroup per
 //     utterance does power_to_db (ref = max, amin 1e-10, top_db 80) and the
 //     [-1, 1] normalisation with LDS reductions.
+//   ragged mel features: the same two bodies (audio_dsp.h) over utterances
+//     of unequal length packed back to back, one workgroup per frame of the
+//     whole batch and one per utterance, after a peak pass; PCM16 conversion
+//     and peak normalisation are fused into the frame loader, and the padded,
+//     truncated, zero-filled [B, n_mels, T_out] is written directly.
 //   Griffin-Lim: magnitudes from the mel by projected-gradient NNLS
 //     (Nesterov-accelerated, X >= 0, from the clipped pseudo-inverse like
 //     librosa.util.nnls's start), then n_iter x [iSTFT frames -> overlap-add
 //     with the window-sum-square division -> STFT frames with the momentum
 //     update of the phases]; the overlap-add is a gather (each sample sums
 //     its <= n_fft / hop frames), so results are deterministic.
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -43,32 +49,12 @@ __global__ __launch_bounds__(NT) void stft_kernel(const float* __restrict__ y, i
     const int t = blockIdx.x, u = blockIdx.y;
     load_frame<N>(y + (size_t)u * L, L, hop, t, win, a);
     const float2* X = fft_lds<N, false>(a, b, tw);
-    constexpr int F = N / 2 + 1;
     if (spec) {
+        constexpr int F = N / 2 + 1;
         for (int f = threadIdx.x; f < F; f += NT) spec[((size_t)u * frames + t) * F + f] = X[f];
         return;
     }
-    for (int f = threadIdx.x; f < F; f += NT) P[f] = X[f].x * X[f].x + X[f].y * X[f].y;
-    __syncthreads();
-    for (int m = threadIdx.x; m < n_mels; m += NT) {
-        float s = 0.f;
-        for (int f = lo[m]; f < hi[m]; ++f) s += W[(size_t)m * F + f] * P[f];
-        mel[((size_t)u * n_mels + m) * frames + t] = s;
-    }
-}
-
-__device__ float block_reduce(float v, bool is_max, float* red) {
-    for (int o = 32; o > 0; o >>= 1) {
-        const float w = __shfl_xor(v, o);
-        v = is_max ? fmaxf(v, w) : fminf(v, w);
-    }
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    __syncthreads();
-    if (lane == 0) red[wv] = v;
-    __syncthreads();
-    v = red[0];
-    for (int i = 1; i < nw; ++i) v = is_max ? fmaxf(v, red[i]) : fminf(v, red[i]);
-    return v;
+    mel_bands<N>(X, P, W, lo, hi, n_mels, mel + (size_t)u * n_mels * frames + t, (size_t)frames);
 }
 
 // power_to_db(ref=max, amin=1e-10, top_db=80) and 2 (x - min)/(max - min) - 1,
@@ -76,27 +62,166 @@ __device__ float block_reduce(float v, bool is_max, float* red) {
 __global__ __launch_bounds__(1024) void db_norm_kernel(float* __restrict__ mel, int n) {
     __shared__ float red[16];
     float* x = mel + (size_t)blockIdx.x * n;
-    float mx = -INFINITY;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) mx = fmaxf(mx, x[i]);
-    const float ref = block_reduce(mx, true, red);
-    const float off = 10.f * log10f(fmaxf(1e-10f, ref));
-    float lmax = -INFINITY;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        const float v = 10.f * log10f(fmaxf(1e-10f, x[i])) - off;
-        x[i] = v;
-        lmax = fmaxf(lmax, v);
+    const DbRange r = db_floor(x, (size_t)n, red);
+    for (int i = threadIdx.x; i < n; i += blockDim.x) x[i] = db_unit(x[i], r);
+}
+
+// ---- ragged mel features (m2_mel_features_ragged) --------------------------
+// Utterance u owns samples [off[u], off[u + 1]) of the packed buffer and
+// frames [fp[u], fp[u + 1]) of the batch.  Sample i of it is the float32
+// value (int16 PCM: s / 32768) divided by the utterance's peak when one is
+// given (pk > 0), exactly the host arithmetic of load_audio(normalize=True).
+struct RaggedSamples {
+    const void* p;
+    int fmt;  // M2_SAMPLES_F32 / M2_SAMPLES_I16
+    __device__ __forceinline__ float raw(int64_t i) const {
+        return fmt == M2_SAMPLES_I16 ? (float)static_cast<const int16_t*>(p)[i] / 32768.f
+                                     : static_cast<const float*>(p)[i];
     }
-    const float floor_db = block_reduce(lmax, true, red) - 80.f;
-    float vmin = INFINITY, vmax2 = -INFINITY;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        const float v = fmaxf(x[i], floor_db);
-        x[i] = v;
-        vmin = fminf(vmin, v);
-        vmax2 = fmaxf(vmax2, v);
+};
+
+// The largest u in [0, B) with pre[u] <= g, for a non-decreasing pre[0..B]
+// with pre[0] <= g < pre[B].
+__device__ __forceinline__ int ragged_find(const int64_t* __restrict__ pre, int B, int64_t g) {
+    int lo = 0, hi = B;  // pre[lo] <= g < pre[hi]
+    while (hi - lo > 1) {
+        const int mid = lo + (hi - lo) / 2;
+        if (pre[mid] <= g) lo = mid;
+        else hi = mid;
     }
-    const float lo = block_reduce(vmin, false, red), hi = block_reduce(vmax2, true, red);
-    const float sc = 2.f / (hi - lo);
-    for (int i = threadIdx.x; i < n; i += blockDim.x) x[i] = (x[i] - lo) * sc - 1.f;
+    return lo;
+}
+
+// Frame prefix fp[0..B] (fp[u + 1] - fp[u] = 1 + L_u / hop) from the sample
+// offsets, the stored frame counts, and the peaks cleared; one workgroup.
+constexpr int kPrepNT = 1024;
+__global__ __launch_bounds__(kPrepNT) void ragged_prep_kernel(const int64_t* __restrict__ off, int B, int hop,
+                                                               int max_frames, int64_t* __restrict__ fp,
+                                                               unsigned* __restrict__ peak,
+                                                               int32_t* __restrict__ out_frames) {
+    __shared__ int64_t part[kPrepNT];
+    const int per = (B + kPrepNT - 1) / kPrepNT;
+    const int u0 = min(B, (int)threadIdx.x * per), u1 = min(B, u0 + per);
+    int64_t s = 0;
+    for (int u = u0; u < u1; ++u) s += 1 + (off[u + 1] - off[u]) / hop;
+    part[threadIdx.x] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int64_t acc = 0;
+        for (int i = 0; i < kPrepNT; ++i) {
+            const int64_t v = part[i];
+            part[i] = acc;
+            acc += v;
+        }
+        fp[B] = acc;
+    }
+    __syncthreads();
+    s = part[threadIdx.x];
+    for (int u = u0; u < u1; ++u) {
+        const int64_t T = 1 + (off[u + 1] - off[u]) / hop;
+        fp[u] = s;
+        s += T;
+        peak[u] = 0u;
+        out_frames[u] = (int32_t)(max_frames > 0 && T > max_frames ? max_frames : T);
+    }
+}
+
+// max |x| over the packed samples [s0, s1), strided over the workgroup (the
+// partial maxima stay per thread).  With a 16-byte aligned buffer the whole
+// 16-byte vectors inside the range are loaded as such.
+__device__ __forceinline__ float ragged_range_max(const RaggedSamples& smp, int64_t s0, int64_t s1) {
+    float mx = 0.f;
+    int64_t a0 = s1, a1 = s1;  // vectors cover [a0, a1)
+    if ((reinterpret_cast<uintptr_t>(smp.p) & 15) == 0) {
+        const int per = smp.fmt == M2_SAMPLES_I16 ? 8 : 4;
+        a0 = min(s1, (s0 + per - 1) / per * per);
+        a1 = max(a0, s1 / per * per);
+        const int nv = (int)((a1 - a0) / per);
+        if (smp.fmt == M2_SAMPLES_I16) {
+            const int4* v = reinterpret_cast<const int4*>(static_cast<const int16_t*>(smp.p) + a0);
+            for (int k = threadIdx.x; k < nv; k += NT) {
+                const int4 q = v[k];
+                const int w[4] = {q.x, q.y, q.z, q.w};
+                for (int j = 0; j < 4; ++j) {
+                    mx = fmaxf(mx, fabsf((float)(int16_t)(w[j] & 0xffff) / 32768.f));
+                    mx = fmaxf(mx, fabsf((float)(int16_t)(w[j] >> 16) / 32768.f));
+                }
+            }
+        } else {
+            const float4* v = reinterpret_cast<const float4*>(static_cast<const float*>(smp.p) + a0);
+            for (int k = threadIdx.x; k < nv; k += NT) {
+                const float4 q = v[k];
+                mx = fmaxf(fmaxf(fmaxf(mx, fabsf(q.x)), fmaxf(fabsf(q.y), fabsf(q.z))), fabsf(q.w));
+            }
+        }
+    }
+    for (int64_t i = s0 + threadIdx.x; i < a0; i += NT) mx = fmaxf(mx, fabsf(smp.raw(i)));
+    for (int64_t i = a1 + threadIdx.x; i < s1; i += NT) mx = fmaxf(mx, fabsf(smp.raw(i)));
+    return mx;
+}
+
+// peak[u] = bits of max |x| over utterance u: a max does not depend on the
+// order, and the bits of non-negative floats order as unsigned integers, so
+// the integer atomicMax is reproducible.  Each workgroup takes kPeakChunk
+// packed samples and walks the utterances that have samples in them (one,
+// sometimes two): per utterance a workgroup maximum and one atomic.
+constexpr int kPeakChunk = 16384;
+__global__ __launch_bounds__(NT) void ragged_peak_kernel(RaggedSamples smp, const int64_t* __restrict__ off, int B,
+                                                         unsigned* __restrict__ peak) {
+    __shared__ float red[NT / 64];
+    const int64_t c0 = (int64_t)blockIdx.x * kPeakChunk, c1 = min(c0 + (int64_t)kPeakChunk, off[B]);
+    int64_t s0 = c0;
+    for (int u = ragged_find(off, B, c0); s0 < c1; ++u) {  // uniform over the workgroup; ends with u < B
+        const int64_t s1 = min(c1, off[u + 1]);
+        const float mx = block_reduce(ragged_range_max(smp, s0, s1), true, red);
+        if (threadIdx.x == 0) atomicMax(peak + u, __float_as_uint(mx));
+        s0 = s1;
+    }
+}
+
+// One workgroup per frame of the whole batch: stft_kernel's mel branch, the
+// conversion and the division by the peak fused into the frame loader.
+// raw[n_mels * fp[u] + m * T_u + t]: utterance u's [n_mels, T_u] mel powers.
+template <int N>
+__global__ __launch_bounds__(NT) void ragged_frame_kernel(RaggedSamples smp, const int64_t* __restrict__ off,
+                                                          const int64_t* __restrict__ fp, int B, int hop,
+                                                          const unsigned* __restrict__ peak,
+                                                          const float* __restrict__ win, const float2* __restrict__ tw,
+                                                          const float* __restrict__ W, const int* __restrict__ lo,
+                                                          const int* __restrict__ hi, int n_mels,
+                                                          float* __restrict__ raw) {
+    __shared__ float2 a[N], b[N];
+    __shared__ float P[N / 2 + 1];
+    const int64_t g = blockIdx.x;
+    const int u = ragged_find(fp, B, g);
+    const int64_t o = off[u], T = fp[u + 1] - fp[u];
+    const int L = (int)(off[u + 1] - o), t = (int)(g - fp[u]);
+    const float pk = peak ? __uint_as_float(peak[u]) : 0.f;
+    load_frame_with<N>([smp, o, pk](int i) {
+        const float v = smp.raw(o + i);
+        return pk > 0.f ? v / pk : v;
+    }, L, hop, t, win, a);
+    const float2* X = fft_lds<N, false>(a, b, tw);
+    mel_bands<N>(X, P, W, lo, hi, n_mels, raw + (size_t)n_mels * (size_t)fp[u] + t, (size_t)T);
+}
+
+// One workgroup per utterance: db_norm_kernel's arithmetic over all of the
+// utterance's frames (in place in raw), then the first out_frames[u] columns
+// to out[u, :, :] and exact zeros behind them up to T_out.
+__global__ __launch_bounds__(1024) void ragged_db_norm_kernel(float* __restrict__ raw, const int64_t* __restrict__ fp,
+                                                              int n_mels, const int32_t* __restrict__ out_frames,
+                                                              int T_out, float* __restrict__ out) {
+    __shared__ float red[16];
+    const int u = blockIdx.x;
+    const size_t T = (size_t)(fp[u + 1] - fp[u]);
+    float* x = raw + (size_t)n_mels * (size_t)fp[u];
+    const DbRange r = db_floor(x, (size_t)n_mels * T, red);
+    const size_t keep = (size_t)out_frames[u], To = (size_t)T_out;
+    float* y = out + (size_t)u * n_mels * To;
+    for (size_t i = threadIdx.x; i < (size_t)n_mels * To; i += blockDim.x) {
+        const size_t m = i / To, t = i - m * To;
+        y[i] = t < keep ? db_unit(x[m * T + t], r) : 0.f;
+    }
 }
 
 // Griffin-Lim magnitudes (librosa.feature.inverse.mel_to_stft, power 2):
@@ -514,6 +639,69 @@ int32_t m2_mel_spectrogram(const m2_dsp* d, const float* audio, int32_t B, int32
     M2_LAUNCHED("stft_kernel(mel)");
     hipLaunchKernelGGL(dsp::db_norm_kernel, dim3(B), dim3(1024), 0, st, out_mel, d->n_mels * T);
     M2_LAUNCHED("db_norm_kernel");
+    return M2_OK;
+}
+
+// Frames of the whole batch are at most B + total_samples / hop.
+size_t m2_mel_features_ragged_workspace_bytes(const m2_dsp* d, int32_t B, int64_t total_samples) {
+    if (!d || B < 0 || total_samples < 0) return 0;
+    Sizer s;
+    s.take<int64_t>((size_t)B + 1);                                           // frame prefix
+    s.take<unsigned>((size_t)B);                                              // peaks (float bits)
+    s.take<float>((size_t)d->n_mels * ((size_t)B + (size_t)(total_samples / d->hop)));  // mel powers
+    return s.off + 256;
+}
+
+int32_t m2_mel_features_ragged(const m2_dsp* d, const void* samples, int32_t sample_format, const int64_t* offsets,
+                               const int64_t* offsets_host, int32_t B, int32_t normalize, int32_t max_frames,
+                               float* out_mel, int32_t T_out, int32_t* out_frames, void* workspace,
+                               size_t workspace_bytes, void* stream) {
+    M2_CHECK_ARG(d && B >= 0 && max_frames >= 0 && T_out >= 0 &&
+                     (sample_format == M2_SAMPLES_F32 || sample_format == M2_SAMPLES_I16),
+                 "m2_mel_features_ragged: bad argument");
+    if (B == 0) return M2_OK;
+    M2_CHECK_ARG(samples && offsets && offsets_host && out_frames && (out_mel || T_out == 0),
+                 "m2_mel_features_ragged: bad argument");
+    M2_CHECK_ARG(offsets_host[0] == 0, "m2_mel_features_ragged: offsets[0] must be 0");
+    int64_t frames = 0, keep_max = 0;
+    for (int b = 0; b < B; ++b) {
+        const int64_t L = offsets_host[b + 1] - offsets_host[b];
+        M2_CHECK_SHAPE(L > 0, "m2_mel_features_ragged: an utterance has no samples");
+        M2_CHECK_SHAPE(offsets_host[b + 1] < ((int64_t)1 << 31), "m2_mel_features_ragged: 2^31 samples or more in one call");
+        const int64_t T = 1 + L / d->hop;
+        frames += T;
+        keep_max = std::max(keep_max, max_frames > 0 ? std::min<int64_t>(T, max_frames) : T);
+    }
+    const int64_t total = offsets_host[B];
+    M2_CHECK_SHAPE((int64_t)d->n_mels * frames < ((int64_t)1 << 31),
+                   "m2_mel_features_ragged: n_mels x frames reaches 2^31 in one call");
+    M2_CHECK_SHAPE(T_out >= keep_max, "m2_mel_features_ragged: T_out is smaller than the largest stored frame count");
+    Carve c(workspace, workspace_bytes);
+    int64_t* fp = c.take<int64_t>((size_t)B + 1);
+    unsigned* peak = c.take<unsigned>((size_t)B);
+    float* raw = c.take<float>((size_t)d->n_mels * (size_t)frames);
+    if (!c.ok) return fail(M2_E_WORKSPACE, "m2_mel_features_ragged: workspace too small");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dsp::RaggedSamples smp{samples, sample_format};
+    hipLaunchKernelGGL(dsp::ragged_prep_kernel, dim3(1), dim3(dsp::kPrepNT), 0, st, offsets, B, d->hop, max_frames, fp,
+                       peak, out_frames);
+    M2_LAUNCHED("ragged_prep_kernel");
+    if (normalize) {
+        hipLaunchKernelGGL(dsp::ragged_peak_kernel, dim3((unsigned)((total + dsp::kPeakChunk - 1) / dsp::kPeakChunk)),
+                           dim3(dsp::NT), 0, st, smp, offsets, B, peak);
+        M2_LAUNCHED("ragged_peak_kernel");
+    }
+#define M2_RFRAME(NN)                                                                                             \
+    hipLaunchKernelGGL((dsp::ragged_frame_kernel<NN>), dim3((unsigned)frames), dim3(dsp::NT), 0, st, smp, offsets, \
+                       fp, B, d->hop, normalize ? peak : nullptr, d->win, d->tw, d->W, d->lo, d->hi, d->n_mels, raw)
+    if (d->n_fft == 512) M2_RFRAME(512);
+    else if (d->n_fft == 1024) M2_RFRAME(1024);
+    else M2_RFRAME(2048);
+#undef M2_RFRAME
+    M2_LAUNCHED("ragged_frame_kernel");
+    hipLaunchKernelGGL(dsp::ragged_db_norm_kernel, dim3(B), dim3(1024), 0, st, raw, fp, d->n_mels, out_frames, T_out,
+                       out_mel);
+    M2_LAUNCHED("ragged_db_norm_kernel");
     return M2_OK;
 }
 

@@ -78,6 +78,9 @@ _SIGNATURES = {
     "m2_dsp_frames": (c_i32, [c_vp, c_i32]),
     "m2_stft": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp]),
     "m2_mel_spectrogram": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp]),
+    "m2_mel_features_ragged_workspace_bytes": (c_size, [c_vp, c_i32, c_i64]),
+    "m2_mel_features_ragged": (c_i32, [c_vp, c_vp, c_i32, c_vp, ctypes.POINTER(c_i64), c_i32, c_i32, c_i32, c_vp, c_i32,
+                                       c_vp, c_vp, c_size, c_vp]),
     "m2_griffin_lim_workspace_bytes": (c_size, [c_vp, c_i32, c_i32]),
     "m2_mel_to_magnitude_workspace_bytes": (c_size, [c_vp, c_i32, c_i32]),
     "m2_mel_to_magnitude": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_size, c_vp]),

@@ -70,6 +70,67 @@ class Dsp:
         _lib.call("m2_mel_spectrogram", self.handle, y.data_ptr(), B, L, out.data_ptr(), stream_handle(y.device))
         return out
 
+    def mel_features_ragged(self, samples: Tensor, offsets=None, lengths=None, normalize: bool = True,
+                            max_frames: int = 0, out: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+        """compute_mel_spectrogram of B utterances of unequal length in one call
+        (m2_mel_features_ragged), each as if featurized alone.
+
+        ``samples``: the utterances packed back to back, a 1-D device tensor,
+        float32 or int16 (PCM16, read as s / 32768).  ``offsets`` [B + 1] from 0
+        or ``lengths`` [B]: host integers (a list, numpy array or CPU tensor) -
+        the shapes come from them, so nothing is counted on the device.
+        ``normalize``: x / max|x| per utterance when the peak is > 0
+        (load_audio(normalize=True)).  ``max_frames`` > 0 stores only each
+        utterance's first ``max_frames`` frames; the dB reference, the top_db
+        floor and the min/max still cover all of its frames.
+
+        -> (mel [B, n_mels, T_out] float32, frames [B] int32) on the device:
+        utterance b's first frames[b] columns equal ``mel_spectrogram`` of it
+        alone bit for bit, every column behind them is exactly 0.  ``out``
+        ([B, n_mels, T_out], T_out at least the largest stored count) is
+        written in full when given."""
+        require_device(samples, what="m2 mel_features_ragged")
+        if samples.dtype not in (torch.float32, torch.int16):
+            raise TypeError(f"mel_features_ragged: samples must be float32 or int16, got {samples.dtype}")
+        if (offsets is None) == (lengths is None):
+            raise ValueError("mel_features_ragged: give offsets or lengths")
+        if offsets is not None:
+            off = torch.as_tensor(offsets, dtype=torch.int64).cpu().reshape(-1)
+            if off.numel() < 1 or int(off[0]) != 0:
+                raise ValueError("mel_features_ragged: offsets must be [B + 1], from 0")
+        else:
+            ln = torch.as_tensor(lengths, dtype=torch.int64).cpu().reshape(-1)
+            off = torch.zeros(ln.numel() + 1, dtype=torch.int64)
+            torch.cumsum(ln, 0, out=off[1:])
+        off = off.contiguous()
+        B = off.numel() - 1
+        s = samples.reshape(-1).contiguous()
+        if int(off[-1]) != s.numel():
+            raise ValueError(f"mel_features_ragged: offsets end at {int(off[-1])}, {s.numel()} samples given")
+        dev = s.device
+        frames = torch.empty(B, dtype=torch.int32, device=dev)
+        T = 1 + (off[1:] - off[:-1]) // self.hop
+        keep = int((T.clamp(max=max_frames) if max_frames > 0 else T).max()) if B else 0
+        if out is None:
+            out = torch.empty(B, self.n_mels, keep, device=dev, dtype=torch.float32)
+        else:
+            require_device(out, what="m2 mel_features_ragged")
+            if (out.dtype != torch.float32 or out.dim() != 3 or out.shape[:2] != (B, self.n_mels)
+                    or not out.is_contiguous() or out.device != dev):
+                raise ValueError(f"mel_features_ragged: out must be contiguous float32 [{B}, {self.n_mels}, T_out] "
+                                 f"on {dev}, got {out.dtype} {tuple(out.shape)} on {out.device}")
+        if B == 0:
+            return out, frames
+        off_dev = off.to(dev)
+        need = int(_lib.load().m2_mel_features_ragged_workspace_bytes(self.handle, B, s.numel()))
+        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        _lib.call("m2_mel_features_ragged", self.handle, s.data_ptr(), 1 if s.dtype == torch.int16 else 0,
+                  off_dev.data_ptr(), ctypes.cast(off.data_ptr(), ctypes.POINTER(ctypes.c_int64)), B, int(bool(normalize)),
+                  int(max_frames), out.data_ptr(), out.shape[2], frames.data_ptr(), self._ws.data_ptr(),
+                  self._ws.numel(), stream_handle(dev))
+        return out, frames
+
     def mel_to_magnitude(self, mel: Tensor, nnls_iters: int = 200) -> Tensor:
         """librosa.feature.inverse.mel_to_stft of (mel + 1) / 2 in dB (audio.py:128-132)
         -> magnitudes [B, F, T]: librosa.util.nnls's result, its L-BFGS-B's

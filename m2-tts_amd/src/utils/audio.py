@@ -11,14 +11,16 @@ int16 range.
 float32 like it does, but compute on the GPU (m2amd.dsp: STFT, mel filters,
 power_to_db, NNLS, Griffin-Lim kernels) instead of librosa, which this image
 does not have.  ``mel_to_audio``'s random phase start (librosa
-init='random') takes an optional ``seed``.
+init='random') takes an optional ``seed``.  ``AudioProcessor.process_files``
+is an addition: ``process_file`` of a whole corpus in a few ragged GPU calls,
+bit-equal to the one-file path (data.dataset's featurization).
 """
 from __future__ import annotations
 
 import logging
 import wave
 from pathlib import Path
-from typing import Optional, Tuple, Union
+from typing import List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -85,6 +87,71 @@ class AudioProcessor:
         audio = audio / m if m > 0 else audio  # load_audio(normalize=True), audio.py:36-37
         return audio, self.compute_mel_spectrogram(audio)
 
+    def process_files(self, paths: Sequence[Union[str, Path]], max_mel_length: Optional[int] = None,
+                      return_audio: bool = True, sample_budget: int = 1 << 26) -> List[Optional[Tuple]]:
+        """``process_file`` of many files in a few GPU calls -> a list, per file
+        in order, of ``(audio, mel_spec)`` exactly as ``process_file`` returns
+        them (``audio`` is None without ``return_audio``), or None for a file
+        that could not be used.
+
+        The files (mono PCM16 WAV, read with ``wave``) are packed as int16
+        into one host buffer per chunk of at most ``sample_budget`` samples (a
+        single longer file goes alone); each chunk is one upload, one ragged
+        feature call (m2amd.dsp.Dsp.mel_features_ragged: every utterance
+        peak-normalised and featurized as if alone) and one download.
+        ``max_mel_length`` keeps each mel's first frames only, as the
+        dataset's truncation does; the dB scaling still covers the whole file.
+
+        As in ``process_file`` there is no resampler (``librosa.load``'s
+        resampling is out of scope): a file at another sample rate is one
+        that cannot be used.  Such a file, an unreadable one or one without
+        samples is logged and yields None; the others are unaffected."""
+        from m2amd.dsp import get_dsp
+        paths = list(paths)
+        results: List[Optional[Tuple]] = [None] * len(paths)
+        if not torch.cuda.is_available():
+            raise RuntimeError("m2-tts_amd audio features run on a ROCm GPU; none is visible (no CPU path)")
+        dev = torch.device("cuda", torch.cuda.current_device())
+        d = get_dsp(self.sample_rate, self.n_fft, self.hop_length, self.win_length, self.n_mels, self.fmin, self.fmax,
+                    dev)
+        max_frames = int(max_mel_length) if max_mel_length else 0
+        chunk: List[Tuple[int, np.ndarray]] = []
+        held = 0
+
+        def flush():
+            nonlocal chunk, held
+            if not chunk:
+                return
+            lengths = [len(pcm) for _, pcm in chunk]
+            packed = torch.from_numpy(np.concatenate([pcm for _, pcm in chunk]))
+            mel, frames = d.mel_features_ragged(packed.to(dev), lengths=lengths, normalize=True, max_frames=max_frames)
+            mel, frames = mel.cpu().numpy(), frames.cpu().numpy()
+            for k, (i, pcm) in enumerate(chunk):
+                audio = None
+                if return_audio:
+                    audio = pcm.astype(np.float32) / 32768.0
+                    m = np.max(np.abs(audio))
+                    audio = audio / m if m > 0 else audio
+                results[i] = (audio, np.ascontiguousarray(mel[k, :, :frames[k]]))
+            chunk, held = [], 0
+
+        for i, path in enumerate(paths):
+            try:
+                pcm, sr = _read_pcm16(path)
+                if sr != self.sample_rate:
+                    raise ValueError(f"{sr} Hz, expected {self.sample_rate} (no resampler in this build)")
+                if len(pcm) == 0:
+                    raise ValueError("no samples")
+            except Exception as e:  # this file only
+                logger.warning(f"Failed to read {path}: {e}")
+                continue
+            if chunk and held + len(pcm) > sample_budget:
+                flush()
+            chunk.append((i, pcm))
+            held += len(pcm)
+        flush()
+        return results
+
     def mel_to_audio(self, mel_spec, seed: Optional[int] = None) -> np.ndarray:
         return mel_to_audio(mel_spec, self.sample_rate, self.n_fft, self.hop_length, self.win_length, seed=seed)
 
@@ -110,9 +177,14 @@ def save_audio(audio: Union[np.ndarray, torch.Tensor], output_path: Union[str, P
     logger.debug(f"Saved audio to {output_path}")
 
 
-def load_audio_pcm16(path: Union[str, Path]) -> Tuple[np.ndarray, int]:
-    """Read a mono PCM16 WAV back as float32 in [-1, 1) (samples / 32768) and its rate."""
+def _read_pcm16(path: Union[str, Path]) -> Tuple[np.ndarray, int]:
+    """The int16 samples of a mono PCM16 WAV and its rate."""
     with wave.open(str(path), "rb") as w:
         assert w.getsampwidth() == 2 and w.getnchannels() == 1, "mono PCM16 only"
-        data = np.frombuffer(w.readframes(w.getnframes()), dtype="<i2")
-        return data.astype(np.float32) / 32768.0, w.getframerate()
+        return np.frombuffer(w.readframes(w.getnframes()), dtype="<i2"), w.getframerate()
+
+
+def load_audio_pcm16(path: Union[str, Path]) -> Tuple[np.ndarray, int]:
+    """Read a mono PCM16 WAV back as float32 in [-1, 1) (samples / 32768) and its rate."""
+    data, sr = _read_pcm16(path)
+    return data.astype(np.float32) / 32768.0, sr
