@@ -496,8 +496,10 @@ int32_t m2_eval_dct_table(int32_t n_mels, double* out_host);
 int32_t m2_eval_mcd(const float* pred, const float* target, const int32_t* cols, const double* table, int32_t B,
                     int32_t n_mels, int32_t Tp, int32_t Tt, int32_t pred_transposed, double* out, void* stream);
 
-/* ---- training losses, forward values (src/training/losses.py) ---------------
- * No gradients.  Per-utterance rows of double sums as above, columns named by
+/* ---- training losses (src/training/losses.py) ------------------------------
+ * Forward values, and the backward of the discriminator step (the gradient
+ * of the adversarial discriminator loss with respect to the discriminators'
+ * parameters; nothing else has a gradient).  Per-utterance rows of double sums as above, columns named by
  * m2_loss_column_count(kind) / m2_loss_column_name(kind, i): kind 0 =
  * m2_loss_spectral, 1 = m2_disc_losses.  Fixed-order reductions: equal inputs
  * give equal bits, and a batched row equals the row of the utterance alone.
@@ -541,7 +543,34 @@ int32_t m2_eval_mcd(const float* pred, const float* target, const int32_t* cols,
  * 1e-8) - ln(w_j sum_f |T| + 1e-8)| (PerceptualLoss._mel_features: its filter
  * rows are constant), frames.  spec_pred / spec_target (or NULL): the
  * complex64 spectra [B, frames, n_fft/2+1] the sums were taken from; DC and
- * Nyquist bins have imaginary part +0. */
+ * Nyquist bins have imaginary part +0.
+ *
+ * m2_conv1d_strided_backward: the gradients of one layer
+ * y = conv1d(leaky(x_pre, in_slope); w, b; k, stride, padding, groups) given
+ * dy [B,Cout,Lo], the cotangent of y: dx (or NULL) [B,Cin,L], the cotangent of
+ * x_pre (leaky'(v) = v > 0 ? 1 : in_slope, the forward's predicate; exactly 0
+ * at positions no output read); dw [Cout, Cin/groups, k] and db (or NULL)
+ * [Cout], summed over the batch.  Outputs are overwritten.  w and dw are in
+ * PyTorch's layout.  Same generality as m2_conv1d_strided (Cin at most
+ * 65535); the geometries m2_conv1d_strided runs on the MFMA get dx from it
+ * (Cin >= 16), every Cout >= 16 gets dw from it, split over K into partials
+ * in the workspace that are added in a fixed order (no floating-point
+ * atomics: equal inputs give equal bits); the rest run one thread per dx
+ * sample and one workgroup per dw element.
+ *
+ * m2_disc_step: m2_disc_losses's `out` (same launches, same bits; real and
+ * fake are both required) and, in grads (n_scales * 14 device pointers in
+ * state_dict order, PyTorch layouts, overwritten), the gradient of
+ *   L_D = (1/n_scales) sum_s [ mean (D_s(real) - 1)^2 + mean D_s(fake)^2 ]
+ * with respect to every weight and bias.  The logit cotangents
+ * 2 (D - 1) / (N_s n_scales) and 2 D / (N_s n_scales), N_s = B len(s,6), need
+ * no pass of their own: each (slice, scale) runs forward, then each side
+ * backward while its maps are in the workspace, and the gradients accumulate
+ * over slices and sides in stream order.  m2_disc_set_slice_bytes gives the
+ * slices of m2_disc_losses (the bound counts the maps of both sides); the
+ * workspace query adds two cotangent maps of the widest layer and the pooled
+ * audio per utterance of a slice, and the split-K partials (at most 32 MiB
+ * beyond one copy of the largest weight). */
 typedef struct m2_disc m2_disc;
 int32_t m2_loss_column_count(int32_t kind);
 const char* m2_loss_column_name(int32_t kind, int32_t index);
@@ -563,6 +592,15 @@ int32_t m2_disc_forward(const m2_disc* disc, const float* x, int32_t B, int32_t 
 size_t m2_disc_losses_workspace_bytes(const m2_disc* disc, int32_t B, int32_t L);
 int32_t m2_disc_losses(const m2_disc* disc, const float* real, const float* fake, int32_t B, int32_t L, double* out,
                        void* workspace, size_t workspace_bytes, void* stream);
+size_t m2_conv1d_strided_backward_workspace_bytes(int32_t ksize, int32_t stride, int32_t padding, int32_t groups,
+                                                  int32_t B, int32_t Cin, int32_t Cout, int32_t L);
+int32_t m2_conv1d_strided_backward(const float* x_pre, const float* w, const float* dy, int32_t ksize, int32_t stride,
+                                   int32_t padding, int32_t groups, float in_slope, int32_t B, int32_t Cin,
+                                   int32_t Cout, int32_t L, float* dx, float* dw, float* db, void* workspace,
+                                   size_t workspace_bytes, void* stream);
+size_t m2_disc_step_workspace_bytes(const m2_disc* disc, int32_t B, int32_t L);
+int32_t m2_disc_step(const m2_disc* disc, const float* real, const float* fake, int32_t B, int32_t L, double* out,
+                     float* const* grads, void* workspace, size_t workspace_bytes, void* stream);
 size_t m2_loss_spectral_workspace_bytes(const m2_dsp* dsp, int32_t B, int32_t L);
 int32_t m2_loss_spectral(const m2_dsp* dsp, const float* pred, const float* target, int32_t B, int32_t L,
                          const float* mel_weights, int32_t n_weights, double* out, void* spec_pred, void* spec_target,

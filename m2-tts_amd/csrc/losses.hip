@@ -1,7 +1,7 @@
-// Training-loss forward values on the GPU: the sums behind the reference's
+// Training losses on the GPU: the sums behind the reference's
 // src/training/losses.py (SpectralLoss, PerceptualLoss, MultiScaleDiscriminator,
-// AdversarialLoss), batched over utterances.  Forward only: nothing here
-// computes a gradient.
+// AdversarialLoss), batched over utterances, and the one gradient: the
+// discriminator loss with respect to the discriminators' parameters.
 //
 //   conv      Conv1d(k, stride, zero padding, groups) + bias, with a leaky
 //             slope on the input (the discriminators' feature maps are the
@@ -19,6 +19,13 @@
 //             runs real and fake of a slice scale by scale and reduces logits
 //             and feature maps to per-utterance double sums (chunk partials,
 //             then one workgroup per utterance) inside the workspace.
+//   backward  of y = conv(leaky(x_pre), w) + b, on the same exact-f32 MFMA:
+//             conv_dx_mfma_kernel (one stride-1 convolution per stride phase)
+//             and conv_dw_mfma_kernel (split over K into partials that
+//             dw_finish_kernel adds in order), direct kernels for the rest;
+//             m2_disc_step runs each (slice, scale) forward as losses does and
+//             then each side backward while its maps are in the workspace,
+//             accumulating the 42 gradients in stream order.
 //   spectral  spectral_frame_kernel: torch.stft framing (centre, reflect
 //             padding), pred and target through one complex FFT as in
 //             eval_metrics.hip; magnitudes and angles in double from the fp32
@@ -301,6 +308,265 @@ __global__ __launch_bounds__(NT) void reduce_finish_kernel(const double* __restr
     }
 }
 
+// ---- backward of y = conv(leaky(x_pre, in_slope), w) + b ---------------------------
+// Weight element (co, ci in group, tap) is at w[co sCo + ci sCi + tap sK] as in
+// conv_mfma_kernel.  dw and the split-K partials are in PyTorch's [Cout, Cin/g, k].
+
+constexpr int kDxM = 64;         // column positions per conv_dx_mfma workgroup (4 tiles of 16)
+constexpr int kTc = 64;          // output positions staged per conv_dw_mfma step
+constexpr int kDwTiles = 11;     // 16-column tiles per wave of conv_dw_mfma
+constexpr int kDwCols = 4 * 16 * kDwTiles;  // (input channel, tap) columns per workgroup
+constexpr int kDwCiMax = 64;     // input channels per conv_dw_mfma workgroup
+constexpr int kMaxSplits = 64;   // split-K partials of one weight gradient
+constexpr size_t kPartFloats = (size_t)8 << 20;  // floats the partials of one layer may take (beyond one copy of dw)
+
+__device__ __forceinline__ float leaky_grad(float v, float slope) { return v > 0.f ? 1.f : slope; }
+
+// Data gradient.  grid (column tiles, phase blocks x channel tiles, utterances);
+// dy [nb, Cout, Lo], x_pre and dx [nb, Cin, L].  Input position u = stride m +
+// phase - pad receives the taps phase + stride j against dy[m - j]: one stride-1
+// convolution per phase.  The four waves of a workgroup share the columns
+// m in [64 bx, +64) and split into pw phases (dx_phases(): 4 from stride 4,
+// so that a grouped layer's waves share one staged window) x 4 / pw row tiles
+// of 16 input channels: wave w takes phase pw pb + w % pw and the rows
+// [16 (4 / pw) tile + 16 (w / pw), +16), by = pb ntile + tile.  K runs over
+// (tap j, 4 output channels) with dy's window (64 + J - 1 samples,
+// J = ceil(k / stride)) staged in LDS 16 output channels at a time: lane
+// (r, q) supplies A = w[co + q][ci0 + r][phase + stride j] and
+// B = window[co + q][16 t + r - j].  A row tile spanning several groups takes
+// the union of their output channels, A = 0 outside a row's own group.  A
+// position no output read gets an empty sum: 0.
+__global__ __launch_bounds__(256) void conv_dx_mfma_kernel(const float* __restrict__ x_pre,
+                                                           const float* __restrict__ w,
+                                                           const float* __restrict__ dy, float* __restrict__ dx,
+                                                           ConvGeo g, int L, int Lo, long long sCo, long long sCi,
+                                                           long long sK, float in_slope, int J, int pw) {
+    extern __shared__ float ds[];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 15, q = lane >> 4;
+    const int Cg = g.Cin / g.groups, Mg = g.Cout / g.groups;
+    const int win = kDxM + J - 1, winp = win | 1;
+    const int rows = 16 * (4 / pw), ntile = (g.Cin + rows - 1) / rows;  // input channels per workgroup, their tiles
+    const int pb = blockIdx.y / ntile, cw0 = (blockIdx.y - pb * ntile) * rows;
+    const int m0 = blockIdx.x * kDxM, phase = pb * pw + wave % pw, u = blockIdx.z;
+    const int cw1 = min(cw0 + rows, g.Cin) - 1;
+    const int coW0 = cw0 / Cg * Mg, coW1 = (cw1 / Cg + 1) * Mg;  // output channels of this workgroup's groups
+    const int ci0 = cw0 + wave / pw * 16;
+    const bool active = ci0 < g.Cin && phase < g.stride;
+    int ca = 0, cb = 0;  // output channels of this wave's groups
+    if (active) {
+        ca = ci0 / Cg * Mg;
+        cb = (min(ci0 + 15, g.Cin - 1) / Cg + 1) * Mg;
+    }
+    const int ci = ci0 + r;
+    const bool row = ci < g.Cin;
+    const int grp = row ? ci / Cg : 0;
+    const int lo = row ? grp * Mg : 0, hi = row ? lo + Mg : 0;
+    const float* wrow = w + (row ? (long long)(ci - grp * Cg) * sCi : 0);
+    const float* dyb = dy + (size_t)u * g.Cout * Lo;
+    const int M = (L - 1 + g.pad) / g.stride + 1;
+    const int nt = min(4, (M - m0 + 15) / 16);
+    const int nj = phase < g.k ? (g.k - phase + g.stride - 1) / g.stride : 0;
+    f32x4 acc[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int cs = coW0; cs < coW1; cs += kCch) {
+        const int nch = min(kCch, coW1 - cs);
+        for (int i = tid; i < nch * win; i += 256) {
+            const int c = i / win, o = i - c * win, t = m0 - (J - 1) + o;
+            ds[c * winp + o] = (t >= 0 && t < Lo) ? dyb[(size_t)(cs + c) * Lo + t] : 0.f;
+        }
+        __syncthreads();
+        if (active) {
+            for (int j = 0; j < nj; ++j) {
+                const long long tapo = (long long)(phase + g.stride * j) * sK;
+                for (int c4 = 0; c4 < nch; c4 += 4) {
+                    const int cbase = cs + c4;
+                    if (cbase + 4 <= ca || cbase >= cb) continue;  // none of this wave's groups
+                    const int co = cbase + q;
+                    const bool v = c4 + q < nch;
+                    const float a = (v && co >= lo && co < hi) ? wrow[(long long)co * sCo + tapo] : 0.f;
+                    const float* br = ds + (c4 + q) * winp + r + (J - 1) - j;
+#pragma unroll
+                    for (int t = 0; t < 4; ++t)
+                        if (t < nt) {
+                            const float bv = v ? br[t * 16] : 0.f;
+                            acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bv, acc[t], 0, 0, 0);
+                        }
+                }
+            }
+        }
+        __syncthreads();
+    }
+    if (!active) return;
+    const float* xb = x_pre + (size_t)u * g.Cin * L;
+    float* dxb = dx + (size_t)u * g.Cin * L;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const long long pos = (long long)(m0 + t * 16 + r) * g.stride + phase - g.pad;
+        if (t < nt && pos >= 0 && pos < L) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int c = ci0 + 4 * q + i;
+                if (c < g.Cin) dxb[(size_t)c * L + pos] = acc[t][i] * leaky_grad(xb[(size_t)c * L + pos], in_slope);
+            }
+        }
+    }
+}
+
+// Data gradient, one thread per input sample.  grid (position blocks, Cin, utterances).
+__global__ __launch_bounds__(256) void conv_dx_direct_kernel(const float* __restrict__ x_pre,
+                                                             const float* __restrict__ w,
+                                                             const float* __restrict__ dy, float* __restrict__ dx,
+                                                             ConvGeo g, int L, int Lo, long long sCo, long long sCi,
+                                                             long long sK, float in_slope) {
+    const int pos = blockIdx.x * 256 + threadIdx.x, ci = blockIdx.y, u = blockIdx.z;
+    if (pos >= L) return;
+    const int Cg = g.Cin / g.groups, Mg = g.Cout / g.groups, grp = ci / Cg;
+    const float* wr = w + (long long)(ci - grp * Cg) * sCi;
+    const float* dyb = dy + ((size_t)u * g.Cout + (size_t)grp * Mg) * Lo;
+    const int v = pos + g.pad;
+    float s = 0.f;
+    for (int c = 0; c < Mg; ++c)
+        for (int tap = v % g.stride; tap < g.k && tap <= v; tap += g.stride) {
+            const int t = (v - tap) / g.stride;
+            if (t < Lo) s = fmaf(wr[(long long)(grp * Mg + c) * sCo + (long long)tap * sK], dyb[(size_t)c * Lo + t], s);
+        }
+    const size_t i = ((size_t)u * g.Cin + ci) * L + pos;
+    dx[i] = s * leaky_grad(x_pre[i], in_slope);
+}
+
+// Weight gradient partials.  grid (input-channel blocks, 16-row tiles of output
+// channels, splits).  A row tile takes the union of the input channels of the
+// groups it touches, nciB at a time; the columns of a workgroup are (input
+// channel, tap) pairs numbered c k + tap, 16 to a tile, wave w the tiles
+// w, w + 4, ...  K runs over (utterance, output position) in chunks of 64
+// positions, split z the chunks [z cps, (z + 1) cps): dy[16][64] and the input
+// window of those positions ((64 - 1) stride + k samples per channel, through
+// leaky) are staged in LDS; lane (r, q) supplies A = dy[co0 + r][t + q] and
+// B = window[c_r][(t + q) stride + tap_r].  Products of a row with a channel
+// outside its own group are not written.  part [splits, Cout, Cin/g, k].
+__global__ __launch_bounds__(256) void conv_dw_mfma_kernel(const float* __restrict__ x_pre,
+                                                           const float* __restrict__ dy, float* __restrict__ part,
+                                                           ConvGeo g, int nb, int L, int Lo, float in_slope,
+                                                           int nciB, int cps) {
+    extern __shared__ float sm[];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 15, q = lane >> 4;
+    const int Cg = g.Cin / g.groups, Mg = g.Cout / g.groups;
+    const int span = (kTc - 1) * g.stride + g.k, spanp = span | 1;
+    const int co0 = blockIdx.y * 16;
+    const int gA = co0 / Mg, gB = min(co0 + 15, g.Cout - 1) / Mg;
+    const int cb0 = blockIdx.x * nciB, U = (gB + 1 - gA) * Cg;
+    if (cb0 >= U) return;
+    const int c0 = gA * Cg + cb0, nci = min(nciB, U - cb0);
+    const int ncols = nci * g.k, ntiles = (ncols + 15) / 16;
+    float* xs = sm;
+    float* dys = sm + (size_t)nciB * spanp;
+    int off[kDwTiles];
+#pragma unroll
+    for (int i = 0; i < kDwTiles; ++i) {
+        const int n = (wave + 4 * i) * 16 + r;
+        const int c = n / g.k;
+        off[i] = n < ncols ? c * spanp + (n - c * g.k) : 0;
+    }
+    f32x4 acc[kDwTiles];
+#pragma unroll
+    for (int i = 0; i < kDwTiles; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int tcn = (Lo + kTc - 1) / kTc, total = nb * tcn;
+    const int ch1 = min(total, ((int)blockIdx.z + 1) * cps);
+    for (int ch = blockIdx.z * cps; ch < ch1; ++ch) {
+        const int b = ch / tcn, t0 = (ch - b * tcn) * kTc, nt = min(kTc, Lo - t0);
+        const float* dyb = dy + (size_t)b * g.Cout * Lo;
+        for (int i = tid; i < 16 * kTc; i += 256) {
+            const int rr = i / kTc, tt = i - rr * kTc;
+            dys[rr * (kTc + 1) + tt] = (co0 + rr < g.Cout && tt < nt) ? dyb[(size_t)(co0 + rr) * Lo + t0 + tt] : 0.f;
+        }
+        const float* xb = x_pre + ((size_t)b * g.Cin + c0) * L;
+        const long long i0 = (long long)t0 * g.stride - g.pad;
+        for (int i = tid; i < nci * span; i += 256) {
+            const int c = i / span, o = i - c * span;
+            const long long pos = i0 + o;
+            xs[c * spanp + o] = (pos >= 0 && pos < L) ? leaky(xb[(size_t)c * L + pos], in_slope) : 0.f;
+        }
+        __syncthreads();
+        for (int t4 = 0; t4 < nt; t4 += 4) {
+            const float a = dys[r * (kTc + 1) + t4 + q];
+            const float* xr = xs + (t4 + q) * g.stride;
+#pragma unroll
+            for (int i = 0; i < kDwTiles; ++i)
+                if (wave + 4 * i < ntiles) acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, xr[off[i]], acc[i], 0, 0, 0);
+        }
+        __syncthreads();
+    }
+    float* po = part + (size_t)blockIdx.z * g.Cout * Cg * g.k;
+#pragma unroll
+    for (int i = 0; i < kDwTiles; ++i) {
+        const int n = (wave + 4 * i) * 16 + r;
+        if (wave + 4 * i < ntiles && n < ncols) {
+            const int c = n / g.k, tap = n - c * g.k, ci = c0 + c, grp = ci / Cg;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int co = co0 + 4 * q + j;
+                if (co < g.Cout && co / Mg == grp) po[((size_t)co * Cg + (ci - grp * Cg)) * g.k + tap] = acc[i][j];
+            }
+        }
+    }
+}
+
+// dw[i] = (accumulate ? dw[i] : 0) + the partials of i in split order.
+__global__ __launch_bounds__(256) void dw_finish_kernel(const float* __restrict__ part, size_t n, int splits,
+                                                        int accumulate, float* __restrict__ dw) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float s = accumulate ? dw[i] : 0.f;
+    for (int k = 0; k < splits; ++k) s += part[(size_t)k * n + i];
+    dw[i] = s;
+}
+
+// Weight gradient, one workgroup per element.  grid (Cout Cin/g k).
+__global__ __launch_bounds__(NT) void conv_dw_direct_kernel(const float* __restrict__ x_pre,
+                                                            const float* __restrict__ dy, float* __restrict__ dw,
+                                                            ConvGeo g, int nb, int L, int Lo, float in_slope,
+                                                            int accumulate) {
+    __shared__ double red[NT / 64];
+    const int Cg = g.Cin / g.groups, Mg = g.Cout / g.groups;
+    const int tap = blockIdx.x % g.k, rest = blockIdx.x / g.k, cig = rest % Cg, co = rest / Cg;
+    const int ci = co / Mg * Cg + cig;
+    double s = 0.0;
+    for (int b = 0; b < nb; ++b) {
+        const float* xr = x_pre + ((size_t)b * g.Cin + ci) * L;
+        const float* dr = dy + ((size_t)b * g.Cout + co) * Lo;
+        for (int t = threadIdx.x; t < Lo; t += NT) {
+            const long long pos = (long long)t * g.stride + tap - g.pad;
+            if (pos >= 0 && pos < L) s += (double)dr[t] * (double)leaky(xr[pos], in_slope);
+        }
+    }
+    s = block_sum(s, red);
+    if (threadIdx.x == 0) dw[blockIdx.x] = (accumulate ? dw[blockIdx.x] : 0.f) + (float)s;
+}
+
+// db[co] = (accumulate ? db[co] : 0) + sum over utterances and positions of dy.  grid (Cout),
+// kDbThreads threads: few workgroups (64 on the first layer) each stream a whole channel.
+constexpr int kDbThreads = 1024;
+__global__ __launch_bounds__(kDbThreads) void conv_db_kernel(const float* __restrict__ dy, int nb, int Cout, int Lo,
+                                                             int accumulate, float* __restrict__ db) {
+    __shared__ double red[kDbThreads / 64];
+    const int co = blockIdx.x;
+    double s = 0.0;
+    for (int b = 0; b < nb; ++b) {
+        const float* dr = dy + ((size_t)b * Cout + co) * Lo;
+        for (int t = threadIdx.x; t < Lo; t += kDbThreads) s += (double)dr[t];
+    }
+    s = block_sum(s, red);
+    if (threadIdx.x == 0) db[co] = (accumulate ? db[co] : 0.f) + (float)s;
+}
+
+// Cotangent of the logits of one side under L_D: scale (D - target), in double, rounded once.
+__global__ __launch_bounds__(256) void logit_cotangent_kernel(const float* __restrict__ logits, size_t n, double target,
+                                                              double scale, float* __restrict__ dy) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) dy[i] = (float)(((double)logits[i] - target) * scale);
+}
+
 // grid (frames, B): frame t of torch.stft(center=True, pad_mode='reflect') of
 // pred and target [B, L]; part [B, frames, kSpecPart]; the spectra
 // [B, frames, N/2 + 1] are written when asked for.
@@ -465,6 +731,128 @@ int32_t run_scale(const m2_disc* d, int s, const float* x, int nb, int L, float*
         in = out[i];
     }
     return M2_OK;
+}
+
+// ---- backward ----------------------------------------------------------------------
+
+// How the weight gradient of one layer over nb utterances is computed.
+struct DwPlan {
+    bool mfma = false;
+    int nciB = 0, blocks = 0, splits = 1, cps = 0;
+    size_t lds = 0, part_floats = 0;
+};
+
+DwPlan dw_plan(const ConvGeo& g, int nb, int L) {
+    DwPlan p;
+    const int Lo = loss::conv_out_len(L, g), Cg = g.Cin / g.groups, Mg = g.Cout / g.groups;
+    const long long chunks = (long long)nb * cdiv(Lo, loss::kTc);
+    const size_t n = (size_t)g.Cout * Cg * g.k;
+    if (g.Cout < 16 || g.k > loss::kDwCols || chunks > (1 << 30)) return p;
+    int umax = 0;  // the widest union of input channels over the 16-row tiles
+    for (int co0 = 0; co0 < g.Cout; co0 += 16)
+        umax = std::max(umax, (std::min(co0 + 15, g.Cout - 1) / Mg + 1 - co0 / Mg) * Cg);
+    const size_t spanp = (size_t)(((loss::kTc - 1) * g.stride + g.k) | 1), dys = 16 * (loss::kTc + 1);
+    if ((spanp + dys) * sizeof(float) > (size_t)loss::kMaxLds) return p;
+    const size_t fit = ((size_t)loss::kMaxLds / sizeof(float) - dys) / spanp;
+    p.nciB = (int)std::min<size_t>({(size_t)(loss::kDwCols / g.k), (size_t)loss::kDwCiMax, (size_t)umax, fit});
+    p.blocks = cdiv(umax, p.nciB);
+    if (p.blocks > loss::kMaxGrid) return p;
+    p.mfma = true;
+    p.lds = ((size_t)p.nciB * spanp + dys) * sizeof(float);
+    const size_t room = 1 + loss::kPartFloats / n;
+    p.splits = (int)std::max<long long>(1, std::min<long long>({chunks, (long long)loss::kMaxSplits, (long long)room}));
+    p.part_floats = (size_t)p.splits * n;  // before the rounding below: a bound that never shrinks as nb grows
+    p.cps = (int)((chunks + p.splits - 1) / p.splits);
+    p.splits = (int)((chunks + p.cps - 1) / p.cps);
+    return p;
+}
+
+// Phases of the stride one conv_dx_mfma workgroup takes (1, 2 or 4; its other waves take row tiles).
+int dx_phases(const ConvGeo& g) { return g.stride >= 4 ? 4 : g.stride >= 2 ? 2 : 1; }
+
+bool dx_mfma_ok(const ConvGeo& g) {
+    const size_t J = (size_t)cdiv(g.k, g.stride);
+    return loss::conv_path(g) == loss::PATH_MFMA && g.Cin >= 16 &&
+           (size_t)loss::kCch * ((loss::kDxM + J - 1) | 1) * sizeof(float) <= (size_t)loss::kMaxLds &&
+           (long long)cdiv(g.stride, dx_phases(g)) * cdiv(g.Cin, 64 / dx_phases(g)) <= loss::kMaxGrid;
+}
+
+// The gradients of one layer over nb utterances: x_pre [nb, Cin, L], dy [nb, Cout, Lo];
+// dx (or null) is overwritten; dw and db (or null) are overwritten or, with
+// `accumulate`, added to.  packed: w is [k, Cin/g, Cout].  part holds dw_plan's part_floats.
+int32_t launch_conv_bwd(const float* x_pre, const float* w, const float* dy, const ConvGeo& g, int nb, int L,
+                        bool packed, float in_slope, float* dx, float* dw, float* db, bool accumulate, float* part,
+                        hipStream_t st) {
+    const int Lo = loss::conv_out_len(L, g), Cg = g.Cin / g.groups;
+    const size_t n = (size_t)g.Cout * Cg * g.k;
+    if (dx) {
+        const long long sCo = packed ? 1 : (long long)Cg * g.k, sCi = packed ? g.Cout : g.k,
+                        sK = packed ? (long long)Cg * g.Cout : 1;
+        if (dx_mfma_ok(g)) {
+            const int J = cdiv(g.k, g.stride), M = (L - 1 + g.pad) / g.stride + 1;
+            const int pw = dx_phases(g);
+            const dim3 grid(cdiv(M, loss::kDxM), cdiv(g.stride, pw) * cdiv(g.Cin, 64 / pw), nb);
+            hipLaunchKernelGGL(loss::conv_dx_mfma_kernel, grid, dim3(256),
+                               loss::kCch * ((loss::kDxM + J - 1) | 1) * sizeof(float), st, x_pre, w, dy, dx, g, L, Lo,
+                               sCo, sCi, sK, in_slope, J, pw);
+            M2_LAUNCHED("conv_dx_mfma_kernel");
+        } else {
+            hipLaunchKernelGGL(loss::conv_dx_direct_kernel, dim3(cdiv(L, 256), g.Cin, nb), dim3(256), 0, st, x_pre, w,
+                               dy, dx, g, L, Lo, sCo, sCi, sK, in_slope);
+            M2_LAUNCHED("conv_dx_direct_kernel");
+        }
+    }
+    const DwPlan p = dw_plan(g, nb, L);
+    if (p.mfma) {
+        hipLaunchKernelGGL(loss::conv_dw_mfma_kernel, dim3(p.blocks, cdiv(g.Cout, 16), p.splits), dim3(256), p.lds, st,
+                           x_pre, dy, part, g, nb, L, Lo, in_slope, p.nciB, p.cps);
+        M2_LAUNCHED("conv_dw_mfma_kernel");
+        hipLaunchKernelGGL(loss::dw_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, part, n,
+                           p.splits, accumulate ? 1 : 0, dw);
+        M2_LAUNCHED("dw_finish_kernel");
+    } else {
+        hipLaunchKernelGGL(loss::conv_dw_direct_kernel, dim3((unsigned)n), dim3(dsp::NT), 0, st, x_pre, dy, dw, g, nb,
+                           L, Lo, in_slope, accumulate ? 1 : 0);
+        M2_LAUNCHED("conv_dw_direct_kernel");
+    }
+    if (db) {
+        hipLaunchKernelGGL(loss::conv_db_kernel, dim3(g.Cout), dim3(loss::kDbThreads), 0, st, dy, nb, g.Cout, Lo,
+                           accumulate ? 1 : 0, db);
+        M2_LAUNCHED("conv_db_kernel");
+    }
+    return M2_OK;
+}
+
+// What m2_disc_step carves for a batch of B utterances of L samples, per utterance of a slice.
+struct StepPlan {
+    size_t per = 0;      // floats of the seven maps of one utterance and side
+    size_t cot = 0;      // floats of the widest map of one utterance: each of the two cotangent buffers
+    size_t pooled = 0;   // floats of the pooled audio of one utterance (scales above 1)
+    size_t part = 0;     // floats of the split-K partials
+    int nbs = 1, max_chunks = 1;
+};
+
+StepPlan step_plan(const m2_disc* d, int B, int L) {
+    StepPlan p;
+    p.per = disc_floats_max(d, L);
+    for (int s = 0; s < d->n_scales; ++s) {
+        int len[kLayers];
+        if (!disc_lengths(L, d->scales[s], len)) continue;
+        for (int i = 0; i < kLayers; ++i) p.cot = std::max(p.cot, align_up((size_t)kDisc[i].Cout * len[i], 64));
+        if (d->scales[s] > 1) p.pooled = std::max(p.pooled, align_up((size_t)(L / d->scales[s]), 64));
+    }
+    p.nbs = slice_of(d, p.per, 2, B);  // m2_disc_losses's slices: the bound counts the maps of both sides
+    p.max_chunks = cdiv((int)std::min<size_t>(p.per, (size_t)1 << 30), loss::kRedChunk) + 1;
+    for (int s = 0; s < d->n_scales; ++s) {
+        int l = L / d->scales[s];
+        if (l < 1) continue;
+        // the last slice may be shorter, and fewer utterances never take more partials
+        for (int i = 0; i < kLayers; ++i) {
+            p.part = std::max(p.part, dw_plan(kDisc[i], p.nbs, l).part_floats);
+            l = loss::conv_out_len(l, kDisc[i]);
+        }
+    }
+    return p;
 }
 
 bool disc_shape_ok(const m2_disc* d, int B, int L) {
@@ -718,6 +1106,129 @@ int32_t m2_disc_losses(const m2_disc* d, const float* real, const float* fake, i
             hipLaunchKernelGGL(loss::reduce_finish_kernel, dim3(nb), dim3(dsp::NT), 0, st, part, maps, max_chunks,
                                out + (size_t)b0 * loss::kDiscK + (size_t)s * loss::kDiscScaleK, loss::kDiscK);
             M2_LAUNCHED("reduce_finish_kernel");
+        }
+    }
+    return M2_OK;
+}
+
+size_t m2_conv1d_strided_backward_workspace_bytes(int32_t ksize, int32_t stride, int32_t padding, int32_t groups,
+                                                  int32_t B, int32_t Cin, int32_t Cout, int32_t L) {
+    const ConvGeo g{Cin, Cout, ksize, stride, padding, groups};
+    if (B <= 0 || L <= 0 || Cin <= 0 || Cout <= 0 || ksize <= 0 || stride <= 0 || padding < 0 || groups <= 0 ||
+        !geo_ok(g) || (long long)L + 2LL * padding < ksize)
+        return 0;
+    return dw_plan(g, B, L).part_floats * sizeof(float) + 256;
+}
+
+int32_t m2_conv1d_strided_backward(const float* x_pre, const float* w, const float* dy, int32_t ksize, int32_t stride,
+                                   int32_t padding, int32_t groups, float in_slope, int32_t B, int32_t Cin,
+                                   int32_t Cout, int32_t L, float* dx, float* dw, float* db, void* workspace,
+                                   size_t workspace_bytes, void* stream) {
+    const ConvGeo g{Cin, Cout, ksize, stride, padding, groups};
+    M2_CHECK_ARG(x_pre && w && dy && dw && B >= 0 && L > 0 && Cin > 0 && Cout > 0 && ksize > 0 && stride > 0 &&
+                     padding >= 0 && groups > 0,
+                 "m2_conv1d_strided_backward: bad argument");
+    M2_CHECK_SHAPE(geo_ok(g), "m2_conv1d_strided_backward: groups must divide both channel counts");
+    M2_CHECK_SHAPE((long long)L + 2LL * padding >= ksize,
+                   "m2_conv1d_strided_backward: kernel wider than the padded input");
+    M2_CHECK_SHAPE(B <= loss::kMaxGrid && Cout <= loss::kMaxGrid && Cin <= loss::kMaxGrid && L <= (1 << 28) &&
+                       ksize <= (1 << 16) && stride <= (1 << 16) && padding <= (1 << 28) &&
+                       (long long)Cout * (Cin / groups) * ksize < (1LL << 31),
+                   "m2_conv1d_strided_backward: at most 65535 utterances and channels, 2^28 samples and padding, "
+                   "2^16 taps and stride, 2^31 weights");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (B == 0) {  // empty sums
+        M2_HIP(hipMemsetAsync(dw, 0, (size_t)Cout * (Cin / groups) * ksize * sizeof(float), st));
+        if (db) M2_HIP(hipMemsetAsync(db, 0, (size_t)Cout * sizeof(float), st));
+        return M2_OK;
+    }
+    Carve c(workspace, workspace_bytes);
+    const size_t pf = dw_plan(g, B, L).part_floats;
+    float* part = pf ? c.take<float>(pf) : nullptr;
+    if (!c.ok) return fail(M2_E_WORKSPACE, "m2_conv1d_strided_backward: workspace too small");
+    return launch_conv_bwd(x_pre, w, dy, g, B, L, false, in_slope, dx, dw, db, false, part, st);
+}
+
+size_t m2_disc_step_workspace_bytes(const m2_disc* d, int32_t B, int32_t L) {
+    if (!d || B < 0 || L <= 0) return 0;
+    const StepPlan p = step_plan(d, B, L);
+    return (size_t)p.nbs * (2 * p.per + 2 * p.cot + p.pooled) * sizeof(float) + p.part * sizeof(float) +
+           (size_t)p.nbs * kLayers * p.max_chunks * loss::kRedPart * sizeof(double) + 256 * 8;
+}
+
+int32_t m2_disc_step(const m2_disc* d, const float* real, const float* fake, int32_t B, int32_t L, double* out,
+                     float* const* grads, void* workspace, size_t workspace_bytes, void* stream) {
+    M2_CHECK_ARG(d && real && fake && out && grads && B >= 0 && L > 0, "m2_disc_step: bad argument");
+    for (int i = 0; i < d->n_scales * 2 * kLayers; ++i) M2_CHECK_ARG(grads[i], "m2_disc_step: null gradient");
+    M2_CHECK_SHAPE(d->n_scales == loss::kDiscScales, "m2_disc_step: the rows are laid out for three scales");
+    M2_CHECK_SHAPE(disc_shape_ok(d, B, L),
+                   "m2_disc_step: at most 65535 utterances of 2^28 samples, no shorter than the largest scale");
+    if (B == 0) return M2_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const StepPlan pl = step_plan(d, B, L);
+    const int nbs = pl.nbs;
+    Carve c(workspace, workspace_bytes);
+    float* act[2] = {c.take<float>((size_t)nbs * pl.per), c.take<float>((size_t)nbs * pl.per)};
+    double* dpart = c.take<double>((size_t)nbs * kLayers * pl.max_chunks * loss::kRedPart);
+    float* cot[2] = {c.take<float>((size_t)nbs * pl.cot), c.take<float>((size_t)nbs * pl.cot)};
+    float* pooled = pl.pooled ? c.take<float>((size_t)nbs * pl.pooled) : nullptr;
+    float* part = pl.part ? c.take<float>(pl.part) : nullptr;
+    if (!c.ok) return fail(M2_E_WORKSPACE, "m2_disc_step: workspace too small");
+    for (int b0 = 0; b0 < B; b0 += nbs) {
+        const int nb = std::min(nbs, B - b0);
+        for (int s = 0; s < d->n_scales; ++s) {
+            int len[kLayers];
+            disc_lengths(L, d->scales[s], len);
+            // the forward half: m2_disc_losses's launches
+            loss::RedMaps maps;
+            float* map[2][kLayers];
+            int chunks = 1;
+            for (int side = 0; side < 2; ++side) {
+                float* p = act[side];
+                for (int i = 0; i < kLayers; ++i) {
+                    const size_t n = (size_t)kDisc[i].Cout * len[i];
+                    map[side][i] = p;
+                    (side ? maps.fake : maps.real)[i] = p;
+                    maps.n[i] = (long long)n;
+                    chunks = std::max(chunks, cdiv((int)n, loss::kRedChunk));
+                    p += align_up(n, 64) * nb;
+                }
+                const int32_t rc = run_scale(d, s, (side ? fake : real) + (size_t)b0 * L, nb, L, map[side], st);
+                if (rc != M2_OK) return rc;
+            }
+            hipLaunchKernelGGL(loss::reduce_part_kernel, dim3(chunks, kLayers, nb), dim3(dsp::NT), 0, st, maps,
+                               pl.max_chunks, dpart);
+            M2_LAUNCHED("reduce_part_kernel");
+            hipLaunchKernelGGL(loss::reduce_finish_kernel, dim3(nb), dim3(dsp::NT), 0, st, dpart, maps, pl.max_chunks,
+                               out + (size_t)b0 * loss::kDiscK + (size_t)s * loss::kDiscScaleK, loss::kDiscK);
+            M2_LAUNCHED("reduce_finish_kernel");
+            // the backward half, side by side, while the maps are resident
+            const int Lp = L / d->scales[s];
+            const double cscale = 2.0 / ((double)B * (double)len[kLayers - 1] * (double)d->n_scales);
+            for (int side = 0; side < 2; ++side) {
+                const float* x = (side ? fake : real) + (size_t)b0 * L;
+                if (d->scales[s] > 1) {
+                    hipLaunchKernelGGL(loss::avg_pool_kernel, dim3(cdiv(Lp, 256), nb), dim3(256), 0, st, x, L,
+                                       d->scales[s], Lp, pooled);
+                    M2_LAUNCHED("avg_pool_kernel");
+                    x = pooled;
+                }
+                const size_t nl = (size_t)nb * len[kLayers - 1];
+                hipLaunchKernelGGL(loss::logit_cotangent_kernel, dim3((unsigned)((nl + 255) / 256)), dim3(256), 0, st,
+                                   map[side][kLayers - 1], nl, side ? 0.0 : 1.0, cscale, cot[0]);
+                M2_LAUNCHED("logit_cotangent_kernel");
+                const bool accumulate = b0 > 0 || side > 0;
+                int cur = 0;
+                for (int i = kLayers - 1; i >= 0; --i) {
+                    float* const* gp = grads + ((size_t)s * kLayers + i) * 2;
+                    const int32_t rc = launch_conv_bwd(
+                        i > 0 ? map[side][i - 1] : x, d->w[s][i], cot[cur], kDisc[i], nb, i > 0 ? len[i - 1] : Lp,
+                        loss::conv_path(kDisc[i]) == loss::PATH_MFMA, i > 0 ? loss::kDiscSlope : 1.f,
+                        i > 0 ? cot[cur ^ 1] : nullptr, gp[0], gp[1], accumulate, part, st);
+                    if (rc != M2_OK) return rc;
+                    cur ^= 1;
+                }
+            }
         }
     }
     return M2_OK;

@@ -108,6 +108,11 @@ _SIGNATURES = {
     "m2_disc_forward": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_size, c_vp]),
     "m2_disc_losses_workspace_bytes": (c_size, [c_vp, c_i32, c_i32]),
     "m2_disc_losses": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_size, c_vp]),
+    "m2_conv1d_strided_backward_workspace_bytes": (c_size, [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32]),
+    "m2_conv1d_strided_backward": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_i32, c_i32, c_i32,
+                                           c_i32, c_vp, c_vp, c_vp, c_vp, c_size, c_vp]),
+    "m2_disc_step_workspace_bytes": (c_size, [c_vp, c_i32, c_i32]),
+    "m2_disc_step": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_size, c_vp]),
     "m2_loss_spectral_workspace_bytes": (c_size, [c_vp, c_i32, c_i32]),
     "m2_loss_spectral": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_size, c_vp]),
     "m2_front_bytes": (c_size, [c_vp, c_i32, c_i32]),

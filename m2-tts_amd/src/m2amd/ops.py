@@ -139,6 +139,33 @@ def conv1d_strided(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None, *, 
     return y
 
 
+def conv1d_strided_backward(x_pre: Tensor, weight: Tensor, dy: Tensor, *, stride: int = 1, padding: int = 0,
+                            groups: int = 1, in_slope: float = 1.0, need_dx: bool = True, need_db: bool = True):
+    """The gradients of y = F.conv1d(F.leaky_relu(x_pre, in_slope), weight, bias, stride, padding, groups=groups)
+    given dy, the cotangent of y (m2_conv1d_strided_backward): (dx [B,Cin,L] or None, dw like weight, db [Cout]
+    or None), dw and db summed over the batch."""
+    require_device(x_pre, weight, dy, what="conv1d_strided_backward")
+    x_pre, dy, weight = f32c(x_pre), f32c(dy), f32c(weight)
+    B, Cin, L = x_pre.shape
+    Cout, Cg, K = weight.shape
+    if groups < 1 or Cin % groups or Cout % groups or Cg * groups != Cin:
+        raise ValueError(f"conv1d_strided_backward: weight {tuple(weight.shape)} and groups {groups} do not fit "
+                         f"x_pre {tuple(x_pre.shape)}")
+    Lo = (L + 2 * padding - K) // stride + 1
+    if tuple(dy.shape) != (B, Cout, Lo):
+        raise ValueError(f"conv1d_strided_backward: dy {tuple(dy.shape)} must be {(B, Cout, Lo)}")
+    dev = x_pre.device
+    dx = torch.empty_like(x_pre) if need_dx else None
+    dw = torch.empty_like(weight)
+    db = torch.empty(Cout, device=dev, dtype=torch.float32) if need_db else None
+    geo = (K, int(stride), int(padding), int(groups))
+    need = int(_lib.load().m2_conv1d_strided_backward_workspace_bytes(*geo, B, Cin, Cout, L))
+    ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+    _lib.call("m2_conv1d_strided_backward", _ptr(x_pre), _ptr(weight), _ptr(dy), *geo, float(in_slope), B, Cin, Cout, L,
+              _ptr(dx), _ptr(dw), _ptr(db), _ptr(ws), ws.numel(), stream_handle(dev))
+    return dx, dw, db
+
+
 def avg_pool1d(x: Tensor, kernel_size: int) -> Tensor:
     """F.avg_pool1d(x [B,C,L], k, stride=k) -> [B,C,L//k] (m2_avg_pool1d)."""
     require_device(x, what="avg_pool1d")
@@ -258,6 +285,29 @@ class Discriminators:
         _lib.call("m2_disc_losses", self.handle, _ptr(real), _ptr(fake), B, L, _ptr(out), _ptr(ws), ws.numel(),
                   stream_handle(ref.device))
         return out
+
+    def step(self, real: Tensor, fake: Tensor):
+        """The discriminator step (m2_disc_step): ``losses(real, fake)``'s rows, bit for bit, and the
+        gradient of L_D = mean over scales of [mean (D(real) - 1)^2 + mean D(fake)^2] with respect to
+        every weight and bias: new float32 tensors in state_dict order, shaped like the parameters."""
+        real, fake = self._audio(real), self._audio(fake)
+        if real.shape != fake.shape:
+            raise ValueError(f"discriminator: real {tuple(real.shape)} and fake {tuple(fake.shape)} differ")
+        B, _, L = real.shape
+        lib = _lib.load()
+        dev = real.device
+        out = torch.zeros(B, lib.m2_loss_column_count(1), device=dev, dtype=torch.float64)
+        grads = []
+        for _ in self.scales:
+            for cin, cout, k, _, _, groups in self.LAYER_TABLE:
+                grads.append(torch.zeros(cout, cin // groups, k, device=dev, dtype=torch.float32))
+                grads.append(torch.zeros(cout, device=dev, dtype=torch.float32))
+        ptrs = (ctypes.c_void_p * len(grads))(*[g.data_ptr() for g in grads])
+        need = int(lib.m2_disc_step_workspace_bytes(self.handle, B, L))
+        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+        _lib.call("m2_disc_step", self.handle, _ptr(real), _ptr(fake), B, L, _ptr(out), ptrs, _ptr(ws), ws.numel(),
+                  stream_handle(dev))
+        return out, grads
 
 
 def embed_positional(ids: Tensor, emb: Tensor, pe: Tensor, scale: float) -> Tensor:

@@ -8,11 +8,31 @@ m2amd.dsp), which write per-utterance rows of double sums; a few torch ops on
 the device turn those rows into the reference's means, so a call needs no host
 synchronisation.
 
-**Forward values only.**  Every returned value is a 0-dim float32 tensor on the
-inputs' device with ``requires_grad=False``: the values carry no autograd
-graph, the same contract M2TTSModel.forward has in this tree.  They score a
-checkpoint with the objective it was trained on; ``backward()`` through them
-is not available, and the trainers are not part of this package.
+**Values, and one gradient.**  By default every returned value is a 0-dim
+float32 tensor on the inputs' device with ``requires_grad=False``: the values
+carry no autograd graph, the same contract M2TTSModel.forward has in this
+tree, and score a checkpoint with the objective it was trained on.
+
+The discriminator step of the reference's stage-2 trainer is available on
+request: after ``CombinedTTSLoss.enable_backward()`` (or
+``AdversarialLoss.enable_backward()``), with gradients enabled and at least
+one discriminator parameter requiring grad,
+``AdversarialLoss.discriminator_loss(real, fake)`` and the
+``discriminator_loss`` and ``total_loss`` entries of
+``CombinedTTSLoss.forward(..., optimize_discriminator=True)`` carry a
+``grad_fn``: one ``torch.autograd.Function`` whose forward runs m2_disc_step
+(the same values, bit for bit, and the gradients of all 42 parameters) and
+whose backward hands those gradients out scaled by ``grad_output``, on the
+device.  So ``optimizer_d.zero_grad(); loss(...)['total_loss'].backward();
+clip_grad_norm_(...); optimizer_d.step()`` works as in the reference.  The
+backward is once-differentiable, the audio inputs get no gradient (the
+reference detaches the fake audio there), and parameters with
+``requires_grad=False`` get ``None``.  Every other entry stays graph-free
+with the switch on or off: ``mel_loss``, ``duration_loss``, ``spectral_loss``,
+``perceptual_loss``, ``generator_loss``, ``feature_matching_loss`` and the
+generator-mode ``total_loss``; ``backward()`` through them is not available,
+nor is autograd through ``MultiScaleDiscriminator.forward``, and the trainers
+are not part of this package.
 
 The discriminators' parameters live in plain ``nn.Conv1d`` modules built in the
 reference's order, so ``torch.manual_seed(s); CombinedTTSLoss()`` gives the
@@ -98,8 +118,27 @@ class SpectralLoss(nn.Module):
             return self._value(p, t, None).float()
 
 
+class _DiscriminatorStep(torch.autograd.Function):
+    """The discriminator loss with the gradients of the discriminators' parameters, both from one
+    m2_disc_step call in forward; backward scales the kept gradients by grad_output."""
+
+    @staticmethod
+    def forward(ctx, disc, real, fake, *params):
+        rows, grads = disc._handle(real.device).step(real, fake)
+        ctx.grads = grads
+        return disc._discriminator_value(disc._columns(rows.sum(0))).float()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        return (None, None, None) + tuple(grad_output * g if need else None
+                                          for g, need in zip(ctx.grads, ctx.needs_input_grad[3:]))
+
+
 class MultiScaleDiscriminator(nn.Module):
     """Multi-scale discriminator: seven Conv1d per scale, scale i on avg_pool1d(x, scales[i])."""
+
+    backward_enabled = False  # set by enable_backward(); a plain attribute, not in the state_dict
 
     def __init__(self, scales=[1, 2, 4]):
         super().__init__()
@@ -148,17 +187,43 @@ class MultiScaleDiscriminator(nn.Module):
         with torch.no_grad():
             return self._handle(x.device).forward(x, features=True)
 
+    @staticmethod
+    def _columns(sums: Tensor) -> Dict[str, Tensor]:
+        from m2amd.dsp import loss_columns
+        return {name: sums[i] for i, name in enumerate(loss_columns("disc"))}
+
     def _sums(self, real: Optional[Tensor], fake: Optional[Tensor]) -> Dict[str, Tensor]:
         """Batch sums (0-dim float64) of the m2_disc_losses columns."""
-        from m2amd.dsp import loss_columns
         ref = real if real is not None else fake
         _require(real, fake, what="AdversarialLoss")
-        sums = self._handle(ref.device).losses(real, fake).sum(0)
-        return {name: sums[i] for i, name in enumerate(loss_columns("disc"))}
+        return self._columns(self._handle(ref.device).losses(real, fake).sum(0))
+
+    def _discriminator_value(self, c: Dict[str, Tensor]) -> Tensor:
+        """mean over scales of [mean (D(real) - 1)^2 + mean D(fake)^2], float64."""
+        n = len(self.scales)
+        real = sum(c[f"s{s}_real_err_sq"] / c[f"s{s}_logits"] for s in range(n))
+        fake = sum(c[f"s{s}_fake_sq"] / c[f"s{s}_logits"] for s in range(n))
+        return (real + fake) / n
+
+    def enable_backward(self, enabled: bool = True):
+        """Let the discriminator loss carry the gradients of this module's parameters (module docstring)."""
+        self.backward_enabled = bool(enabled)
+        return self
+
+    def _wants_backward(self) -> bool:
+        return self.backward_enabled and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+
+    def _step_loss(self, real: Tensor, fake: Tensor) -> Tensor:
+        """The discriminator loss (0-dim float32) with a grad_fn that reaches the parameters."""
+        _require(real, fake, what="AdversarialLoss")
+        with torch.enable_grad():
+            return _DiscriminatorStep.apply(self, real.detach(), fake.detach(),
+                                            *self.state_dict(keep_vars=True).values())
 
 
 class AdversarialLoss(nn.Module):
-    """GAN-based adversarial loss (least squares), values only."""
+    """GAN-based adversarial loss (least squares); values, and after enable_backward() the
+    discriminator loss's gradient with respect to the discriminators' parameters."""
 
     def __init__(self):
         super().__init__()
@@ -176,10 +241,16 @@ class AdversarialLoss(nn.Module):
         total = sum(c[f"s{s}_l{j}_abs_diff"] / c[f"s{s}_l{j}_count"] for s in range(n) for j in range(layers))
         return total / (n * layers)
 
+    def enable_backward(self, enabled: bool = True):
+        """Switch the gradient of discriminator_loss on or off (module docstring)."""
+        self.discriminator.enable_backward(enabled)
+        return self
+
     def discriminator_loss(self, real_audio, fake_audio):
+        if self.discriminator._wants_backward():
+            return self.discriminator._step_loss(real_audio, fake_audio)
         with torch.no_grad():
-            c = self.discriminator._sums(real_audio, fake_audio)
-            return ((self._mse(c, "real_err_sq") + self._mse(c, "fake_sq")) / len(self.discriminator.scales)).float()
+            return self.discriminator._discriminator_value(self.discriminator._sums(real_audio, fake_audio)).float()
 
     def generator_loss(self, fake_audio):
         with torch.no_grad():
@@ -234,7 +305,8 @@ class PerceptualLoss(nn.Module):
 
 
 class CombinedTTSLoss(nn.Module):
-    """Combined loss of stage 2 TTS training, values only (see the module docstring)."""
+    """Combined loss of stage 2 TTS training: values, and after enable_backward() the gradient of
+    the discriminator step (see the module docstring)."""
 
     def __init__(
         self,
@@ -261,6 +333,12 @@ class CombinedTTSLoss(nn.Module):
         else:
             self.adversarial_loss = None
         self.training_step = 0
+
+    def enable_backward(self, enabled: bool = True):
+        """Switch the gradient of the discriminator step on or off (module docstring)."""
+        if self.adversarial_loss is not None:
+            self.adversarial_loss.enable_backward(enabled)
+        return self
 
     @staticmethod
     def _mel_loss(mel_pred: Tensor, mel_target: Tensor, mel_lengths) -> Tensor:
@@ -313,10 +391,13 @@ class CombinedTTSLoss(nn.Module):
             optimize_discriminator: compute the discriminator loss instead of the generator's
 
         Returns:
-            the loss components by name, 0-dim float32 tensors without a graph
+            the loss components by name, 0-dim float32 tensors; without a graph, except the
+            discriminator_loss and total_loss of a discriminator step after enable_backward()
         """
         _require(mel_pred, mel_target, duration_pred, duration_target, audio_pred, audio_target,
                  what="CombinedTTSLoss")
+        step = optimize_discriminator and self.adversarial_loss is not None and \
+            self.adversarial_loss.discriminator._wants_backward()
         with torch.no_grad():
             v: Dict[str, Tensor] = {}  # float64 on the device
             v["mel_loss"] = self._mel_loss(mel_pred, mel_target, mel_lengths)
@@ -329,10 +410,11 @@ class CombinedTTSLoss(nn.Module):
                 if self.adversarial_loss is not None:
                     adv = self.adversarial_loss
                     real, fake = t.unsqueeze(1), p.unsqueeze(1)
-                    if optimize_discriminator:
-                        c = adv.discriminator._sums(real, fake)
-                        v["discriminator_loss"] = (adv._mse(c, "real_err_sq") + adv._mse(c, "fake_sq")) / \
-                            len(adv.discriminator.scales)
+                    if step:
+                        v["discriminator_loss"] = adv.discriminator._step_loss(real, fake)  # float32, with a grad_fn
+                    elif optimize_discriminator:
+                        v["discriminator_loss"] = adv.discriminator._discriminator_value(
+                            adv.discriminator._sums(real, fake))
                     else:
                         # one pass over each signal serves both terms (the reference runs fake twice)
                         c = adv.discriminator._sums(real, fake)

@@ -7,8 +7,14 @@ Prints one JSON line: milliseconds per CombinedTTSLoss call in generator and in
 discriminator mode, per spectral / discriminator part, and for the two heaviest
 packed layers of scale 1 (the grouped 64 -> 128 k = 41 stride-4 layer and the
 dense 1024 -> 1024 k = 5 layer) their time and FLOP/time as a fraction of the
-fp32 MFMA peak (157.3 TFLOP/s).  Each figure is the median of --iters timed
-calls after --warmup untimed ones.
+fp32 MFMA peak (157.3 TFLOP/s).  The discriminator step (enable_backward():
+the discriminator loss forward and backward, m2_disc_step) is timed as
+discriminator_loss(...).backward() against the forward-only discriminator_loss
+call of the same process (step_over_forward), and the two MFMA gradients of the
+same two layers on their own: the weight gradient (its split-K kernel and the
+fixed-order finish), and the data gradient as the difference between a call
+that computes both and one that computes the weight gradient alone.  Each
+figure is the median of --iters timed calls after --warmup untimed ones.
 """
 import argparse
 import json
@@ -69,6 +75,21 @@ def main():
     disc = loss.adversarial_loss.discriminator
     out["discriminator_sums_ms"] = timed(lambda: disc._sums(kw["audio_target"], kw["audio_pred"]), args.warmup,
                                          args.iters)
+    adv = loss.adversarial_loss
+    real, fake = kw["audio_target"], kw["audio_pred"]
+    out["discriminator_loss_forward_ms"] = timed(lambda: adv.discriminator_loss(real, fake), args.warmup, args.iters)
+    loss.enable_backward()
+
+    def step():
+        for p in disc.parameters():
+            p.grad = None
+        adv.discriminator_loss(real, fake).backward()
+
+    out["discriminator_step_ms"] = timed(step, args.warmup, args.iters)
+    loss.enable_backward(False)
+    for p in disc.parameters():
+        p.grad = None
+    out["step_over_forward"] = out["discriminator_step_ms"] / out["discriminator_loss_forward_ms"]
     h = disc._handle(dev)
     shapes = h.shapes(L)[0]
     for name, layer in (("grouped_64_128_k41", 1), ("dense_1024_1024_k5", 5)):
@@ -77,6 +98,15 @@ def main():
         ms = timed(lambda: h.layer(0, layer, x), args.warmup, args.iters)
         flop = 2.0 * cout * (cin // groups) * k * shapes[layer][1] * B
         out[name] = {"ms": ms, "gflop": flop / 1e9, "fraction_of_f32_mfma_peak": flop / (ms * 1e-3) / PEAK_F32_MFMA}
+        from m2amd import ops
+        _, _, _, stride, pad, _ = h.LAYER_TABLE[layer]
+        w = torch.randn(cout, cin // groups, k, device=dev)
+        dy = torch.randn(B, cout, shapes[layer][1], device=dev)
+        geo = dict(stride=stride, padding=pad, groups=groups, in_slope=0.2, need_db=False)
+        dw_ms = timed(lambda: ops.conv1d_strided_backward(x, w, dy, need_dx=False, **geo), args.warmup, args.iters)
+        both_ms = timed(lambda: ops.conv1d_strided_backward(x, w, dy, need_dx=True, **geo), args.warmup, args.iters)
+        for key, t in (("weight_gradient", dw_ms), ("data_gradient", both_ms - dw_ms)):
+            out[name][key] = {"ms": t, "fraction_of_f32_mfma_peak": flop / (t * 1e-3) / PEAK_F32_MFMA}
     print(json.dumps(out))
 
 
