@@ -89,6 +89,8 @@ void reload_switches() {
     s.tailp2_nch = env_int("M2_TAILP2_NCH", 0);
     s.tailp2_seven = env_set("M2_TAILP2_SEVEN");
     s.head_inconv = env_set("M2_HEAD_INCONV");
+    // "0" or "1"; anything else keeps the default (m2amd.runtime.headmid_switch rejects it at handle creation)
+    if (const char* e = std::getenv("M2_HEADMID"); e && (e[0] == '0' || e[0] == '1') && !e[1]) s.headmid = e[0] == '1';
     const int malt = env_int("M2_S2_MID_ALT", -1);
     s.s2_mid_alt = (malt == 0 || malt == 1) ? malt : -1;
     const int htf = env_int("M2_S2_HEAD_TF", env_set("M2_S2_HEAD_TF16") ? 16 : 0);
@@ -913,6 +915,7 @@ int32_t vocoder_run(const m2_model* m, const float* mel, int32_t mel_layout, int
         VocW vw = m->vw;
         vx.dT = vw.dT = dT;
         vx.head_prio = sw().x3_head_prio;
+        vx.prof_slots = rec ? m->prof_mask : 0u;
         if (x3 && redo >= 0) {
             vx.rflag = m->rflag_dev + redo;
             vx.rclear = m->rflag_dev + (redo ^ 1);

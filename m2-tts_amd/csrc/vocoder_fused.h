@@ -146,6 +146,9 @@ struct VocX {
     // waves of each SIMD higher; measured level at stage1 B=32 in both
     // orders, profiles/r06/r06z16_head_prio.txt: an A/B switch only)
     int head_prio = 0;
+    // the kernels (bits 0..2: head, mid, tail) this call records events
+    // around: with bit 0 or 1 set the head and the mid stay two launches
+    unsigned prof_slots = 0;
     // device frame count (dev_frames): when set, the T passed to the launches
     // is the capacity their grids cover
     const int32_t* dT = nullptr;

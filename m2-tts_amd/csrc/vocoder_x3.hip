@@ -32,10 +32,12 @@
 #include <cstdlib>
 #include <cstring>
 #include <type_traits>
+#include <atomic>
 #include <functional>
 
 #include "m2_common.h"
 #include "vocoder_fused.h"
+#include "vocoder_midp.h"
 
 namespace m2 {
 namespace x3 {
@@ -642,13 +644,17 @@ __device__ __forceinline__ void head_edge_terms(const float4 (&ev)[4], float eb,
 template <int MP, int COUT, int RSM, int RSO>
 __device__ __forceinline__ void head_convT1c_planar(const u32x4* __restrict__ Wp, const float* __restrict__ bias,
                                                     const unsigned char* corr, XW mel, unsigned char* u, int f0,
-                                                    int T, APipe* ap, const u32x4* wp_next) {
+                                                    int T, APipe* ap, const u32x4* wp_next, int rot = 0) {
     constexpr int MB = COUT / 16, NKB = nkb_of<MP, 4>(), NT = 4;
     static_assert(NKB == 8 && pd_of<MP, 4, 1>() == 4, "the ConvT1 weight pipeline shape");
     const int item = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int ph = item / MB, mb = item - ph * MB;
+    const int pv = item / MB, mb = item - pv * MB;
+    // rot (headmid_kernel): the window starts at position 4 f0 + rot, so plane
+    // pv holds output phase (pv + rot) mod 4 of the columns one further on
+    // where pv + rot wraps; the arithmetic of a position is the same
+    const int ph = (pv + rot) & 3;
     const int lane = threadIdx.x & 63, li = lane & 15, g = lane >> 4, co0 = mb * 16 + 4 * g;
-    const int qs = qs_u(ph, f0), d0 = ph < 2 ? 0 : 1;  // taps: mel frames q + d0 + 1 - k
+    const int qs = qs_u(pv, f0) + ((pv + rot) >> 2), d0 = ph < 2 ? 0 : 1;  // taps: mel frames q + d0 + 1 - k
     const u32x4* wp = Wp + (size_t)(ph * MB + mb) * NKB * 128 + lane;
     const unsigned char* bp = mel.p + (qs + li + d0 + 1 - mel.start) * RSM;
     f32x4 acc[1][NT];
@@ -669,7 +675,7 @@ __device__ __forceinline__ void head_convT1c_planar(const u32x4* __restrict__ Wp
                 for (int r = 0; r < 4; ++r) acc[0][n][r] -= c[r];
             }
         }
-        store_row<COUT, ACT_LEAKY, false, false>(acc[0][n], u + (ph * kPlane + 16 * n + li) * RSO, nullptr, co0,
+        store_row<COUT, ACT_LEAKY, false, false>(acc[0][n], u + (pv * kPlane + 16 * n + li) * RSO, nullptr, co0,
                                                  t < 0 || t >= L, true, nullptr, t, plane_sw(li));
     }
 }
@@ -677,13 +683,18 @@ __device__ __forceinline__ void head_convT1c_planar(const u32x4* __restrict__ Wp
 // ResBlock1 conv (k3, pad 1) between planes: input planes start at qsi(p),
 // output plane p covers q in [qso(p), +64).  CONV2: + x from the u planes,
 // stored straight to U1 (t < L and q < f0 + tf only); else leaky into the
-// h planes (0 outside [0, L)).
-template <int C, int RS, bool CONV2>
+// h planes (0 outside [0, L)).  INPL (headmid_kernel): conv2 + x goes back
+// into the u planes instead, 0 outside [0, L): each lane reads the residual
+// of its four channels before the permlane16 swap and writes, after it, 16 B
+// of the same row and m-block, which only this wave touches.  rot: plane p
+// holds positions 4 q + p + rot (head_convT1c_planar).
+template <int C, int RS, bool CONV2, bool INPL = false>
 __device__ __forceinline__ void head_rb1_planar(const u32x4* __restrict__ Wp, const float* __restrict__ bias,
                                                 const unsigned char* in, unsigned char* out,
                                                 const unsigned char* x, int f0, int tf, int L, APipe* ap,
-                                                const u32x4* wp_next, unsigned char* gout) {
+                                                const u32x4* wp_next, unsigned char* gout, int rot = 0) {
     constexpr int MB = C / 16, NKB = nkb_of<C, 3>(), NT = 4;
+    static_assert(CONV2 || !INPL, "in place: conv2 only");
     const int item = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int p = item / MB, mb = item - p * MB;
     const int lane = threadIdx.x & 63, li = lane & 15, g = lane >> 4, co0 = mb * 16 + 4 * g;
@@ -706,8 +717,13 @@ __device__ __forceinline__ void head_rb1_planar(const u32x4* __restrict__ Wp, co
     mma_x3<C, 3, 1, RS, NT, false, 1, NKB * 128, true, true>(wp, nullptr, nullptr, acc, *ap, wp_next, tb);
 #pragma unroll
     for (int n = 0; n < NT; ++n) {
-        const int q = qo + 16 * n + li, t = 4 * q + p;
-        if constexpr (CONV2) {
+        const int q = qo + 16 * n + li, t = 4 * q + p + rot;
+        if constexpr (INPL) {
+            const int xr = q - qs_u(p, f0);
+            unsigned char* xrow = const_cast<unsigned char*>(x) + (p * kPlane + xr) * RS;
+            store_row<C, ACT_NONE, true, false>(acc[0][n], xrow, xrow, co0, t < 0 || t >= L, q < f0 + tf, nullptr, t,
+                                                plane_sw(xr), plane_sw(xr));
+        } else if constexpr (CONV2) {
             const int xr = q - qs_u(p, f0);
             store_row<C, ACT_NONE, true, true>(acc[0][n], nullptr, x + (p * kPlane + xr) * RS, co0, false,
                                                q < f0 + tf && t < L, gout, t, 0, plane_sw(xr));
@@ -1280,6 +1296,170 @@ __global__ __launch_bounds__(Cfg::HW * 64, Cfg::HMIN) void x3_head_kernel(const 
     XSTAMP(0, 11);
 }
 
+// ---------------------------------------------------------------------------
+// headmid_kernel (stage1): the composed planar head and the pipelined mid
+// stage (vocoder_midp.h) in one launch, U1 handed over in LDS.
+//
+// The mid's true dependency on U1 is +-1 column, and the head's planes give
+// 4 TF = 252 valid U1 positions (256 u positions less two k3 convs), so a
+// workgroup owns a strip of S <= 250 columns [qa, qa + S) and its window is
+// the 252 positions from qa - 1.  qa - 1 is no multiple of 4 in general: the
+// window starts at 4 f0 + rot and the head's planes are rotated by rot
+// (head_convT1c_planar).  ResBlock1's conv2 writes U1 back into the u planes
+// (0 outside the utterance, which is what the mid's loader delivers for such
+// columns); after one barrier region A - the mel window, then the h planes -
+// is dead and holds the mid's rings R1 and R2, and the mid's layer 0 reads the
+// planes where midp_kernel reads ring R0.  No loader wave, no U1 in global
+// memory, one launch boundary less.  Every output keeps its operation
+// sequence: U2 is bit-identical to the two launches'.
+// The mid's roles take 12 of the 16 waves (HEADMID_T2W 8: ConvT2 on eight
+// waves, one m-block each, and all 16); the others only keep the step
+// barriers.  Each role fetches its weight fragments when it starts, as in
+// midp_kernel.
+#ifndef HEADMID_T2W
+#define HEADMID_T2W 4
+#endif
+struct HmPlan {
+    using Pl = HeadPlan<CfgS1::MP, CfgS1::C, CfgS1::TF, true>;
+    static constexpr int S_MAX = 4 * CfgS1::TF - 2;  // owned columns + one on either side = the valid positions
+    struct Lay {
+        static constexpr bool PLANES = true;
+        static constexpr int R0_OFF = 0, R1_OFF = 0, R2_OFF = mp::RROWS * mp::RS1;  // (no R0)
+        static constexpr int U_OFF = Pl::RA;
+    };
+    static constexpr int NCH_MAX = (S_MAX + 15) / 16;
+    static_assert(head_planar<CfgS1>() && CfgS1::HW == 16, "the phase-planar head of 16 waves");
+    static_assert(Pl::RS_1 == mp::PRS && kPlane == mp::PROWS, "layer 0 of the mid reads the head's u planes");
+    static_assert(Lay::R2_OFF + mp::RROWS * mp::RS1 <= Pl::RA, "rings R1 and R2 in region A");
+    // layer 0 reads window positions -14 .. 16 NCH_MAX + 3: rows -4 .. 4 NCH_MAX + 1 of a plane
+    static_assert(Lay::U_OFF >= 4 * mp::PRS, "the warm-up chunk's rows stay inside LDS");
+    static_assert(Lay::U_OFF + (3 * mp::PROWS + 4 * NCH_MAX + 2) * mp::PRS <= Pl::LDS_BYTES,
+                  "the last chunk's rows stay inside LDS");
+};
+
+template <bool TRANS, int NCHC>
+__global__ __launch_bounds__(CfgS1::HW * 64, CfgS1::HMIN) void headmid_kernel(const float* __restrict__ mel, int T,
+                                                                               VocX w, unsigned char* __restrict__ U2,
+                                                                               int S, int nch_arg) {
+    if (w.rclear && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < 5) {
+        if (threadIdx.x == 0) *reinterpret_cast<volatile int*>(w.rclear) = 0;
+        else if (w.rqueue) reinterpret_cast<volatile unsigned*>(w.rqueue)[threadIdx.x - 1] = 0u;
+    }
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (w.head_prio == 1) {
+        const int pr = wv >> 2;
+        if (pr == 1) __builtin_amdgcn_s_setprio(1);
+        else if (pr == 2) __builtin_amdgcn_s_setprio(2);
+        else if (pr >= 3) __builtin_amdgcn_s_setprio(3);
+    }
+    using Cfg = CfgS1;
+    using Pl = HmPlan::Pl;
+    using Lay = HmPlan::Lay;
+    constexpr int M = Cfg::M, MP = Cfg::MP, TF = Cfg::TF, C1 = Pl::C1, MB1 = C1 / 16;
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    const int nch = NCHC ? NCHC : nch_arg;
+    const int b = blockIdx.y, qa = blockIdx.x * S, L1 = 4 * T;
+    const int o = qa - 1, f0 = o >> 2, rot = o & 3;  // the window: positions [4 f0 + rot, + 252)
+    APipe ap;
+    {
+        const int it0 = (((wv / MB1) + rot) & 3) * MB1 + wv % MB1;  // this wave's ConvT1 item: (phase, m-block)
+        const u32x4* wp0 = w.hc + (size_t)it0 * nkb_of<MP, 4>() * 128 + (threadIdx.x & 63);
+#pragma unroll
+        for (int kb = 0; kb < 4; ++kb) {
+            ap[kb][0][0] = wp0[kb * 128];
+            ap[kb][0][1] = wp0[kb * 128 + 64];
+        }
+    }
+    static_assert(Pl::CAP_MEL * Pl::RS_M + 4 * 4 * C1 <= Pl::RA, "mel window + edge terms in region A");
+    const XW melA{lds, f0 - 3};
+    unsigned char* corr = lds + Pl::CAP_MEL * Pl::RS_M;
+    // the windows whose planes hold input column 0 / T - 1 (columns f0 - 1 .. f0 + 64 at the most)
+    const bool left = f0 <= 1, right = T - 1 >= f0 - 1 && T - 1 <= f0 + 64;
+    float4 ev[4];
+    float eb = 0.f;
+    if (left || right) head_edge_load<MP, C1>(w.hce, ev, eb);
+    gload_mel<TRANS, M, MP, Pl::RS_M, Pl::MEL_N, Cfg::HW * 64>(mel + (size_t)b * M * T, T, melA);
+    __syncthreads();
+    if (left || right) {
+        head_edge_terms<MP, C1, Pl::RS_M>(ev, eb, melA, T, left, right, corr);
+        __syncthreads();
+    }
+    unsigned char* up = lds + Pl::RA;
+    unsigned char* hp = lds;
+    const u32x4* wr1 = w.w1[0] + (size_t)(wv % MB1) * nkb_of<C1, 3>() * 128 + (threadIdx.x & 63);
+    const u32x4* wr2 = w.w2[0] + (size_t)(wv % MB1) * nkb_of<C1, 3>() * 128 + (threadIdx.x & 63);
+    head_convT1c_planar<MP, C1, Pl::RS_M, Pl::RS_1>(w.hc, w.hcb, (left || right) ? corr : nullptr, melA, up, f0, T,
+                                                    &ap, wr1, rot);
+    __syncthreads();
+    head_rb1_planar<C1, Pl::RS_1, false>(w.w1[0], w.b1[0], up, hp, nullptr, f0, TF, L1, &ap, wr2, nullptr, rot);
+    __syncthreads();
+    head_rb1_planar<C1, Pl::RS_1, true, true>(w.w2[0], w.b2[0], hp, nullptr, up, f0, TF, L1, &ap, nullptr, nullptr,
+                                              rot);
+    __syncthreads();  // U1 of the window is in the u planes; region A is dead
+    // the mid's pipeline over the strip (midp_kernel's roles and step protocol)
+    const bool edge = qa < 16 || qa + 16 * nch + 16 > L1;
+    const int xown = min(L1, qa + S);
+    unsigned char* u2row = U2 + (size_t)b * 4 * L1 * 128;
+    const u32x4* W = w.mp;
+    const float* bias = w.mpb;
+    constexpr bool T8 = HEADMID_T2W == 8;
+    const int layer = T8 ? (wv < 8 ? 0 : (wv < 12 ? 1 : 2)) : (wv < 12 ? wv >> 2 : 3);
+    if (layer == 2) __builtin_amdgcn_s_setprio(2);  // later layers: younger waves, the step waits for them
+    else if (layer == 1) __builtin_amdgcn_s_setprio(1);
+    else __builtin_amdgcn_s_setprio(0);
+    if constexpr (T8) {
+        switch (wv) {
+            case 0: mp::layer_role<0, 0, Lay, 0, 1>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
+            case 1: mp::layer_role<0, 0, Lay, 1, 1>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
+            case 2: mp::layer_role<0, 1, Lay, 0, 1>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
+            case 3: mp::layer_role<0, 1, Lay, 1, 1>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
+            case 4: mp::layer_role<0, 2, Lay, 0, 1>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
+            case 5: mp::layer_role<0, 2, Lay, 1, 1>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
+            case 6: mp::layer_role<0, 3, Lay, 0, 1>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
+            case 7: mp::layer_role<0, 3, Lay, 1, 1>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
+            case 8: mp::layer_role<1, 0, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
+            case 9: mp::layer_role<1, 1, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
+            case 10: mp::layer_role<1, 2, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
+            case 11: mp::layer_role<1, 3, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
+            case 12: mp::layer_role<2, 0, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
+            case 13: mp::layer_role<2, 1, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
+            case 14: mp::layer_role<2, 2, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
+            default: mp::layer_role<2, 3, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
+        }
+    } else {
+        switch (wv) {
+            case 0: mp::layer_role<0, 0, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
+            case 1: mp::layer_role<0, 1, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
+            case 2: mp::layer_role<0, 2, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
+            case 3: mp::layer_role<0, 3, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
+            case 4: mp::layer_role<1, 0, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
+            case 5: mp::layer_role<1, 1, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
+            case 6: mp::layer_role<1, 2, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
+            case 7: mp::layer_role<1, 3, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
+            case 8: mp::layer_role<2, 0, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
+            case 9: mp::layer_role<2, 1, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
+            case 10: mp::layer_role<2, 2, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
+            case 11: mp::layer_role<2, 3, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
+            default:  // no role: the step barriers only
+#pragma unroll 1
+                for (int s = -1; s <= nch + 2; ++s) pipe::step_barrier();
+                break;
+        }
+    }
+}
+
+// Why a call does not take headmid_kernel (null: it does).
+inline const char* headmid_excluded(const VocX& w, bool comp, bool s1) {
+    if (!sw().headmid) return "M2_HEADMID=0";
+    if (!s1) return "not the stage1 shapes";
+    if (w.dT) return "the frame count is on the device: the grid covers the capacity";
+    if (!w.mp || !w.hc || !comp) return "no split packs of the composed head and the pipelined mid (or M2_HEAD_INCONV)";
+    if (sw().midp_nch > 0) return "M2_MIDP_NCH forces the mid's strip length";
+    if (w.prof_slots & 3u) return "events around the head or the mid: the fused launch has no boundary between them";
+    return nullptr;
+}
+std::atomic<long> g_headmid_launches{0};
+
 template <class Cfg>
 __global__ __launch_bounds__(Cfg::MW * 64, Cfg::MMIN) void x3_mid_kernel(const unsigned char* __restrict__ U1,
                                                                            int L1, VocX w,
@@ -1422,7 +1602,7 @@ int32_t run(const float* mel, bool trans, int B, int T, const VocX& w, void* U1,
     using HP27 = HeadPlan<CfgS2H27::MP, CfgS2H27::C, CfgS2H27::TF, false>;
     using MP = MidPlan<Cfg::C / 2, Cfg::W2>;
     using TP = TailPlan<Cfg::C / 4, Cfg::W3>;
-    constexpr bool S2 = std::is_same<Cfg, CfgS2>::value;
+    constexpr bool S2 = std::is_same<Cfg, CfgS2>::value, S1 = std::is_same<Cfg, CfgS1>::value;
     using MPA = MidPlan<CfgS2Alt::C / 2, CfgS2Alt::W2>;
     using TPA = TailPlan<CfgS2Alt::C / 4, CfgS2Alt::W3>;
     static bool attr = false;
@@ -1444,6 +1624,12 @@ int32_t run(const float* mel, bool trans, int B, int T, const VocX& w, void* U1,
             if ((rc = set_lds(x3_mid_kernel<CfgS2Alt>, MPA::LDS_BYTES))) return rc;
             if ((rc = set_lds(x3_tail_kernel<CfgS2Alt>, TPA::LDS_BYTES))) return rc;
         }
+        if constexpr (S1) {
+            if ((rc = set_lds(headmid_kernel<false, 16>, HmPlan::Pl::LDS_BYTES))) return rc;
+            if ((rc = set_lds(headmid_kernel<true, 16>, HmPlan::Pl::LDS_BYTES))) return rc;
+            if ((rc = set_lds(headmid_kernel<false, 0>, HmPlan::Pl::LDS_BYTES))) return rc;
+            if ((rc = set_lds(headmid_kernel<true, 0>, HmPlan::Pl::LDS_BYTES))) return rc;
+        }
         attr = true;
     }
     bool alt_mid = false, alt_tail = false;
@@ -1463,11 +1649,56 @@ int32_t run(const float* mel, bool trans, int B, int T, const VocX& w, void* U1,
     }
     auto* u1 = static_cast<unsigned char*>(U1);
     auto* u2 = static_cast<unsigned char*>(U2);
-    mark(0, true);
+    auto tail = [&]() -> int32_t {
+        mark(2, true);
+        if (w.tp2) {  // stage2: the pipelined tail (vocoder_tailp2.hip)
+            const int32_t rc = launch_vocoder_tailp2(u2, 16 * T, B, w.tp2, w.tp2b, audio, w.rflag, st, w.dT,
+                                                     VocRedo{w.redo_w, mel, trans});
+            mark(2, false);
+            return rc;
+        }
+        if (w.tp) {  // stage1: the pipelined tail (vocoder_tailp.hip)
+            const int32_t rc = launch_vocoder_tailp(u2, 16 * T, B, w.tp, w.tpb, audio, w.rflag, st, w.dT,
+                                                    VocRedo{w.redo_w, mel, trans});
+            mark(2, false);
+            return rc;
+        }
+        if (S2 && alt_tail)
+            hipLaunchKernelGGL((x3_tail_kernel<CfgS2Alt>), dim3(cdiv(16 * T, CfgS2Alt::W3), B), dim3(Cfg::TW * 64),
+                               TPA::LDS_BYTES, st, u2, 16 * T, w, audio);
+        else
+            hipLaunchKernelGGL((x3_tail_kernel<Cfg>), dim3(cdiv(16 * T, Cfg::W3), B), dim3(Cfg::TW * 64),
+                               TP::LDS_BYTES, st, u2, 16 * T, w, audio);
+        mark(2, false);
+        M2_LAUNCHED("x3_tail_kernel");
+        return M2_OK;
+    };
     // the composed input_conv o ConvT1 head when packed (stage1; 22.1 -> 19.7
     // us, profiles/ab/r02l_head_comp.txt); M2_HEAD_INCONV=1 runs the two
     // layers (A/B and test switch, m2_common.h switch table)
     const bool comp = w.hc && !sw().head_inconv;
+    if constexpr (S1) {
+        // stage1, host-known T, split packs: the head and the mid in one
+        // launch (headmid_kernel); headmid_excluded names what keeps a call
+        // on the three launches.  n strips of S <= 250 columns per utterance.
+        if (!headmid_excluded(w, comp, S1)) {
+            const int n = cdiv(4 * T, HmPlan::S_MAX), S = cdiv(4 * T, n), nch = cdiv(S, 16);
+            const dim3 g(n, B), b(Cfg::HW * 64);
+            const int lds = HmPlan::Pl::LDS_BYTES;
+            if (nch == 16 && trans)
+                hipLaunchKernelGGL((headmid_kernel<true, 16>), g, b, lds, st, mel, T, w, u2, S, nch);
+            else if (nch == 16)
+                hipLaunchKernelGGL((headmid_kernel<false, 16>), g, b, lds, st, mel, T, w, u2, S, nch);
+            else if (trans)
+                hipLaunchKernelGGL((headmid_kernel<true, 0>), g, b, lds, st, mel, T, w, u2, S, nch);
+            else
+                hipLaunchKernelGGL((headmid_kernel<false, 0>), g, b, lds, st, mel, T, w, u2, S, nch);
+            M2_LAUNCHED("headmid_kernel");
+            g_headmid_launches.fetch_add(1, std::memory_order_relaxed);
+            return tail();
+        }
+    }
+    mark(0, true);
     const dim3 hg(cdiv(T, Cfg::TF), B), hb(Cfg::HW * 64);
     // stage2, composed head: the 16-wave heads (24 / 27 frames) on large
     // grids, the 8-wave heads (16 / 19) below; within a pair the fewer rounds
@@ -1528,28 +1759,7 @@ int32_t run(const float* mel, bool trans, int B, int T, const VocX& w, void* U1,
         M2_LAUNCHED("x3_mid_kernel");
     }
     mark(1, false);
-    mark(2, true);
-    if (w.tp2) {  // stage2: the pipelined tail (vocoder_tailp2.hip)
-        const int32_t rc = launch_vocoder_tailp2(u2, 16 * T, B, w.tp2, w.tp2b, audio, w.rflag, st, w.dT,
-                                                 VocRedo{w.redo_w, mel, trans});
-        mark(2, false);
-        return rc;
-    }
-    if (w.tp) {  // stage1: the pipelined tail (vocoder_tailp.hip)
-        const int32_t rc =
-            launch_vocoder_tailp(u2, 16 * T, B, w.tp, w.tpb, audio, w.rflag, st, w.dT, VocRedo{w.redo_w, mel, trans});
-        mark(2, false);
-        return rc;
-    }
-    if (S2 && alt_tail)
-        hipLaunchKernelGGL((x3_tail_kernel<CfgS2Alt>), dim3(cdiv(16 * T, CfgS2Alt::W3), B), dim3(Cfg::TW * 64),
-                           TPA::LDS_BYTES, st, u2, 16 * T, w, audio);
-    else
-        hipLaunchKernelGGL((x3_tail_kernel<Cfg>), dim3(cdiv(16 * T, Cfg::W3), B), dim3(Cfg::TW * 64), TP::LDS_BYTES, st,
-                           u2, 16 * T, w, audio);
-    mark(2, false);
-    M2_LAUNCHED("x3_tail_kernel");
-    return M2_OK;
+    return tail();
 }
 
 }  // namespace x3
@@ -1565,6 +1775,8 @@ extern "C" int32_t m2_debug_stamps_x3(void* host, size_t bytes) {
                                         bytes < sizeof(x3::g_x3_stamps) ? bytes : sizeof(x3::g_x3_stamps));
 }
 #endif
+
+extern "C" int64_t m2_debug_headmid_launches(void) { return x3::g_headmid_launches.load(std::memory_order_relaxed); }
 
 bool vocoder_x3_supported(int M, int C) { return (M == 64 && C == 128) || (M == 80 && C == 256); }
 

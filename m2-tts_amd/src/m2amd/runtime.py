@@ -456,6 +456,18 @@ def default_range_policy() -> str:
     return env
 
 
+def headmid_switch() -> bool:
+    """M2_HEADMID: the stage1 vocoder's head and mid stages as one launch (1,
+    the default) or two (0).  Any other value is an error, named here at
+    handle creation: the library itself would keep the default."""
+    env = os.environ.get("M2_HEADMID")
+    if env is None or env == "":
+        return True
+    if env not in ("0", "1"):
+        raise ValueError(f"M2_HEADMID={env!r}: expected 0 or 1")
+    return env == "1"
+
+
 class HandleCache:
     """Per-device HipModel for one nn.Module, rebuilt when its weights change.
     ``lane`` > 0 gives further handles of the same weights (one per stream of a
@@ -469,6 +481,7 @@ class HandleCache:
         ent = self._entries.get((device, lane))
         if ent is not None and ent[0] == key:
             return ent[1]
+        headmid_switch()  # a bad M2_HEADMID is reported before the handle exists
         hm = HipModel(module.state_dict(), cfg, device)
         # per-model vocoder modes survive a rebuild (weights reloaded, .to())
         chunk = module.__dict__.get("_m2_chunk_frames", 0)
