@@ -570,7 +570,37 @@ int32_t m2_eval_mcd(const float* pred, const float* target, const int32_t* cols,
  * slices of m2_disc_losses (the bound counts the maps of both sides); the
  * workspace query adds two cotangent maps of the widest layer and the pooled
  * audio per utterance of a slice, and the split-K partials (at most 32 MiB
- * beyond one copy of the largest weight). */
+ * beyond one copy of the largest weight).
+ *
+ * m2_disc_gen_step: the generator step's gradient through the
+ * discriminators.  `out` as m2_disc_losses writes it (same launches, same
+ * bits) and d_fake [B,1,L] (overwritten), the gradient with respect to `fake`
+ * of
+ *   w_adv L_G + w_fm L_FM,
+ *   L_G  = (1/3) sum_s mean (D_s(fake) - 1)^2,
+ *   L_FM = (1/18) sum_{s,j} mean |f_{s,j}(fake) - f_{s,j}(real)|,
+ * f_{s,j} the six pre-activation maps of scale s.  real may be NULL exactly
+ * when w_fm == 0: only the fake side runs then, and `out` is
+ * m2_disc_losses(NULL, fake)'s (NULL with w_fm != 0 is M2_E_ARG).  Each
+ * (slice, scale) runs forward, then the fake side backward while the maps of
+ * both sides are in the workspace: the logit cotangent
+ * w_adv 2 (D - 1) / (3 N_s), the data gradients of layers 6..1 (no weight,
+ * bias or split-K launch), w_fm sign(f_fake - f_real) / (18 count(s,j)) added
+ * to the cotangent of map j before the layer below reads it (sign(0) = 0, as
+ * torch's l1_loss backward), and the first layer fused with the adjoint of
+ * avg_pool1d: d_pooled[u] / scale on samples u scale .. u scale + scale - 1,
+ * nothing on the samples floor pooling dropped.  Scale index 0 overwrites a
+ * slice's rows of d_fake, the later scales add in stream order; no kernel
+ * reduces over the batch, so the slice size does not change a bit.  real and
+ * the discriminators' parameters get no gradient.  Slices as m2_disc_losses;
+ * the workspace query adds the two cotangent maps of m2_disc_step.
+ *
+ * m2_conv1d_audio_backward: that last kernel on its own: the gradient of
+ * y = conv1d(avg_pool1d(x, pool); w [Cout,1,k], stride 1, padding) with
+ * respect to x [B,1,L], given dy [B,Cout,L/pool + 2 padding - k + 1]; dx
+ * [B,1,L] is overwritten (the dropped tail samples with 0) or, with
+ * `accumulate`, added to (the tail left alone).  Cout k floats of weights and
+ * a 16-channel window of 256 + k - 1 samples must fit 48 KiB of LDS. */
 typedef struct m2_disc m2_disc;
 int32_t m2_loss_column_count(int32_t kind);
 const char* m2_loss_column_name(int32_t kind, int32_t index);
@@ -601,6 +631,12 @@ int32_t m2_conv1d_strided_backward(const float* x_pre, const float* w, const flo
 size_t m2_disc_step_workspace_bytes(const m2_disc* disc, int32_t B, int32_t L);
 int32_t m2_disc_step(const m2_disc* disc, const float* real, const float* fake, int32_t B, int32_t L, double* out,
                      float* const* grads, void* workspace, size_t workspace_bytes, void* stream);
+size_t m2_disc_gen_step_workspace_bytes(const m2_disc* disc, int32_t B, int32_t L);
+int32_t m2_disc_gen_step(const m2_disc* disc, const float* real, const float* fake, int32_t B, int32_t L,
+                         double w_adv, double w_fm, double* out, float* d_fake, void* workspace,
+                         size_t workspace_bytes, void* stream);
+int32_t m2_conv1d_audio_backward(const float* dy, const float* w, int32_t ksize, int32_t padding, int32_t pool,
+                                 int32_t B, int32_t Cout, int32_t L, int32_t accumulate, float* dx, void* stream);
 size_t m2_loss_spectral_workspace_bytes(const m2_dsp* dsp, int32_t B, int32_t L);
 int32_t m2_loss_spectral(const m2_dsp* dsp, const float* pred, const float* target, int32_t B, int32_t L,
                          const float* mel_weights, int32_t n_weights, double* out, void* spec_pred, void* spec_target,

@@ -1,7 +1,8 @@
 // Training losses on the GPU: the sums behind the reference's
 // src/training/losses.py (SpectralLoss, PerceptualLoss, MultiScaleDiscriminator,
-// AdversarialLoss), batched over utterances, and the one gradient: the
-// discriminator loss with respect to the discriminators' parameters.
+// AdversarialLoss), batched over utterances, and two gradients: the
+// discriminator loss with respect to the discriminators' parameters, and the
+// generator's adversarial and feature-matching terms with respect to the audio.
 //
 //   conv      Conv1d(k, stride, zero padding, groups) + bias, with a leaky
 //             slope on the input (the discriminators' feature maps are the
@@ -26,6 +27,14 @@
 //             m2_disc_step runs each (slice, scale) forward as losses does and
 //             then each side backward while its maps are in the workspace,
 //             accumulating the 42 gradients in stream order.
+//   generator m2_disc_gen_step: the gradient of the adversarial and
+//             feature-matching terms with respect to the fake audio.  The
+//             forward half again, then the fake side backward with data
+//             gradients only: logit_cotangent_kernel, layers 6..1 through the
+//             dx kernels above, fm_cotangent_kernel adding the sign term to
+//             each map's cotangent before the layer below reads it, and
+//             conv_dx_audio_kernel: the first layer's data gradient fused
+//             with the adjoint of avg_pool1d and the sum over scales.
 //   spectral  spectral_frame_kernel: torch.stft framing (centre, reflect
 //             padding), pred and target through one complex FFT as in
 //             eval_metrics.hip; magnitudes and angles in double from the fp32
@@ -567,6 +576,71 @@ __global__ __launch_bounds__(256) void logit_cotangent_kernel(const float* __res
     if (i < n) dy[i] = (float)(((double)logits[i] - target) * scale);
 }
 
+// The feature-matching term of one map, added to the cotangent of that map:
+// cot[i] += c sign(f_fake[i] - f_real[i]), sign(0) = 0 (torch's l1_loss backward).
+__global__ __launch_bounds__(256) void fm_cotangent_kernel(const float* __restrict__ f_fake,
+                                                           const float* __restrict__ f_real, size_t n, float c,
+                                                           float* __restrict__ cot) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float a = f_fake[i], b = f_real[i];
+    if (a != b) cot[i] += a > b ? c : a < b ? -c : a - b;  // unordered: the NaN goes on, as torch's sign does
+}
+
+// Data gradient of y = conv(avg_pool1d(x, pool), w) for one input channel and
+// stride 1 (the discriminators' first layer), down to the audio samples.
+// grid (cdiv(L, 256 pool), utterances); dy [nb, Cout, Lo], w [Cout, 1, k],
+// dx [nb, 1, L], Lp = L / pool pooled positions, Lo = Lp + 2 pad - k + 1.  A
+// workgroup owns the pooled positions u in [256 bx, +256), one per thread:
+// acc = sum over (co, tap), in that order, of w[co][tap] dy[co][u + pad - tap],
+// with the weights in LDS and dy's window (256 + k - 1 samples, 0 outside
+// [0, Lo)) staged 16 channels at a time at an odd row pitch.  The sums change
+// hands in LDS, so that consecutive threads write consecutive samples: sample
+// i gets acc[i / pool] / pool, overwritten or, with `accumulate`, added to; the
+// samples floor pooling dropped (i >= pool Lp) are zeroed or left alone.
+constexpr int kAuP = 256;
+__global__ __launch_bounds__(kAuP) void conv_dx_audio_kernel(const float* __restrict__ dy, const float* __restrict__ w,
+                                                             float* __restrict__ dx, int Cout, int k, int pad, int pool,
+                                                             int L, int Lp, int Lo, int accumulate) {
+    extern __shared__ float ds[];
+    const int tid = threadIdx.x, u0 = blockIdx.x * kAuP;
+    const int win = kAuP + k - 1, winp = win | 1;
+    float* wl = ds;                 // [Cout][k]
+    float* wnd = ds + Cout * k;     // [kCch][winp]
+    float acc = 0.f;
+    if (u0 < Lp) {  // the same for every thread of the workgroup
+        for (int i = tid; i < Cout * k; i += kAuP) wl[i] = w[i];
+        const float* dyb = dy + (size_t)blockIdx.y * Cout * Lo;
+        const int t0 = u0 + pad - (k - 1);
+        for (int cs = 0; cs < Cout; cs += kCch) {
+            const int nch = min(kCch, Cout - cs);
+            for (int i = tid; i < nch * win; i += kAuP) {
+                const int c = i / win, o = i - c * win, t = t0 + o;
+                wnd[c * winp + o] = (t >= 0 && t < Lo) ? dyb[(size_t)(cs + c) * Lo + t] : 0.f;
+            }
+            __syncthreads();
+            for (int c = 0; c < nch; ++c) {
+                const float* wr = wl + (cs + c) * k;
+                const float* br = wnd + c * winp + tid + (k - 1);
+                for (int tap = 0; tap < k; ++tap) acc = fmaf(wr[tap], br[-tap], acc);
+            }
+            __syncthreads();
+        }
+    }
+    wnd[tid] = acc / (float)pool;
+    __syncthreads();
+    float* dxb = dx + (size_t)blockIdx.y * L;
+    for (int j = 0; j < pool; ++j) {
+        const int o = j * kAuP + tid;
+        const long long i = (long long)u0 * pool + o;
+        if (i >= L) break;
+        if (u0 + o / pool < Lp)
+            dxb[i] = (accumulate ? dxb[i] : 0.f) + wnd[o / pool];
+        else if (!accumulate)
+            dxb[i] = 0.f;
+    }
+}
+
 // grid (frames, B): frame t of torch.stft(center=True, pad_mode='reflect') of
 // pred and target [B, L]; part [B, frames, kSpecPart]; the spectra
 // [B, frames, N/2 + 1] are written when asked for.
@@ -778,8 +852,9 @@ bool dx_mfma_ok(const ConvGeo& g) {
 }
 
 // The gradients of one layer over nb utterances: x_pre [nb, Cin, L], dy [nb, Cout, Lo];
-// dx (or null) is overwritten; dw and db (or null) are overwritten or, with
-// `accumulate`, added to.  packed: w is [k, Cin/g, Cout].  part holds dw_plan's part_floats.
+// dx (or null) is overwritten; dw (or null: no weight gradient, no partials) and db (or null)
+// are overwritten or, with `accumulate`, added to.  packed: w is [k, Cin/g, Cout].  part holds
+// dw_plan's part_floats.
 int32_t launch_conv_bwd(const float* x_pre, const float* w, const float* dy, const ConvGeo& g, int nb, int L,
                         bool packed, float in_slope, float* dx, float* dw, float* db, bool accumulate, float* part,
                         hipStream_t st) {
@@ -802,15 +877,15 @@ int32_t launch_conv_bwd(const float* x_pre, const float* w, const float* dy, con
             M2_LAUNCHED("conv_dx_direct_kernel");
         }
     }
-    const DwPlan p = dw_plan(g, nb, L);
-    if (p.mfma) {
+    const DwPlan p = dw ? dw_plan(g, nb, L) : DwPlan();
+    if (dw && p.mfma) {
         hipLaunchKernelGGL(loss::conv_dw_mfma_kernel, dim3(p.blocks, cdiv(g.Cout, 16), p.splits), dim3(256), p.lds, st,
                            x_pre, dy, part, g, nb, L, Lo, in_slope, p.nciB, p.cps);
         M2_LAUNCHED("conv_dw_mfma_kernel");
         hipLaunchKernelGGL(loss::dw_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, part, n,
                            p.splits, accumulate ? 1 : 0, dw);
         M2_LAUNCHED("dw_finish_kernel");
-    } else {
+    } else if (dw) {
         hipLaunchKernelGGL(loss::conv_dw_direct_kernel, dim3((unsigned)n), dim3(dsp::NT), 0, st, x_pre, dy, dw, g, nb,
                            L, Lo, in_slope, accumulate ? 1 : 0);
         M2_LAUNCHED("conv_dw_direct_kernel");
@@ -853,6 +928,58 @@ StepPlan step_plan(const m2_disc* d, int B, int L) {
         }
     }
     return p;
+}
+
+// The forward half of one (slice, scale) of m2_disc_losses, shared with the two steps so that
+// their rows are its rows bit for bit: each side that is given runs into act[side] (map[side][i]
+// receives where layer i went, null for a side that is not given), then the two reductions write
+// the scale's columns of the slice's rows.
+int32_t scale_forward(const m2_disc* d, int s, const float* real, const float* fake, int b0, int nb, int L,
+                      const int len[kLayers], float* const act[2], double* part, int max_chunks, double* out,
+                      float* map[2][kLayers], hipStream_t st) {
+    loss::RedMaps maps;
+    int chunks = 1;
+    for (int side = 0; side < 2; ++side) {
+        const float* x = side ? fake : real;
+        float* out_l[kLayers];
+        float* p = act[side];
+        for (int i = 0; i < kLayers; ++i) {
+            const size_t n = (size_t)kDisc[i].Cout * len[i];
+            out_l[i] = p;
+            map[side][i] = x ? p : nullptr;
+            (side ? maps.fake : maps.real)[i] = x ? p : nullptr;
+            maps.n[i] = (long long)n;
+            chunks = std::max(chunks, cdiv((int)n, loss::kRedChunk));
+            p += align_up(n, 64) * nb;
+        }
+        if (!x) continue;
+        const int32_t rc = run_scale(d, s, x + (size_t)b0 * L, nb, L, out_l, st);
+        if (rc != M2_OK) return rc;
+    }
+    hipLaunchKernelGGL(loss::reduce_part_kernel, dim3(chunks, kLayers, nb), dim3(dsp::NT), 0, st, maps, max_chunks,
+                       part);
+    M2_LAUNCHED("reduce_part_kernel");
+    hipLaunchKernelGGL(loss::reduce_finish_kernel, dim3(nb), dim3(dsp::NT), 0, st, part, maps, max_chunks,
+                       out + (size_t)b0 * loss::kDiscK + (size_t)s * loss::kDiscScaleK, loss::kDiscK);
+    M2_LAUNCHED("reduce_finish_kernel");
+    return M2_OK;
+}
+
+// The first-layer data gradient down to the audio samples (conv_dx_audio_kernel's layout).
+bool audio_bwd_ok(int Cout, int k) {
+    return (long long)Cout * k <= (1 << 13) && k <= (1 << 12) &&
+           ((size_t)Cout * k + (size_t)loss::kCch * ((loss::kAuP + k - 1) | 1)) * sizeof(float) <= (size_t)loss::kMaxLds;
+}
+
+int32_t launch_audio_bwd(const float* dy, const float* w, int Cout, int k, int pad, int pool, int nb, int L,
+                         bool accumulate, float* dx, hipStream_t st) {
+    const int Lp = L / pool, Lo = Lp + 2 * pad - k + 1;
+    const size_t lds = ((size_t)Cout * k + (size_t)loss::kCch * ((loss::kAuP + k - 1) | 1)) * sizeof(float);
+    hipLaunchKernelGGL(loss::conv_dx_audio_kernel, dim3((unsigned)(((long long)L + (long long)loss::kAuP * pool - 1) /
+                                                                   ((long long)loss::kAuP * pool)), nb),
+                       dim3(loss::kAuP), lds, st, dy, w, dx, Cout, k, pad, pool, L, Lp, Lo, accumulate ? 1 : 0);
+    M2_LAUNCHED("conv_dx_audio_kernel");
+    return M2_OK;
 }
 
 bool disc_shape_ok(const m2_disc* d, int B, int L) {
@@ -1082,30 +1209,9 @@ int32_t m2_disc_losses(const m2_disc* d, const float* real, const float* fake, i
         for (int s = 0; s < d->n_scales; ++s) {
             int len[kLayers];
             disc_lengths(L, d->scales[s], len);
-            loss::RedMaps maps;
-            int chunks = 1;
-            for (int side = 0; side < 2; ++side) {
-                const float* x = side ? fake : real;
-                float* out_l[kLayers];
-                float* p = act[side];
-                for (int i = 0; i < kLayers; ++i) {
-                    const size_t n = (size_t)kDisc[i].Cout * len[i];
-                    out_l[i] = p;
-                    (side ? maps.fake : maps.real)[i] = x ? p : nullptr;
-                    maps.n[i] = (long long)n;
-                    chunks = std::max(chunks, cdiv((int)n, loss::kRedChunk));
-                    p += align_up(n, 64) * nb;
-                }
-                if (!x) continue;
-                const int32_t rc = run_scale(d, s, x + (size_t)b0 * L, nb, L, out_l, st);
-                if (rc != M2_OK) return rc;
-            }
-            hipLaunchKernelGGL(loss::reduce_part_kernel, dim3(chunks, kLayers, nb), dim3(dsp::NT), 0, st, maps,
-                               max_chunks, part);
-            M2_LAUNCHED("reduce_part_kernel");
-            hipLaunchKernelGGL(loss::reduce_finish_kernel, dim3(nb), dim3(dsp::NT), 0, st, part, maps, max_chunks,
-                               out + (size_t)b0 * loss::kDiscK + (size_t)s * loss::kDiscScaleK, loss::kDiscK);
-            M2_LAUNCHED("reduce_finish_kernel");
+            float* map[2][kLayers];
+            const int32_t rc = scale_forward(d, s, real, fake, b0, nb, L, len, act, part, max_chunks, out, map, st);
+            if (rc != M2_OK) return rc;
         }
     }
     return M2_OK;
@@ -1180,28 +1286,9 @@ int32_t m2_disc_step(const m2_disc* d, const float* real, const float* fake, int
             int len[kLayers];
             disc_lengths(L, d->scales[s], len);
             // the forward half: m2_disc_losses's launches
-            loss::RedMaps maps;
             float* map[2][kLayers];
-            int chunks = 1;
-            for (int side = 0; side < 2; ++side) {
-                float* p = act[side];
-                for (int i = 0; i < kLayers; ++i) {
-                    const size_t n = (size_t)kDisc[i].Cout * len[i];
-                    map[side][i] = p;
-                    (side ? maps.fake : maps.real)[i] = p;
-                    maps.n[i] = (long long)n;
-                    chunks = std::max(chunks, cdiv((int)n, loss::kRedChunk));
-                    p += align_up(n, 64) * nb;
-                }
-                const int32_t rc = run_scale(d, s, (side ? fake : real) + (size_t)b0 * L, nb, L, map[side], st);
-                if (rc != M2_OK) return rc;
-            }
-            hipLaunchKernelGGL(loss::reduce_part_kernel, dim3(chunks, kLayers, nb), dim3(dsp::NT), 0, st, maps,
-                               pl.max_chunks, dpart);
-            M2_LAUNCHED("reduce_part_kernel");
-            hipLaunchKernelGGL(loss::reduce_finish_kernel, dim3(nb), dim3(dsp::NT), 0, st, dpart, maps, pl.max_chunks,
-                               out + (size_t)b0 * loss::kDiscK + (size_t)s * loss::kDiscScaleK, loss::kDiscK);
-            M2_LAUNCHED("reduce_finish_kernel");
+            const int32_t rcf = scale_forward(d, s, real, fake, b0, nb, L, len, act, dpart, pl.max_chunks, out, map, st);
+            if (rcf != M2_OK) return rcf;
             // the backward half, side by side, while the maps are resident
             const int Lp = L / d->scales[s];
             const double cscale = 2.0 / ((double)B * (double)len[kLayers - 1] * (double)d->n_scales);
@@ -1229,6 +1316,84 @@ int32_t m2_disc_step(const m2_disc* d, const float* real, const float* fake, int
                     cur ^= 1;
                 }
             }
+        }
+    }
+    return M2_OK;
+}
+
+int32_t m2_conv1d_audio_backward(const float* dy, const float* w, int32_t ksize, int32_t padding, int32_t pool,
+                                 int32_t B, int32_t Cout, int32_t L, int32_t accumulate, float* dx, void* stream) {
+    M2_CHECK_ARG(dy && w && dx && ksize > 0 && padding >= 0 && pool > 0 && B >= 0 && Cout > 0 && L > 0,
+                 "m2_conv1d_audio_backward: bad argument");
+    M2_CHECK_SHAPE(B <= loss::kMaxGrid && L <= (1 << 28) && pool <= (1 << 16) && padding <= (1 << 12) &&
+                       audio_bwd_ok(Cout, ksize),
+                   "m2_conv1d_audio_backward: at most 65535 utterances of 2^28 samples, pool 2^16, padding 2^12, "
+                   "and weights and a 16-channel window that fit LDS");
+    M2_CHECK_SHAPE(L / pool + 2 * padding >= ksize && L / pool >= 1,
+                   "m2_conv1d_audio_backward: kernel wider than the padded pooled input");
+    if (B == 0) return M2_OK;
+    return launch_audio_bwd(dy, w, Cout, ksize, padding, pool, B, L, accumulate != 0, dx,
+                            static_cast<hipStream_t>(stream));
+}
+
+size_t m2_disc_gen_step_workspace_bytes(const m2_disc* d, int32_t B, int32_t L) {
+    if (!d || B < 0 || L <= 0) return 0;
+    const StepPlan p = step_plan(d, B, L);
+    return (size_t)p.nbs * (2 * p.per + 2 * p.cot) * sizeof(float) +
+           (size_t)p.nbs * kLayers * p.max_chunks * loss::kRedPart * sizeof(double) + 256 * 8;
+}
+
+int32_t m2_disc_gen_step(const m2_disc* d, const float* real, const float* fake, int32_t B, int32_t L, double w_adv,
+                         double w_fm, double* out, float* d_fake, void* workspace, size_t workspace_bytes,
+                         void* stream) {
+    M2_CHECK_ARG(d && fake && out && d_fake && B >= 0 && L > 0, "m2_disc_gen_step: bad argument");
+    M2_CHECK_ARG(real || w_fm == 0.0, "m2_disc_gen_step: the feature-matching term needs real");
+    M2_CHECK_SHAPE(d->n_scales == loss::kDiscScales, "m2_disc_gen_step: the rows are laid out for three scales");
+    M2_CHECK_SHAPE(disc_shape_ok(d, B, L),
+                   "m2_disc_gen_step: at most 65535 utterances of 2^28 samples, no shorter than the largest scale");
+    if (B == 0) return M2_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const StepPlan pl = step_plan(d, B, L);
+    const int nbs = pl.nbs;
+    Carve c(workspace, workspace_bytes);
+    float* act[2] = {c.take<float>((size_t)nbs * pl.per), c.take<float>((size_t)nbs * pl.per)};
+    double* dpart = c.take<double>((size_t)nbs * kLayers * pl.max_chunks * loss::kRedPart);
+    float* cot[2] = {c.take<float>((size_t)nbs * pl.cot), c.take<float>((size_t)nbs * pl.cot)};
+    if (!c.ok) return fail(M2_E_WORKSPACE, "m2_disc_gen_step: workspace too small");
+    for (int b0 = 0; b0 < B; b0 += nbs) {
+        const int nb = std::min(nbs, B - b0);
+        for (int s = 0; s < d->n_scales; ++s) {
+            int len[kLayers];
+            disc_lengths(L, d->scales[s], len);
+            // the forward half: m2_disc_losses's launches
+            float* map[2][kLayers];
+            const int32_t rcf = scale_forward(d, s, real, fake, b0, nb, L, len, act, dpart, pl.max_chunks, out, map, st);
+            if (rcf != M2_OK) return rcf;
+            // the fake side backward, data gradients only, while the maps of both sides are resident
+            const size_t nl = (size_t)nb * len[kLayers - 1];
+            const double cscale = w_adv * 2.0 / ((double)B * (double)len[kLayers - 1] * (double)d->n_scales);
+            hipLaunchKernelGGL(loss::logit_cotangent_kernel, dim3((unsigned)((nl + 255) / 256)), dim3(256), 0, st,
+                               map[1][kLayers - 1], nl, 1.0, cscale, cot[0]);
+            M2_LAUNCHED("logit_cotangent_kernel");
+            int cur = 0;
+            for (int i = kLayers - 1; i >= 1; --i) {
+                const int32_t rc = launch_conv_bwd(map[1][i - 1], d->w[s][i], cot[cur], kDisc[i], nb, len[i - 1],
+                                                   loss::conv_path(kDisc[i]) == loss::PATH_MFMA, loss::kDiscSlope,
+                                                   cot[cur ^ 1], nullptr, nullptr, false, nullptr, st);
+                if (rc != M2_OK) return rc;
+                cur ^= 1;
+                if (w_fm != 0.0) {  // the feature-matching term of map i - 1, before the next layer down reads it
+                    const size_t per_utt = (size_t)kDisc[i - 1].Cout * len[i - 1], n = per_utt * nb;
+                    const double fm = w_fm / ((double)(d->n_scales * kFeat) * (double)B * (double)per_utt);
+                    hipLaunchKernelGGL(loss::fm_cotangent_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
+                                       map[1][i - 1], map[0][i - 1], n, (float)fm, cot[cur]);
+                    M2_LAUNCHED("fm_cotangent_kernel");
+                }
+            }
+            // scale index 0 overwrites the slice's rows of d_fake, the later scales add in stream order
+            const int32_t rc = launch_audio_bwd(cot[cur], d->w[s][0], kDisc[0].Cout, kDisc[0].k, kDisc[0].pad,
+                                                d->scales[s], nb, L, s > 0, d_fake + (size_t)b0 * L, st);
+            if (rc != M2_OK) return rc;
         }
     }
     return M2_OK;

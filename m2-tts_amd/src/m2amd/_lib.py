@@ -16,6 +16,7 @@ LIB_PATH = Path(os.environ.get("M2TTS_HIP_LIB", _HERE / "libm2tts_hip.so"))
 c_i32 = ctypes.c_int32
 c_i64 = ctypes.c_int64
 c_f32 = ctypes.c_float
+c_f64 = ctypes.c_double
 c_size = ctypes.c_size_t
 c_vp = ctypes.c_void_p
 
@@ -113,6 +114,9 @@ _SIGNATURES = {
                                            c_i32, c_vp, c_vp, c_vp, c_vp, c_size, c_vp]),
     "m2_disc_step_workspace_bytes": (c_size, [c_vp, c_i32, c_i32]),
     "m2_disc_step": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_size, c_vp]),
+    "m2_disc_gen_step_workspace_bytes": (c_size, [c_vp, c_i32, c_i32]),
+    "m2_disc_gen_step": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_f64, c_f64, c_vp, c_vp, c_vp, c_size, c_vp]),
+    "m2_conv1d_audio_backward": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "m2_loss_spectral_workspace_bytes": (c_size, [c_vp, c_i32, c_i32]),
     "m2_loss_spectral": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_size, c_vp]),
     "m2_front_bytes": (c_size, [c_vp, c_i32, c_i32]),

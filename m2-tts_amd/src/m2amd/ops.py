@@ -166,6 +166,30 @@ def conv1d_strided_backward(x_pre: Tensor, weight: Tensor, dy: Tensor, *, stride
     return dx, dw, db
 
 
+def conv1d_audio_backward(dy: Tensor, weight: Tensor, L: int, *, padding: int = 0, pool: int = 1,
+                          out: Optional[Tensor] = None) -> Tensor:
+    """The gradient of y = F.conv1d(F.avg_pool1d(x, pool), weight [Cout,1,k], padding=padding) with respect to
+    x [B,1,L], given dy [B,Cout,L//pool + 2 padding - k + 1] (m2_conv1d_audio_backward).  Without ``out`` a new
+    [B,1,L] tensor is written, the samples floor pooling dropped with 0; with ``out`` the gradient is added to
+    it and those samples are left alone."""
+    require_device(dy, weight, out, what="conv1d_audio_backward")
+    dy, weight = f32c(dy), f32c(weight)
+    B, Cout, Lo = dy.shape
+    K, L, pool, padding = weight.shape[2], int(L), int(pool), int(padding)
+    if tuple(weight.shape) != (Cout, 1, K) or pool < 1 or Lo != L // pool + 2 * padding - K + 1:
+        raise ValueError(f"conv1d_audio_backward: dy {tuple(dy.shape)} and weight {tuple(weight.shape)} do not fit "
+                         f"{L} samples, pool {pool}, padding {padding}")
+    if out is None:
+        dx = torch.empty(B, 1, L, device=dy.device, dtype=torch.float32)
+    else:
+        dx = out
+        if tuple(dx.shape) != (B, 1, L) or dx.dtype != torch.float32 or not dx.is_contiguous():
+            raise ValueError(f"conv1d_audio_backward: out must be contiguous float32 {(B, 1, L)}")
+    _lib.call("m2_conv1d_audio_backward", _ptr(dy), _ptr(weight), K, padding, pool, B, Cout, L,
+              0 if out is None else 1, _ptr(dx), stream_handle(dy.device))
+    return dx
+
+
 def avg_pool1d(x: Tensor, kernel_size: int) -> Tensor:
     """F.avg_pool1d(x [B,C,L], k, stride=k) -> [B,C,L//k] (m2_avg_pool1d)."""
     require_device(x, what="avg_pool1d")
@@ -308,6 +332,29 @@ class Discriminators:
         _lib.call("m2_disc_step", self.handle, _ptr(real), _ptr(fake), B, L, _ptr(out), ptrs, _ptr(ws), ws.numel(),
                   stream_handle(dev))
         return out, grads
+
+    def gen_step(self, real: Optional[Tensor], fake: Tensor, w_adv: float, w_fm: float):
+        """The generator step through the discriminators (m2_disc_gen_step): ``losses(real, fake)``'s rows,
+        bit for bit, and d_fake [B,1,L] float32, the gradient of w_adv * generator loss + w_fm *
+        feature-matching loss with respect to ``fake``.  ``real`` may be None only when ``w_fm == 0``: the
+        rows are ``losses(None, fake)``'s then."""
+        w_adv, w_fm = float(w_adv), float(w_fm)
+        if real is None and w_fm != 0.0:
+            raise ValueError("discriminator: gen_step needs real for the feature-matching term")
+        fake = self._audio(fake)
+        real = None if real is None else self._audio(real)
+        if real is not None and real.shape != fake.shape:
+            raise ValueError(f"discriminator: real {tuple(real.shape)} and fake {tuple(fake.shape)} differ")
+        B, _, L = fake.shape
+        lib = _lib.load()
+        dev = fake.device
+        out = torch.zeros(B, lib.m2_loss_column_count(1), device=dev, dtype=torch.float64)
+        d_fake = torch.empty_like(fake)
+        need = int(lib.m2_disc_gen_step_workspace_bytes(self.handle, B, L))
+        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+        _lib.call("m2_disc_gen_step", self.handle, _ptr(real), _ptr(fake), B, L, w_adv, w_fm, _ptr(out), _ptr(d_fake),
+                  _ptr(ws), ws.numel(), stream_handle(dev))
+        return out, d_fake
 
 
 def embed_positional(ids: Tensor, emb: Tensor, pe: Tensor, scale: float) -> Tensor:

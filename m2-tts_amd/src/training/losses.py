@@ -8,7 +8,7 @@ m2amd.dsp), which write per-utterance rows of double sums; a few torch ops on
 the device turn those rows into the reference's means, so a call needs no host
 synchronisation.
 
-**Values, and one gradient.**  By default every returned value is a 0-dim
+**Values, and two gradients.**  By default every returned value is a 0-dim
 float32 tensor on the inputs' device with ``requires_grad=False``: the values
 carry no autograd graph, the same contract M2TTSModel.forward has in this
 tree, and score a checkpoint with the objective it was trained on.
@@ -27,11 +27,42 @@ device.  So ``optimizer_d.zero_grad(); loss(...)['total_loss'].backward();
 clip_grad_norm_(...); optimizer_d.step()`` works as in the reference.  The
 backward is once-differentiable, the audio inputs get no gradient (the
 reference detaches the fake audio there), and parameters with
-``requires_grad=False`` get ``None``.  Every other entry stays graph-free
-with the switch on or off: ``mel_loss``, ``duration_loss``, ``spectral_loss``,
-``perceptual_loss``, ``generator_loss``, ``feature_matching_loss`` and the
-generator-mode ``total_loss``; ``backward()`` through them is not available,
-nor is autograd through ``MultiScaleDiscriminator.forward``, and the trainers
+``requires_grad=False`` get ``None``.
+
+The same switch governs the generator side.  A generator-side graph exists
+only when the switch is on, gradients are enabled and the prediction tensor in
+question has ``requires_grad=True``; with plain input tensors everything stays
+graph-free.  Values are computed as without the switch and are bit-equal; an
+``_AttachGradients`` function returns the value unchanged and, in its
+once-differentiable backward, hands each prediction its kept gradient scaled
+by ``grad_output``, on the device.
+
+* ``AdversarialLoss.generator_loss(fake)``, ``feature_matching_loss(real,
+  fake)`` and ``generator_terms(real, fake, adversarial_weight,
+  feature_matching_weight)`` (the weighted sum as one tensor from one pass)
+  run m2_disc_gen_step: the gradient through the three discriminators into the
+  fake audio.  ``real`` never gets a gradient.
+* ``CombinedTTSLoss.forward`` in generator mode runs one m2_disc_gen_step with
+  its two weights in place of the forward-only sums when ``audio_pred``
+  requires grad (same rows, same values, no second forward).  Its ``mel_loss``
+  and ``duration_loss`` entries carry a ``grad_fn`` when ``mel_pred`` /
+  ``duration_pred`` require grad (sign(pred - target) over the counted frames,
+  and 2 (p - t) / n, a few device-side torch ops); ``generator_loss`` and
+  ``feature_matching_loss`` stay plain values.  ``total_loss`` carries a graph
+  only when every term of it with a non-zero weight has a gradient, i.e. with
+  ``spectral_loss_weight == perceptual_loss_weight == 0`` or without audio;
+  otherwise it stays graph-free and a one-time warning names the terms
+  without a gradient, because a ``backward()`` that silently omitted two
+  terms would be worse than none.
+
+One difference from the reference: there a generator ``backward()`` also fills
+the discriminators' ``.grad``, which its trainer zeroes before the next
+discriminator step, so nothing reads them; here the generator step leaves the
+42 parameters' ``.grad`` alone.
+
+``spectral_loss`` and ``perceptual_loss`` have no gradient yet (they need the
+STFT's adjoint), nor does anything go through
+``MultiScaleDiscriminator.forward`` or into ``M2TTSModel``, and the trainers
 are not part of this package.
 
 The discriminators' parameters live in plain ``nn.Conv1d`` modules built in the
@@ -135,6 +166,29 @@ class _DiscriminatorStep(torch.autograd.Function):
                                           for g, need in zip(ctx.grads, ctx.needs_input_grad[3:]))
 
 
+class _AttachGradients(torch.autograd.Function):
+    """A value computed outside autograd together with its gradients: forward returns ``value``
+    unchanged, backward hands each input its kept gradient (cast and reshaped to the input's dtype
+    and shape) scaled by grad_output, on the device."""
+
+    @staticmethod
+    def forward(ctx, value, grads, *inputs):
+        ctx.grads = [g.to(x.dtype).reshape(x.shape) for g, x in zip(grads, inputs)]
+        return value.clone()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        return (None, None) + tuple(grad_output.to(g.dtype) * g if need else None
+                                    for g, need in zip(ctx.grads, ctx.needs_input_grad[2:]))
+
+
+def _attach(value: Tensor, pairs) -> Tensor:
+    """``value`` (no graph) with a grad_fn that reaches the inputs of ``pairs`` [(input, gradient)]."""
+    with torch.enable_grad():
+        return _AttachGradients.apply(value, [g for _, g in pairs], *[x for x, _ in pairs])
+
+
 class MultiScaleDiscriminator(nn.Module):
     """Multi-scale discriminator: seven Conv1d per scale, scale i on avg_pool1d(x, scales[i])."""
 
@@ -213,6 +267,18 @@ class MultiScaleDiscriminator(nn.Module):
     def _wants_backward(self) -> bool:
         return self.backward_enabled and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
 
+    def _wants_gradient(self, pred: Optional[Tensor]) -> bool:
+        """Whether a generator-side term of ``pred`` carries a graph: the switch, grad mode, and pred itself."""
+        return self.backward_enabled and torch.is_grad_enabled() and pred is not None and pred.requires_grad
+
+    def _gen_step(self, real: Optional[Tensor], fake: Tensor, w_adv: float, w_fm: float):
+        """``_sums(real, fake)`` (the same rows, from m2_disc_gen_step) and the gradient of w_adv *
+        generator loss + w_fm * feature-matching loss with respect to fake, float32 [B, 1, L]."""
+        _require(real, fake, what="AdversarialLoss")
+        with torch.no_grad():
+            rows, d_fake = self._handle(fake.device).gen_step(real, fake, w_adv, w_fm)
+            return self._columns(rows.sum(0)), d_fake
+
     def _step_loss(self, real: Tensor, fake: Tensor) -> Tensor:
         """The discriminator loss (0-dim float32) with a grad_fn that reaches the parameters."""
         _require(real, fake, what="AdversarialLoss")
@@ -253,12 +319,33 @@ class AdversarialLoss(nn.Module):
             return self.discriminator._discriminator_value(self.discriminator._sums(real_audio, fake_audio)).float()
 
     def generator_loss(self, fake_audio):
+        if self.discriminator._wants_gradient(fake_audio):
+            c, d_fake = self.discriminator._gen_step(None, fake_audio, 1.0, 0.0)
+            return _attach(self._generator(c).float(), [(fake_audio, d_fake)])
         with torch.no_grad():
             return self._generator(self.discriminator._sums(None, fake_audio)).float()
 
     def feature_matching_loss(self, real_audio, fake_audio):
+        if self.discriminator._wants_gradient(fake_audio):
+            c, d_fake = self.discriminator._gen_step(real_audio, fake_audio, 0.0, 1.0)
+            return _attach(self._feature_matching(c).float(), [(fake_audio, d_fake)])
         with torch.no_grad():
             return self._feature_matching(self.discriminator._sums(real_audio, fake_audio)).float()
+
+    def generator_terms(self, real_audio, fake_audio, adversarial_weight: float = 1.0,
+                        feature_matching_weight: float = 1.0):
+        """adversarial_weight * generator_loss + feature_matching_weight * feature_matching_loss as one
+        0-dim tensor from one pass over each signal; with a gradient (module docstring) one chain
+        through the discriminators serves both terms."""
+        aw, fw = float(adversarial_weight), float(feature_matching_weight)
+        grad = self.discriminator._wants_gradient(fake_audio)
+        if grad:
+            c, d_fake = self.discriminator._gen_step(real_audio, fake_audio, aw, fw)
+        with torch.no_grad():
+            if not grad:
+                c = self.discriminator._sums(real_audio, fake_audio)
+            value = (aw * self._generator(c) + fw * self._feature_matching(c)).float()
+        return _attach(value, [(fake_audio, d_fake)]) if grad else value
 
 
 class PerceptualLoss(nn.Module):
@@ -334,11 +421,43 @@ class CombinedTTSLoss(nn.Module):
             self.adversarial_loss = None
         self.training_step = 0
 
+    backward_enabled = False  # set by enable_backward(); a plain attribute, not in the state_dict
+    _warned_partial_total = False
+
     def enable_backward(self, enabled: bool = True):
-        """Switch the gradient of the discriminator step on or off (module docstring)."""
+        """Switch the gradients of the discriminator step and of the generator step on or off
+        (module docstring)."""
+        self.backward_enabled = bool(enabled)
         if self.adversarial_loss is not None:
             self.adversarial_loss.enable_backward(enabled)
         return self
+
+    def _wants_gradient(self, pred: Optional[Tensor]) -> bool:
+        on = self.backward_enabled or (self.adversarial_loss is not None and
+                                       self.adversarial_loss.discriminator.backward_enabled)
+        return on and torch.is_grad_enabled() and pred is not None and pred.requires_grad
+
+    @staticmethod
+    def _mel_gradient(mel_pred: Tensor, mel_target: Tensor, mel_lengths) -> Tensor:
+        """d _mel_loss / d mel_pred, float32 like mel_pred [B, Tp, M]: sign(pred - target) / (B M len_b)
+        on the first len_b of T = min(Tp, Tt) frames with lengths, sign(pred - target) / (B T M) without."""
+        B, Tp, M = mel_pred.shape
+        T = min(Tp, mel_target.shape[2])
+        sgn = torch.sign(mel_pred.detach()[:, :T].float() - mel_target.detach()[:, :, :T].transpose(1, 2).float())
+        g = torch.zeros(B, Tp, M, device=mel_pred.device, dtype=torch.float32)
+        if mel_lengths is None:
+            g[:, :T] = sgn / float(B * T * M)
+            return g
+        n = torch.as_tensor(mel_lengths).to(mel_pred.device).reshape(-1).clamp(min=0, max=T)
+        live = torch.arange(T, device=mel_pred.device)[None, :] < n[:, None]
+        g[:, :T] = torch.where(live[:, :, None], sgn / (float(B * M) * n.float())[:, None, None], torch.zeros_like(sgn))
+        return g
+
+    @staticmethod
+    def _duration_gradient(pred: Tensor, target: Tensor) -> Tensor:
+        """d _duration_loss / d pred: 2 (p - t) / n over the broadcast pair, summed back to pred's shape."""
+        p, t = torch.broadcast_tensors(pred.detach().float(), target.detach().float().to(pred.device))
+        return ((p - t) * (2.0 / max(p.numel(), 1))).sum_to_size(pred.shape)
 
     @staticmethod
     def _mel_loss(mel_pred: Tensor, mel_target: Tensor, mel_lengths) -> Tensor:
@@ -391,17 +510,28 @@ class CombinedTTSLoss(nn.Module):
             optimize_discriminator: compute the discriminator loss instead of the generator's
 
         Returns:
-            the loss components by name, 0-dim float32 tensors; without a graph, except the
-            discriminator_loss and total_loss of a discriminator step after enable_backward()
+            the loss components by name, 0-dim float32 tensors; without a graph, except after
+            enable_backward() the discriminator_loss and total_loss of a discriminator step and,
+            for predictions that require grad, the generator side (module docstring)
         """
         _require(mel_pred, mel_target, duration_pred, duration_target, audio_pred, audio_target,
                  what="CombinedTTSLoss")
         step = optimize_discriminator and self.adversarial_loss is not None and \
             self.adversarial_loss.discriminator._wants_backward()
+        # the gradient of each generator-side term, by name (filled below for the terms that get one)
+        gen = not optimize_discriminator  # the discriminator step's other entries stay plain values
+        wants = {"mel_loss": gen and self._wants_gradient(mel_pred),
+                 "duration_loss": gen and self._wants_gradient(duration_pred),
+                 "adversarial": gen and self._wants_gradient(audio_pred)}
+        grads: Dict[str, Tuple[Tensor, Tensor]] = {}
         with torch.no_grad():
             v: Dict[str, Tensor] = {}  # float64 on the device
             v["mel_loss"] = self._mel_loss(mel_pred, mel_target, mel_lengths)
             v["duration_loss"] = self._duration_loss(duration_pred, duration_target)
+            if wants["mel_loss"]:
+                grads["mel_loss"] = (mel_pred, self._mel_gradient(mel_pred, mel_target, mel_lengths))
+            if wants["duration_loss"]:
+                grads["duration_loss"] = (duration_pred, self._duration_gradient(duration_pred, duration_target))
             if audio_pred is not None and audio_target is not None:
                 p, t = _audio_pair(audio_pred, audio_target, "CombinedTTSLoss")
                 cache: dict = {}
@@ -417,10 +547,16 @@ class CombinedTTSLoss(nn.Module):
                             adv.discriminator._sums(real, fake))
                     else:
                         # one pass over each signal serves both terms (the reference runs fake twice)
-                        c = adv.discriminator._sums(real, fake)
+                        if wants["adversarial"]:  # the same rows, and the weighted pair's gradient
+                            c, d_fake = adv.discriminator._gen_step(real, fake, self.adversarial_loss_weight,
+                                                                    self.feature_matching_weight)
+                            grads["adversarial"] = (audio_pred, d_fake)
+                        else:
+                            c = adv.discriminator._sums(real, fake)
                         v["generator_loss"] = adv._generator(c)
                         v["feature_matching_loss"] = adv._feature_matching(c)
 
+            weights = {"mel_loss": self.mel_loss_weight, "duration_loss": self.duration_loss_weight}
             if optimize_discriminator and "discriminator_loss" in v:
                 total = v["discriminator_loss"]
             else:
@@ -431,8 +567,25 @@ class CombinedTTSLoss(nn.Module):
                                      ("feature_matching_loss", self.feature_matching_weight)):
                     if name in v:
                         total = total + weight * v[name]
+                        weights[name] = weight
             v["total_loss"] = total
             losses = {k: x.float() for k, x in v.items()}
+            pairs = [(x, weights[k] * g) for k, (x, g) in grads.items() if k in weights and weights[k] != 0]
+            if "adversarial" in grads:
+                pairs.append(grads["adversarial"])
+        if grads:
+            for k in ("mel_loss", "duration_loss"):
+                if k in grads:
+                    losses[k] = _attach(losses[k], [grads[k]])
+            have = {"mel_loss": "mel_loss", "duration_loss": "duration_loss", "generator_loss": "adversarial",
+                    "feature_matching_loss": "adversarial"}
+            missing = [k for k, w in weights.items() if w != 0 and have.get(k) not in grads]
+            if not missing:
+                losses["total_loss"] = _attach(losses["total_loss"], pairs)
+            elif not self._warned_partial_total:
+                self._warned_partial_total = True
+                logger.warning("CombinedTTSLoss: total_loss carries no graph: %s has no gradient here "
+                               "(backward() through the other entries is available)", ", ".join(missing))
         self.training_step += 1
         return losses
 

@@ -13,7 +13,11 @@ discriminator_loss(...).backward() against the forward-only discriminator_loss
 call of the same process (step_over_forward), and the two MFMA gradients of the
 same two layers on their own: the weight gradient (its split-K kernel and the
 fixed-order finish), and the data gradient as the difference between a call
-that computes both and one that computes the weight gradient alone.  Each
+that computes both and one that computes the weight gradient alone.  The
+generator step is the generator-mode call again with the three predictions
+requiring grad (generator_step_ms, against generator_ms: generator_step_over_forward),
+generator_terms(...).backward(), m2_disc_gen_step alone, and the first-layer
+audio gradient kernel summed over the three scales.  Each
 figure is the median of --iters timed calls after --warmup untimed ones.
 """
 import argparse
@@ -91,6 +95,32 @@ def main():
         p.grad = None
     out["step_over_forward"] = out["discriminator_step_ms"] / out["discriminator_loss_forward_ms"]
     h = disc._handle(dev)
+    # the generator step: the same generator-mode call with the predictions requiring grad (one
+    # m2_disc_gen_step instead of m2_disc_losses, the mel and duration gradients), against generator_ms above
+    loss.enable_backward()
+    kg = dict(kw)
+    for k in ("mel_pred", "duration_pred", "audio_pred"):
+        kg[k] = kw[k].clone().requires_grad_()
+
+    def gen_step():
+        kg["audio_pred"].grad = None
+        adv.generator_terms(real, kg["audio_pred"], loss.adversarial_loss_weight,
+                            loss.feature_matching_weight).backward()
+
+    out["generator_step_ms"] = timed(lambda: loss(**kg, optimize_discriminator=False), args.warmup, args.iters)
+    out["generator_step_over_forward"] = out["generator_step_ms"] / out["generator_ms"]
+    out["generator_terms_backward_ms"] = timed(gen_step, args.warmup, args.iters)
+    loss.enable_backward(False)
+    out["gen_step_ms"] = timed(lambda: h.gen_step(real, fake, loss.adversarial_loss_weight,
+                                                  loss.feature_matching_weight), args.warmup, args.iters)
+    from m2amd import ops
+    w0 = disc.discriminators[0][0].weight.detach()
+    audio_ms = 0.0
+    for pool in disc.scales:  # the first-layer data gradient down to the samples, once per scale as in the step
+        dy0 = torch.randn(B, 64, L // pool, device=dev)
+        audio_ms += timed(lambda: ops.conv1d_audio_backward(dy0, w0, L, padding=7, pool=pool), args.warmup, args.iters)
+    out["audio_gradient_ms"] = audio_ms
+    out["audio_gradient_share_of_gen_step"] = audio_ms / out["gen_step_ms"]
     shapes = h.shapes(L)[0]
     for name, layer in (("grouped_64_128_k41", 1), ("dense_1024_1024_k5", 5)):
         cin, cout, k, _, _, groups = h.LAYER_TABLE[layer]
