@@ -423,7 +423,9 @@ int32_t m2_mel_spectrogram(const m2_dsp* dsp, const float* audio, int32_t B, int
  * atomic is an integer max).  M2_E_SHAPE: an L_b of 0, a T_out smaller than
  * the largest stored count, or total samples or n_mels x total frames
  * reaching 2^31 (split the corpus into several calls).
- * Scratch: m2_mel_features_ragged_workspace_bytes(B, total samples). */
+ * Scratch: m2_mel_features_ragged_workspace_bytes(B, total samples).  Like
+ * every *_workspace_bytes of the DSP, evaluation and loss calls below, the
+ * returned size is exact up to 256 bytes of slack. */
 #define M2_SAMPLES_F32 0
 #define M2_SAMPLES_I16 1
 size_t m2_mel_features_ragged_workspace_bytes(const m2_dsp* dsp, int32_t B, int64_t total_samples);
@@ -616,6 +618,7 @@ int32_t m2_disc_layer_shape(const m2_disc* disc, int32_t L, int32_t scale_index,
                             int32_t* length);
 int32_t m2_disc_layer(const m2_disc* disc, int32_t scale_index, int32_t layer, const float* x, int32_t B, int32_t L,
                       float* y, void* stream);
+/* The *_workspace_bytes below: the returned size is exact up to 256 bytes of slack. */
 size_t m2_disc_forward_workspace_bytes(const m2_disc* disc, int32_t B, int32_t L);
 int32_t m2_disc_forward(const m2_disc* disc, const float* x, int32_t B, int32_t L, float* logits, float* features,
                         void* workspace, size_t workspace_bytes, void* stream);

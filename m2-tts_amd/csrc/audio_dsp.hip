@@ -498,6 +498,52 @@ int32_t nnls_magnitudes(const m2_dsp* d, const float* mel, int B, int T, int ite
     M2_LAUNCHED("nnls_finish_kernel");
     return M2_OK;
 }
+
+// The workspace layouts, each written once: over a Sizer for the _workspace_bytes function, over
+// a Carve for the call.
+
+// m2_mel_features_ragged; the frames of the whole batch are at most B + total_samples / hop.
+struct RaggedBufs {
+    int64_t* fp;     // frame prefix
+    unsigned* peak;  // peaks (float bits)
+    float* raw;      // mel powers
+};
+template <typename A>
+void carve_ragged(A& a, const m2_dsp* d, int B, int64_t total_samples, RaggedBufs* out) {
+    int64_t* fp = a.template take<int64_t>((size_t)B + 1);
+    unsigned* peak = a.template take<unsigned>((size_t)B);
+    float* raw = a.template take<float>((size_t)d->n_mels * ((size_t)B + (size_t)(total_samples / d->hop)));
+    if (out) *out = RaggedBufs{fp, peak, raw};
+}
+
+// nnls_magnitudes' scratch: per-frame projected-gradient maxima.
+template <typename A>
+void carve_nnls(A& a, int B, int T, float** pg) {
+    float* p = a.template take<float>((size_t)B * T);
+    if (pg) *pg = p;
+}
+
+// m2_griffin_lim; the NNLS scratch is counted whether the magnitudes come from mel or are given.
+struct GriffinLimBufs {
+    float* S;      // magnitudes
+    float2* ang;   // angles
+    float2* prev;  // previous rebuilt spectrum
+    float* fr;     // windowed inverse frames
+    float* y;      // the signal of each iteration
+    float* pg;
+};
+template <typename A>
+void carve_griffin_lim(A& a, const m2_dsp* d, int B, int T, GriffinLimBufs* out) {
+    const size_t F = d->n_fft / 2 + 1, Lout = (size_t)d->hop * (T > 0 ? T - 1 : 0);
+    GriffinLimBufs b;
+    b.S = a.template take<float>((size_t)B * T * F);
+    b.ang = a.template take<float2>((size_t)B * T * F);
+    b.prev = a.template take<float2>((size_t)B * T * F);
+    b.fr = a.template take<float>((size_t)B * T * d->n_fft);
+    b.y = a.template take<float>((size_t)B * std::max<size_t>(Lout, 1));
+    carve_nnls(a, B, T, &b.pg);
+    if (out) *out = b;
+}
 }  // namespace
 
 extern "C" {
@@ -642,13 +688,10 @@ int32_t m2_mel_spectrogram(const m2_dsp* d, const float* audio, int32_t B, int32
     return M2_OK;
 }
 
-// Frames of the whole batch are at most B + total_samples / hop.
 size_t m2_mel_features_ragged_workspace_bytes(const m2_dsp* d, int32_t B, int64_t total_samples) {
     if (!d || B < 0 || total_samples < 0) return 0;
     Sizer s;
-    s.take<int64_t>((size_t)B + 1);                                           // frame prefix
-    s.take<unsigned>((size_t)B);                                              // peaks (float bits)
-    s.take<float>((size_t)d->n_mels * ((size_t)B + (size_t)(total_samples / d->hop)));  // mel powers
+    carve_ragged(s, d, B, total_samples, nullptr);
     return s.off + 256;
 }
 
@@ -677,29 +720,28 @@ int32_t m2_mel_features_ragged(const m2_dsp* d, const void* samples, int32_t sam
                    "m2_mel_features_ragged: n_mels x frames reaches 2^31 in one call");
     M2_CHECK_SHAPE(T_out >= keep_max, "m2_mel_features_ragged: T_out is smaller than the largest stored frame count");
     Carve c(workspace, workspace_bytes);
-    int64_t* fp = c.take<int64_t>((size_t)B + 1);
-    unsigned* peak = c.take<unsigned>((size_t)B);
-    float* raw = c.take<float>((size_t)d->n_mels * (size_t)frames);
+    RaggedBufs w;
+    carve_ragged(c, d, B, total, &w);
     if (!c.ok) return fail(M2_E_WORKSPACE, "m2_mel_features_ragged: workspace too small");
     hipStream_t st = static_cast<hipStream_t>(stream);
     const dsp::RaggedSamples smp{samples, sample_format};
-    hipLaunchKernelGGL(dsp::ragged_prep_kernel, dim3(1), dim3(dsp::kPrepNT), 0, st, offsets, B, d->hop, max_frames, fp,
-                       peak, out_frames);
+    hipLaunchKernelGGL(dsp::ragged_prep_kernel, dim3(1), dim3(dsp::kPrepNT), 0, st, offsets, B, d->hop, max_frames, w.fp,
+                       w.peak, out_frames);
     M2_LAUNCHED("ragged_prep_kernel");
     if (normalize) {
         hipLaunchKernelGGL(dsp::ragged_peak_kernel, dim3((unsigned)((total + dsp::kPeakChunk - 1) / dsp::kPeakChunk)),
-                           dim3(dsp::NT), 0, st, smp, offsets, B, peak);
+                           dim3(dsp::NT), 0, st, smp, offsets, B, w.peak);
         M2_LAUNCHED("ragged_peak_kernel");
     }
 #define M2_RFRAME(NN)                                                                                             \
     hipLaunchKernelGGL((dsp::ragged_frame_kernel<NN>), dim3((unsigned)frames), dim3(dsp::NT), 0, st, smp, offsets, \
-                       fp, B, d->hop, normalize ? peak : nullptr, d->win, d->tw, d->W, d->lo, d->hi, d->n_mels, raw)
+                       w.fp, B, d->hop, normalize ? w.peak : nullptr, d->win, d->tw, d->W, d->lo, d->hi, d->n_mels, w.raw)
     if (d->n_fft == 512) M2_RFRAME(512);
     else if (d->n_fft == 1024) M2_RFRAME(1024);
     else M2_RFRAME(2048);
 #undef M2_RFRAME
     M2_LAUNCHED("ragged_frame_kernel");
-    hipLaunchKernelGGL(dsp::ragged_db_norm_kernel, dim3(B), dim3(1024), 0, st, raw, fp, d->n_mels, out_frames, T_out,
+    hipLaunchKernelGGL(dsp::ragged_db_norm_kernel, dim3(B), dim3(1024), 0, st, w.raw, w.fp, d->n_mels, out_frames, T_out,
                        out_mel);
     M2_LAUNCHED("ragged_db_norm_kernel");
     return M2_OK;
@@ -707,7 +749,9 @@ int32_t m2_mel_features_ragged(const m2_dsp* d, const void* samples, int32_t sam
 
 size_t m2_mel_to_magnitude_workspace_bytes(const m2_dsp* d, int32_t B, int32_t T) {
     if (!d || B < 0 || T < 0) return 0;
-    return ((size_t)B * T * sizeof(float) + 255) / 256 * 256 + 256;
+    Sizer s;
+    carve_nnls(s, B, T, nullptr);
+    return s.off + 256;
 }
 
 int32_t m2_mel_to_magnitude(const m2_dsp* d, const float* mel, int32_t B, int32_t T, int32_t nnls_iters,
@@ -716,21 +760,16 @@ int32_t m2_mel_to_magnitude(const m2_dsp* d, const float* mel, int32_t B, int32_
                  "m2_mel_to_magnitude: bad argument");
     if (B == 0 || T == 0) return M2_OK;
     Carve c(workspace, workspace_bytes);
-    float* pg = c.take<float>((size_t)B * T);
+    float* pg;
+    carve_nnls(c, B, T, &pg);
     if (!c.ok) return fail(M2_E_WORKSPACE, "m2_mel_to_magnitude: workspace too small");
     return nnls_magnitudes(d, mel, B, T, nnls_iters, out_mag, pg, static_cast<hipStream_t>(stream));
 }
 
 size_t m2_griffin_lim_workspace_bytes(const m2_dsp* d, int32_t B, int32_t T) {
     if (!d || B < 0 || T < 0) return 0;
-    const int F = d->n_fft / 2 + 1, Lout = d->hop * (T > 0 ? T - 1 : 0);
     Sizer s;
-    s.take<float>((size_t)B * T * F);           // magnitudes
-    s.take<float2>((size_t)B * T * F);          // angles
-    s.take<float2>((size_t)B * T * F);          // previous rebuilt spectrum
-    s.take<float>((size_t)B * T * d->n_fft);    // windowed inverse frames
-    s.take<float>((size_t)B * (Lout > 0 ? Lout : 1));  // the signal of each iteration
-    s.take<float>((size_t)B * T);               // NNLS: per-frame projected-gradient maxima
+    carve_griffin_lim(s, d, B, T, nullptr);
     return s.off + 256;
 }
 
@@ -745,13 +784,11 @@ int32_t m2_griffin_lim(const m2_dsp* d, const float* mel, const float* mag, cons
     M2_CHECK_ARG((mel || mag) && init_angles && out_audio, "m2_griffin_lim: bad argument");
     const int N = d->n_fft, F = N / 2 + 1, Lout = d->hop * (T - 1);
     Carve c(workspace, workspace_bytes);
-    float* S = c.take<float>((size_t)B * T * F);
-    float2* ang = c.take<float2>((size_t)B * T * F);
-    float2* prev = c.take<float2>((size_t)B * T * F);
-    float* fr = c.take<float>((size_t)B * T * N);
-    float* y = c.take<float>((size_t)B * Lout);
-    float* pgw = mag ? nullptr : c.take<float>((size_t)B * T);
+    GriffinLimBufs w;
+    carve_griffin_lim(c, d, B, T, &w);
     if (!c.ok) return fail(M2_E_WORKSPACE, "m2_griffin_lim: workspace too small");
+    float *S = w.S, *fr = w.fr, *y = w.y, *pgw = w.pg;
+    float2 *ang = w.ang, *prev = w.prev;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 fgrid(T, B);
     if (mag) {

@@ -278,6 +278,15 @@ using namespace m2;
 constexpr int kMaxGridY = 65535;
 
 int chunks_of(int Lp) { return cdiv(Lp, eval::kChunk); }
+
+// m2_eval_audio's workspace, written once: the partials of eval_frame_kernel [B, frames, kFramePart]
+// and of eval_time_kernel [B, chunks, kChunkPart].
+template <typename A>
+void carve_eval_audio(A& a, const m2_dsp* d, int B, int Lp, double** fpart, double** cpart) {
+    double* f = a.template take<double>((size_t)B * (1 + Lp / d->hop) * eval::kFramePart);
+    double* c = a.template take<double>((size_t)B * chunks_of(Lp) * eval::kChunkPart);
+    if (fpart) *fpart = f, *cpart = c;
+}
 }  // namespace
 
 extern "C" {
@@ -294,8 +303,7 @@ const char* m2_eval_column_name(int32_t kind, int32_t index) {
 size_t m2_eval_audio_workspace_bytes(const m2_dsp* d, int32_t B, int32_t Lp) {
     if (!d || B < 0 || Lp < 0) return 0;
     Sizer s;
-    s.take<double>((size_t)B * (1 + Lp / d->hop) * eval::kFramePart);
-    s.take<double>((size_t)B * chunks_of(Lp) * eval::kChunkPart);
+    carve_eval_audio(s, d, B, Lp, nullptr, nullptr);
     return s.off + 256;
 }
 
@@ -308,8 +316,8 @@ int32_t m2_eval_audio(const m2_dsp* d, const float* pred, const float* target, i
     const int frames = 1 + Lp / d->hop, frames_pair = target ? 1 + L / d->hop : 0, chunks = chunks_of(Lp);
     if (!target) Lt = 0;
     Carve c(workspace, workspace_bytes);
-    double* fpart = c.take<double>((size_t)B * frames * eval::kFramePart);
-    double* cpart = c.take<double>((size_t)B * chunks * eval::kChunkPart);
+    double *fpart, *cpart;
+    carve_eval_audio(c, d, B, Lp, &fpart, &cpart);
     if (!c.ok) return fail(M2_E_WORKSPACE, "m2_eval_audio: workspace too small");
     hipStream_t st = static_cast<hipStream_t>(stream);
 #define M2_EVAL(NN)                                                                                                   \

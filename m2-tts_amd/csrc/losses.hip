@@ -49,6 +49,7 @@
 #include <vector>
 
 #include "audio_dsp.h"
+#include "losses_plan.h"
 
 namespace m2 {
 namespace loss {
@@ -56,27 +57,7 @@ namespace loss {
 using dsp::block_sum;
 using dsp::NT;
 
-struct ConvGeo {
-    int Cin, Cout, k, stride, pad, groups;
-};
-
-constexpr int kNP = 64;          // output positions per conv_mfma workgroup
-constexpr int kCoWg = 64;        // output channels per conv_mfma workgroup (4 waves x 16)
-constexpr int kCch = 16;         // input channels staged in LDS per step
-constexpr int kMaxLds = 48 * 1024;
-constexpr int kMaxGrid = 65535;
-
-constexpr int kLayers = 7;
-constexpr int kFeat = 6;         // layers whose output is a feature map (more than one channel)
-constexpr int kMaxScales = 8;
-const ConvGeo kDisc[kLayers] = {{1, 64, 15, 1, 7, 1},       {64, 128, 41, 4, 20, 4},     {128, 256, 41, 4, 20, 16},
-                                {256, 512, 41, 4, 20, 64},  {512, 1024, 41, 4, 20, 256}, {1024, 1024, 5, 1, 2, 1},
-                                {1024, 1, 3, 1, 1, 1}};
 constexpr float kDiscSlope = 0.2f;
-
-constexpr int kRedChunk = 16384;  // elements per reduce_part_kernel workgroup
-constexpr int kRedPart = 4;
-constexpr size_t kSliceBytes = (size_t)1 << 30;  // activation bytes a batch slice may take (m2_disc_set_slice_bytes)
 
 constexpr int kSpecPart = 3;  // per frame: sum | |P| - |T| |, sum |angle P - angle T|, the perceptual term
 const char* const kSpecCols[] = {"mag_abs", "phase_abs", "bins", "mel_log_abs", "frames"};
@@ -85,17 +66,6 @@ constexpr int kSpecK = sizeof(kSpecCols) / sizeof(kSpecCols[0]);
 constexpr int kDiscScaleK = 5 + 2 * kFeat;
 constexpr int kDiscScales = 3;
 constexpr int kDiscK = kDiscScales * kDiscScaleK;
-
-__host__ __device__ inline int conv_out_len(int L, const ConvGeo& g) { return (L + 2 * g.pad - g.k) / g.stride + 1; }
-inline int span_of(const ConvGeo& g) { return (kNP - 1) * g.stride + g.k; }
-inline int spanp_of(const ConvGeo& g) { return span_of(g) | 1; }
-
-enum Path { PATH_DIRECT = 0, PATH_MFMA = 1, PATH_WAVE = 2 };
-inline Path conv_path(const ConvGeo& g) {
-    const int K = g.Cin / g.groups * g.k;
-    if (g.Cout >= 16 && K >= 32 && (size_t)kCch * spanp_of(g) * sizeof(float) <= (size_t)kMaxLds) return PATH_MFMA;
-    return K >= 256 ? PATH_WAVE : PATH_DIRECT;
-}
 
 __device__ __forceinline__ float leaky(float v, float slope) { return v > 0.f ? v : v * slope; }
 
@@ -320,14 +290,6 @@ __global__ __launch_bounds__(NT) void reduce_finish_kernel(const double* __restr
 // ---- backward of y = conv(leaky(x_pre, in_slope), w) + b ---------------------------
 // Weight element (co, ci in group, tap) is at w[co sCo + ci sCi + tap sK] as in
 // conv_mfma_kernel.  dw and the split-K partials are in PyTorch's [Cout, Cin/g, k].
-
-constexpr int kDxM = 64;         // column positions per conv_dx_mfma workgroup (4 tiles of 16)
-constexpr int kTc = 64;          // output positions staged per conv_dw_mfma step
-constexpr int kDwTiles = 11;     // 16-column tiles per wave of conv_dw_mfma
-constexpr int kDwCols = 4 * 16 * kDwTiles;  // (input channel, tap) columns per workgroup
-constexpr int kDwCiMax = 64;     // input channels per conv_dw_mfma workgroup
-constexpr int kMaxSplits = 64;   // split-K partials of one weight gradient
-constexpr size_t kPartFloats = (size_t)8 << 20;  // floats the partials of one layer may take (beyond one copy of dw)
 
 __device__ __forceinline__ float leaky_grad(float v, float slope) { return v > 0.f ? 1.f : slope; }
 
@@ -598,7 +560,6 @@ __global__ __launch_bounds__(256) void fm_cotangent_kernel(const float* __restri
 // hands in LDS, so that consecutive threads write consecutive samples: sample
 // i gets acc[i / pool] / pool, overwritten or, with `accumulate`, added to; the
 // samples floor pooling dropped (i >= pool Lp) are zeroed or left alone.
-constexpr int kAuP = 256;
 __global__ __launch_bounds__(kAuP) void conv_dx_audio_kernel(const float* __restrict__ dy, const float* __restrict__ w,
                                                              float* __restrict__ dx, int Cout, int k, int pad, int pool,
                                                              int L, int Lp, int Lo, int accumulate) {
@@ -740,15 +701,14 @@ bool geo_ok(const ConvGeo& g) {
 // One layer over nb utterances; packed: w is [k, Cin/g, Cout] (MFMA path only).
 int32_t launch_conv(const float* x, const float* w, const float* b, float* y, const ConvGeo& g, int nb, int Lraw,
                     int pool, bool packed, float in_slope, float slope, hipStream_t st) {
-    const int L = Lraw / pool, Lo = loss::conv_out_len(L, g), Cg = g.Cin / g.groups;
+    const int L = Lraw / pool, Lo = loss::conv_out_len(L, g);
     const loss::Path path = loss::conv_path(g);
     if (pool != 1 && path != loss::PATH_DIRECT) return fail(M2_E_INTERNAL, "launch_conv: only the direct kernel pools");
     if (path == loss::PATH_MFMA) {
-        const long long sCo = packed ? 1 : (long long)Cg * g.k, sCi = packed ? g.Cout : g.k,
-                        sK = packed ? (long long)Cg * g.Cout : 1;
+        const loss::WStride ws = loss::w_stride(g, packed);
         const dim3 grid(cdiv(Lo, loss::kNP), cdiv(g.Cout, loss::kCoWg), nb);
         hipLaunchKernelGGL(loss::conv_mfma_kernel, grid, dim3(256), loss::kCch * loss::spanp_of(g) * sizeof(float), st,
-                           x, w, b, y, g, L, Lo, sCo, sCi, sK, in_slope, slope);
+                           x, w, b, y, g, L, Lo, ws.sCo, ws.sCi, ws.sK, in_slope, slope);
         M2_LAUNCHED("conv_mfma_kernel");
     } else if (path == loss::PATH_WAVE) {
         hipLaunchKernelGGL(loss::conv_wave_kernel, dim3(cdiv(Lo, 4), g.Cout, nb), dim3(256), 0, st, x, w, b, y, g, L,
@@ -762,33 +722,19 @@ int32_t launch_conv(const float* x, const float* w, const float* b, float* y, co
     return M2_OK;
 }
 
-// Output lengths of the seven layers of the discriminator at `scale`; false when the pooled input is empty.
-bool disc_lengths(int L, int scale, int len[kLayers]) {
-    int l = L / scale;
-    if (l < 1) return false;
-    for (int i = 0; i < kLayers; ++i) len[i] = l = loss::conv_out_len(l, kDisc[i]);
-    return true;
+// The handle keeps the weights of the layers on the MFMA path packed as [k, Cin/g, Cout].
+bool disc_packed(int layer) { return loss::conv_path(kDisc[layer]) == loss::PATH_MFMA; }
+float disc_in_slope(int layer) { return layer > 0 ? loss::kDiscSlope : 1.f; }
+
+loss::DiscPlan disc_plan(const m2_disc* d, int B, int L, loss::DiscMode mode) {
+    return loss::disc_plan(d->scales, d->n_scales, d->slice_bytes, B, L, mode);
 }
 
-// floats of the seven outputs of one utterance at `scale`
-size_t disc_floats(int L, int scale) {
-    int len[kLayers];
-    if (!disc_lengths(L, scale, len)) return 0;
-    size_t n = 0;
-    for (int i = 0; i < kLayers; ++i) n += align_up((size_t)kDisc[i].Cout * len[i], 64);
-    return n;
-}
-
-size_t disc_floats_max(const m2_disc* d, int L) {
-    size_t n = 0;
-    for (int s = 0; s < d->n_scales; ++s) n = std::max(n, disc_floats(L, d->scales[s]));
-    return n;
-}
-
-int slice_of(const m2_disc* d, size_t floats_per_utt, int copies, int B) {
-    const size_t per = std::max<size_t>(1, floats_per_utt * copies * sizeof(float));
-    const size_t n = d->slice_bytes / per;
-    return (int)std::max<size_t>(1, std::min<size_t>(n, (size_t)std::max(B, 1)));
+size_t disc_bytes(const m2_disc* d, int B, int L, loss::DiscMode mode) {
+    if (!d || B < 0 || L <= 0) return 0;
+    Sizer s;
+    loss::carve_disc(s, disc_plan(d, B, L, mode), nullptr);
+    return s.off + 256;
 }
 
 // The seven layers of scale s over nb utterances of x [nb, 1, L]; out[i] receives layer i.
@@ -796,9 +742,8 @@ int32_t run_scale(const m2_disc* d, int s, const float* x, int nb, int L, float*
     int Lraw = L, pool = d->scales[s];
     const float* in = x;
     for (int i = 0; i < kLayers; ++i) {
-        const bool packed = loss::conv_path(kDisc[i]) == loss::PATH_MFMA;
-        const int32_t rc = launch_conv(in, d->w[s][i], d->b[s][i], out[i], kDisc[i], nb, Lraw, pool, packed,
-                                       i > 0 ? loss::kDiscSlope : 1.f, 1.f, st);
+        const int32_t rc = launch_conv(in, d->w[s][i], d->b[s][i], out[i], kDisc[i], nb, Lraw, pool, disc_packed(i),
+                                       disc_in_slope(i), 1.f, st);
         if (rc != M2_OK) return rc;
         Lraw = loss::conv_out_len(Lraw / pool, kDisc[i]);
         pool = 1;
@@ -808,48 +753,6 @@ int32_t run_scale(const m2_disc* d, int s, const float* x, int nb, int L, float*
 }
 
 // ---- backward ----------------------------------------------------------------------
-
-// How the weight gradient of one layer over nb utterances is computed.
-struct DwPlan {
-    bool mfma = false;
-    int nciB = 0, blocks = 0, splits = 1, cps = 0;
-    size_t lds = 0, part_floats = 0;
-};
-
-DwPlan dw_plan(const ConvGeo& g, int nb, int L) {
-    DwPlan p;
-    const int Lo = loss::conv_out_len(L, g), Cg = g.Cin / g.groups, Mg = g.Cout / g.groups;
-    const long long chunks = (long long)nb * cdiv(Lo, loss::kTc);
-    const size_t n = (size_t)g.Cout * Cg * g.k;
-    if (g.Cout < 16 || g.k > loss::kDwCols || chunks > (1 << 30)) return p;
-    int umax = 0;  // the widest union of input channels over the 16-row tiles
-    for (int co0 = 0; co0 < g.Cout; co0 += 16)
-        umax = std::max(umax, (std::min(co0 + 15, g.Cout - 1) / Mg + 1 - co0 / Mg) * Cg);
-    const size_t spanp = (size_t)(((loss::kTc - 1) * g.stride + g.k) | 1), dys = 16 * (loss::kTc + 1);
-    if ((spanp + dys) * sizeof(float) > (size_t)loss::kMaxLds) return p;
-    const size_t fit = ((size_t)loss::kMaxLds / sizeof(float) - dys) / spanp;
-    p.nciB = (int)std::min<size_t>({(size_t)(loss::kDwCols / g.k), (size_t)loss::kDwCiMax, (size_t)umax, fit});
-    p.blocks = cdiv(umax, p.nciB);
-    if (p.blocks > loss::kMaxGrid) return p;
-    p.mfma = true;
-    p.lds = ((size_t)p.nciB * spanp + dys) * sizeof(float);
-    const size_t room = 1 + loss::kPartFloats / n;
-    p.splits = (int)std::max<long long>(1, std::min<long long>({chunks, (long long)loss::kMaxSplits, (long long)room}));
-    p.part_floats = (size_t)p.splits * n;  // before the rounding below: a bound that never shrinks as nb grows
-    p.cps = (int)((chunks + p.splits - 1) / p.splits);
-    p.splits = (int)((chunks + p.cps - 1) / p.cps);
-    return p;
-}
-
-// Phases of the stride one conv_dx_mfma workgroup takes (1, 2 or 4; its other waves take row tiles).
-int dx_phases(const ConvGeo& g) { return g.stride >= 4 ? 4 : g.stride >= 2 ? 2 : 1; }
-
-bool dx_mfma_ok(const ConvGeo& g) {
-    const size_t J = (size_t)cdiv(g.k, g.stride);
-    return loss::conv_path(g) == loss::PATH_MFMA && g.Cin >= 16 &&
-           (size_t)loss::kCch * ((loss::kDxM + J - 1) | 1) * sizeof(float) <= (size_t)loss::kMaxLds &&
-           (long long)cdiv(g.stride, dx_phases(g)) * cdiv(g.Cin, 64 / dx_phases(g)) <= loss::kMaxGrid;
-}
 
 // The gradients of one layer over nb utterances: x_pre [nb, Cin, L], dy [nb, Cout, Lo];
 // dx (or null) is overwritten; dw (or null: no weight gradient, no partials) and db (or null)
@@ -861,23 +764,20 @@ int32_t launch_conv_bwd(const float* x_pre, const float* w, const float* dy, con
     const int Lo = loss::conv_out_len(L, g), Cg = g.Cin / g.groups;
     const size_t n = (size_t)g.Cout * Cg * g.k;
     if (dx) {
-        const long long sCo = packed ? 1 : (long long)Cg * g.k, sCi = packed ? g.Cout : g.k,
-                        sK = packed ? (long long)Cg * g.Cout : 1;
-        if (dx_mfma_ok(g)) {
+        const loss::WStride ws = loss::w_stride(g, packed);
+        if (loss::dx_mfma_ok(g)) {
             const int J = cdiv(g.k, g.stride), M = (L - 1 + g.pad) / g.stride + 1;
-            const int pw = dx_phases(g);
-            const dim3 grid(cdiv(M, loss::kDxM), cdiv(g.stride, pw) * cdiv(g.Cin, 64 / pw), nb);
-            hipLaunchKernelGGL(loss::conv_dx_mfma_kernel, grid, dim3(256),
-                               loss::kCch * ((loss::kDxM + J - 1) | 1) * sizeof(float), st, x_pre, w, dy, dx, g, L, Lo,
-                               sCo, sCi, sK, in_slope, J, pw);
+            const dim3 grid(cdiv(M, loss::kDxM), (unsigned)loss::dx_grid_y(g), nb);
+            hipLaunchKernelGGL(loss::conv_dx_mfma_kernel, grid, dim3(256), loss::dx_lds_bytes(g), st, x_pre, w, dy, dx,
+                               g, L, Lo, ws.sCo, ws.sCi, ws.sK, in_slope, J, loss::dx_phases(g));
             M2_LAUNCHED("conv_dx_mfma_kernel");
         } else {
             hipLaunchKernelGGL(loss::conv_dx_direct_kernel, dim3(cdiv(L, 256), g.Cin, nb), dim3(256), 0, st, x_pre, w,
-                               dy, dx, g, L, Lo, sCo, sCi, sK, in_slope);
+                               dy, dx, g, L, Lo, ws.sCo, ws.sCi, ws.sK, in_slope);
             M2_LAUNCHED("conv_dx_direct_kernel");
         }
     }
-    const DwPlan p = dw ? dw_plan(g, nb, L) : DwPlan();
+    const loss::DwPlan p = dw ? loss::dw_plan(g, nb, L) : loss::DwPlan();
     if (dw && p.mfma) {
         hipLaunchKernelGGL(loss::conv_dw_mfma_kernel, dim3(p.blocks, cdiv(g.Cout, 16), p.splits), dim3(256), p.lds, st,
                            x_pre, dy, part, g, nb, L, Lo, in_slope, p.nciB, p.cps);
@@ -896,38 +796,6 @@ int32_t launch_conv_bwd(const float* x_pre, const float* w, const float* dy, con
         M2_LAUNCHED("conv_db_kernel");
     }
     return M2_OK;
-}
-
-// What m2_disc_step carves for a batch of B utterances of L samples, per utterance of a slice.
-struct StepPlan {
-    size_t per = 0;      // floats of the seven maps of one utterance and side
-    size_t cot = 0;      // floats of the widest map of one utterance: each of the two cotangent buffers
-    size_t pooled = 0;   // floats of the pooled audio of one utterance (scales above 1)
-    size_t part = 0;     // floats of the split-K partials
-    int nbs = 1, max_chunks = 1;
-};
-
-StepPlan step_plan(const m2_disc* d, int B, int L) {
-    StepPlan p;
-    p.per = disc_floats_max(d, L);
-    for (int s = 0; s < d->n_scales; ++s) {
-        int len[kLayers];
-        if (!disc_lengths(L, d->scales[s], len)) continue;
-        for (int i = 0; i < kLayers; ++i) p.cot = std::max(p.cot, align_up((size_t)kDisc[i].Cout * len[i], 64));
-        if (d->scales[s] > 1) p.pooled = std::max(p.pooled, align_up((size_t)(L / d->scales[s]), 64));
-    }
-    p.nbs = slice_of(d, p.per, 2, B);  // m2_disc_losses's slices: the bound counts the maps of both sides
-    p.max_chunks = cdiv((int)std::min<size_t>(p.per, (size_t)1 << 30), loss::kRedChunk) + 1;
-    for (int s = 0; s < d->n_scales; ++s) {
-        int l = L / d->scales[s];
-        if (l < 1) continue;
-        // the last slice may be shorter, and fewer utterances never take more partials
-        for (int i = 0; i < kLayers; ++i) {
-            p.part = std::max(p.part, dw_plan(kDisc[i], p.nbs, l).part_floats);
-            l = loss::conv_out_len(l, kDisc[i]);
-        }
-    }
-    return p;
 }
 
 // The forward half of one (slice, scale) of m2_disc_losses, shared with the two steps so that
@@ -966,19 +834,49 @@ int32_t scale_forward(const m2_disc* d, int s, const float* real, const float* f
 }
 
 // The first-layer data gradient down to the audio samples (conv_dx_audio_kernel's layout).
-bool audio_bwd_ok(int Cout, int k) {
-    return (long long)Cout * k <= (1 << 13) && k <= (1 << 12) &&
-           ((size_t)Cout * k + (size_t)loss::kCch * ((loss::kAuP + k - 1) | 1)) * sizeof(float) <= (size_t)loss::kMaxLds;
-}
-
 int32_t launch_audio_bwd(const float* dy, const float* w, int Cout, int k, int pad, int pool, int nb, int L,
                          bool accumulate, float* dx, hipStream_t st) {
     const int Lp = L / pool, Lo = Lp + 2 * pad - k + 1;
-    const size_t lds = ((size_t)Cout * k + (size_t)loss::kCch * ((loss::kAuP + k - 1) | 1)) * sizeof(float);
     hipLaunchKernelGGL(loss::conv_dx_audio_kernel, dim3((unsigned)(((long long)L + (long long)loss::kAuP * pool - 1) /
                                                                    ((long long)loss::kAuP * pool)), nb),
-                       dim3(loss::kAuP), lds, st, dy, w, dx, Cout, k, pad, pool, L, Lp, Lo, accumulate ? 1 : 0);
+                       dim3(loss::kAuP), loss::audio_lds_bytes(Cout, k), st, dy, w, dx, Cout, k, pad, pool, L, Lp, Lo,
+                       accumulate ? 1 : 0);
     M2_LAUNCHED("conv_dx_audio_kernel");
+    return M2_OK;
+}
+
+// One side of scale s backward over the nb utterances of a slice, while its maps are resident:
+// the logits' cotangent cscale (D - target), then layers kLayers - 1 .. lowest.  The cotangent of
+// a layer's output is in one of bufs.cot and that of its input goes to the other; *last (or null)
+// receives the one written last.  Layer i reads map[i - 1], layer 0 reads x0 [nb, 1, L0] and has
+// no data gradient.  grads (or null: data gradients only) are the scale's (weight, bias) pairs,
+// overwritten or, with `accumulate`, added to.  With w_fm != 0 the feature-matching term of map
+// i - 1 against fm_real[i - 1] joins that map's cotangent before the layer below reads it.
+int32_t backward_chain(const m2_disc* d, int s, float* const map[kLayers], const float* x0, int L0,
+                       const int len[kLayers], int nb, int B, double target, double cscale, int lowest,
+                       float* const* grads, bool accumulate, float* const fm_real[kLayers], double w_fm,
+                       const loss::DiscBufs& bufs, const float** last, hipStream_t st) {
+    const size_t nl = (size_t)nb * len[kLayers - 1];
+    hipLaunchKernelGGL(loss::logit_cotangent_kernel, dim3((unsigned)((nl + 255) / 256)), dim3(256), 0, st,
+                       map[kLayers - 1], nl, target, cscale, bufs.cot[0]);
+    M2_LAUNCHED("logit_cotangent_kernel");
+    int cur = 0;
+    for (int i = kLayers - 1; i >= lowest; --i) {
+        const int32_t rc = launch_conv_bwd(i > 0 ? map[i - 1] : x0, d->w[s][i], bufs.cot[cur], kDisc[i], nb,
+                                           i > 0 ? len[i - 1] : L0, disc_packed(i), disc_in_slope(i),
+                                           i > 0 ? bufs.cot[cur ^ 1] : nullptr, grads ? grads[2 * i] : nullptr,
+                                           grads ? grads[2 * i + 1] : nullptr, accumulate, bufs.part, st);
+        if (rc != M2_OK) return rc;
+        cur ^= 1;
+        if (i > 0 && w_fm != 0.0) {
+            const size_t per_utt = (size_t)kDisc[i - 1].Cout * len[i - 1], n = per_utt * nb;
+            const double fm = w_fm / ((double)(d->n_scales * kFeat) * (double)B * (double)per_utt);
+            hipLaunchKernelGGL(loss::fm_cotangent_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
+                               map[i - 1], fm_real[i - 1], n, (float)fm, bufs.cot[cur]);
+            M2_LAUNCHED("fm_cotangent_kernel");
+        }
+    }
+    if (last) *last = bufs.cot[cur];
     return M2_OK;
 }
 
@@ -987,6 +885,74 @@ bool disc_shape_ok(const m2_disc* d, int B, int L) {
     for (int s = 0; s < d->n_scales; ++s)
         if (L / d->scales[s] < 1) return false;
     return true;
+}
+
+// m2_disc_losses, m2_disc_step and m2_disc_gen_step (`who`, after its own argument checks): the
+// batch in slices, a slice scale by scale.  Each (slice, scale) runs scale_forward and then, while
+// the maps of both sides are in the workspace, the backward of the mode.  The discriminator step:
+// each side from its (pooled) audio through all seven layers, the 42 gradients overwritten by the
+// first (slice, side) and accumulated in stream order by the later ones.  The generator step: the
+// fake side with data gradients only down to layer 1, then the first layer fused with the adjoint
+// of the pooling; scale index 0 overwrites the slice's rows of d_fake and the later scales add.
+int32_t disc_walk(const m2_disc* d, loss::DiscMode mode, const char* who, const float* real, const float* fake, int B,
+                  int L, double w_adv, double w_fm, double* out, float* const* grads, float* d_fake, void* workspace,
+                  size_t workspace_bytes, hipStream_t st) {
+    const std::string name(who);
+    if (d->n_scales != loss::kDiscScales)
+        return fail(M2_E_SHAPE, (name + ": the rows are laid out for three scales").c_str());
+    if (!disc_shape_ok(d, B, L))
+        return fail(M2_E_SHAPE,
+                    (name + ": at most 65535 utterances of 2^28 samples, no shorter than the largest scale").c_str());
+    if (B == 0) return M2_OK;
+    const loss::DiscPlan pl = disc_plan(d, B, L, mode);
+    Carve c(workspace, workspace_bytes);
+    loss::DiscBufs bufs;
+    loss::carve_disc(c, pl, &bufs);
+    if (!c.ok) return fail(M2_E_WORKSPACE, (name + ": workspace too small").c_str());
+    for (int b0 = 0; b0 < B; b0 += pl.nbs) {
+        const int nb = std::min(pl.nbs, B - b0);
+        for (int s = 0; s < d->n_scales; ++s) {
+            int len[kLayers];
+            loss::disc_lengths(L, d->scales[s], len);
+            float* map[2][kLayers];
+            int32_t rc = scale_forward(d, s, real, fake, b0, nb, L, len, bufs.act, bufs.dpart, pl.max_chunks, out, map,
+                                       st);
+            if (rc != M2_OK) return rc;
+            const int Lp = L / d->scales[s];
+            const double logits = (double)B * (double)len[kLayers - 1] * (double)d->n_scales;
+            if (mode == loss::DISC_STEP) {
+                for (int side = 0; side < 2; ++side) {
+                    const float* x = (side ? fake : real) + (size_t)b0 * L;
+                    if (d->scales[s] > 1) {
+                        hipLaunchKernelGGL(loss::avg_pool_kernel, dim3(cdiv(Lp, 256), nb), dim3(256), 0, st, x, L,
+                                           d->scales[s], Lp, bufs.pooled);
+                        M2_LAUNCHED("avg_pool_kernel");
+                        x = bufs.pooled;
+                    }
+                    rc = backward_chain(d, s, map[side], x, Lp, len, nb, B, side ? 0.0 : 1.0, 2.0 / logits, 0,
+                                        grads + (size_t)s * kLayers * 2, b0 > 0 || side > 0, nullptr, 0.0, bufs,
+                                        nullptr, st);
+                    if (rc != M2_OK) return rc;
+                }
+            } else if (mode == loss::DISC_GEN_STEP) {
+                const float* dy0;
+                rc = backward_chain(d, s, map[1], nullptr, 0, len, nb, B, 1.0, w_adv * 2.0 / logits, 1, nullptr, false,
+                                    map[0], w_fm, bufs, &dy0, st);
+                if (rc != M2_OK) return rc;
+                rc = launch_audio_bwd(dy0, d->w[s][0], kDisc[0].Cout, kDisc[0].k, kDisc[0].pad, d->scales[s], nb, L,
+                                      s > 0, d_fake + (size_t)b0 * L, st);
+                if (rc != M2_OK) return rc;
+            }
+        }
+    }
+    return M2_OK;
+}
+
+// m2_loss_spectral's workspace: spectral_frame_kernel's partials, [B, frames, kSpecPart].
+template <typename A>
+void carve_spectral(A& a, const m2_dsp* d, int B, int L, double** part) {
+    double* p = a.template take<double>((size_t)B * (1 + L / d->hop) * loss::kSpecPart);
+    if (part) *part = p;
 }
 }  // namespace
 
@@ -1065,7 +1031,7 @@ int32_t m2_disc_create(const float* const* weights, int32_t count, const int32_t
             const int Cg = g.Cin / g.groups;
             const size_t nw = (size_t)g.Cout * Cg * g.k;
             const float* src = weights[(s * kLayers + i) * 2];
-            if (loss::conv_path(g) == loss::PATH_MFMA) {
+            if (disc_packed(i)) {
                 hipLaunchKernelGGL(loss::pack_weights_kernel, dim3((unsigned)std::min<size_t>(1024, (nw + 255) / 256)),
                                    dim3(256), 0, st, src, g.Cout, Cg, g.k, p);
                 e = hipGetLastError();
@@ -1109,7 +1075,7 @@ int32_t m2_disc_layer_shape(const m2_disc* d, int32_t L, int32_t scale_index, in
                      layer < kLayers,
                  "m2_disc_layer_shape: bad argument");
     int len[kLayers];
-    M2_CHECK_SHAPE(disc_lengths(L, d->scales[scale_index], len), "m2_disc_layer_shape: audio shorter than the scale");
+    M2_CHECK_SHAPE(loss::disc_lengths(L, d->scales[scale_index], len), "m2_disc_layer_shape: audio shorter than the scale");
     *channels = kDisc[layer].Cout;
     *length = len[layer];
     return M2_OK;
@@ -1123,14 +1089,11 @@ int32_t m2_disc_layer(const m2_disc* d, int32_t scale_index, int32_t layer, cons
     M2_CHECK_SHAPE(B <= loss::kMaxGrid && L <= (1 << 28), "m2_disc_layer: at most 65535 utterances of 2^28 samples");
     if (B == 0) return M2_OK;
     return launch_conv(x, d->w[scale_index][layer], d->b[scale_index][layer], y, kDisc[layer], B, L, 1,
-                       loss::conv_path(kDisc[layer]) == loss::PATH_MFMA, layer > 0 ? loss::kDiscSlope : 1.f, 1.f,
-                       static_cast<hipStream_t>(stream));
+                       disc_packed(layer), disc_in_slope(layer), 1.f, static_cast<hipStream_t>(stream));
 }
 
 size_t m2_disc_forward_workspace_bytes(const m2_disc* d, int32_t B, int32_t L) {
-    if (!d || B < 0 || L <= 0) return 0;
-    const size_t per = disc_floats_max(d, L);
-    return (size_t)slice_of(d, per, 1, B) * per * sizeof(float) + 256 * (kLayers + 1);
+    return disc_bytes(d, B, L, loss::DISC_FORWARD);
 }
 
 int32_t m2_disc_forward(const m2_disc* d, const float* x, int32_t B, int32_t L, float* logits, float* features,
@@ -1140,26 +1103,24 @@ int32_t m2_disc_forward(const m2_disc* d, const float* x, int32_t B, int32_t L, 
                    "m2_disc_forward: at most 65535 utterances of 2^28 samples, no shorter than the largest scale");
     if (B == 0) return M2_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const int nbs = slice_of(d, disc_floats_max(d, L), 1, B);
+    const loss::DiscPlan pl = disc_plan(d, B, L, loss::DISC_FORWARD);
     Carve c(workspace, workspace_bytes);
-    float* ws[kLayers];
-    {
-        int len[kLayers];
-        size_t mx[kLayers] = {};
-        for (int s = 0; s < d->n_scales; ++s) {
-            disc_lengths(L, d->scales[s], len);
-            for (int i = 0; i < kLayers; ++i) mx[i] = std::max(mx[i], (size_t)kDisc[i].Cout * len[i]);
-        }
-        for (int i = 0; i < kLayers; ++i) ws[i] = (features && i < kFeat) || i == kLayers - 1 ? nullptr : c.take<float>(mx[i] * nbs);
-        if (!c.ok) return fail(M2_E_WORKSPACE, "m2_disc_forward: workspace too small");
+    loss::DiscBufs bufs;
+    loss::carve_disc(c, pl, &bufs);
+    if (!c.ok) return fail(M2_E_WORKSPACE, "m2_disc_forward: workspace too small");
+    float* ws[kLayers];  // layer i of a slice when the caller does not ask for it: the widest of the scales
+    float* p = bufs.act[0];
+    for (int i = 0; i < kLayers; ++i) {
+        ws[i] = p;
+        p += align_up(pl.layer[i], 64) * pl.nbs;
     }
-    for (int b0 = 0; b0 < B; b0 += nbs) {
-        const int nb = std::min(nbs, B - b0);
+    for (int b0 = 0; b0 < B; b0 += pl.nbs) {
+        const int nb = std::min(pl.nbs, B - b0);
         float* lg = logits;
         float* ft = features;
         for (int s = 0; s < d->n_scales; ++s) {
             int len[kLayers];
-            disc_lengths(L, d->scales[s], len);
+            loss::disc_lengths(L, d->scales[s], len);
             float* out[kLayers];
             for (int i = 0; i < kLayers; ++i) {
                 const size_t n = (size_t)kDisc[i].Cout * len[i];
@@ -1181,40 +1142,14 @@ int32_t m2_disc_forward(const m2_disc* d, const float* x, int32_t B, int32_t L, 
 }
 
 size_t m2_disc_losses_workspace_bytes(const m2_disc* d, int32_t B, int32_t L) {
-    if (!d || B < 0 || L <= 0) return 0;
-    const size_t per = disc_floats_max(d, L);
-    const int nbs = slice_of(d, per, 2, B);
-    const size_t chunks = (size_t)cdiv((int)std::min<size_t>(per, (size_t)1 << 30), loss::kRedChunk) + 1;
-    return (size_t)nbs * per * 2 * sizeof(float) + (size_t)nbs * kLayers * chunks * loss::kRedPart * sizeof(double) +
-           256 * 4;
+    return disc_bytes(d, B, L, loss::DISC_LOSSES);
 }
 
 int32_t m2_disc_losses(const m2_disc* d, const float* real, const float* fake, int32_t B, int32_t L, double* out,
                        void* workspace, size_t workspace_bytes, void* stream) {
     M2_CHECK_ARG(d && (real || fake) && out && B >= 0 && L > 0, "m2_disc_losses: bad argument");
-    M2_CHECK_SHAPE(d->n_scales == loss::kDiscScales, "m2_disc_losses: the rows are laid out for three scales");
-    M2_CHECK_SHAPE(disc_shape_ok(d, B, L),
-                   "m2_disc_losses: at most 65535 utterances of 2^28 samples, no shorter than the largest scale");
-    if (B == 0) return M2_OK;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const size_t per = disc_floats_max(d, L);
-    const int nbs = slice_of(d, per, 2, B);
-    const int max_chunks = cdiv((int)std::min<size_t>(per, (size_t)1 << 30), loss::kRedChunk) + 1;
-    Carve c(workspace, workspace_bytes);
-    float* act[2] = {c.take<float>((size_t)nbs * per), c.take<float>((size_t)nbs * per)};
-    double* part = c.take<double>((size_t)nbs * kLayers * max_chunks * loss::kRedPart);
-    if (!c.ok) return fail(M2_E_WORKSPACE, "m2_disc_losses: workspace too small");
-    for (int b0 = 0; b0 < B; b0 += nbs) {
-        const int nb = std::min(nbs, B - b0);
-        for (int s = 0; s < d->n_scales; ++s) {
-            int len[kLayers];
-            disc_lengths(L, d->scales[s], len);
-            float* map[2][kLayers];
-            const int32_t rc = scale_forward(d, s, real, fake, b0, nb, L, len, act, part, max_chunks, out, map, st);
-            if (rc != M2_OK) return rc;
-        }
-    }
-    return M2_OK;
+    return disc_walk(d, loss::DISC_LOSSES, "m2_disc_losses", real, fake, B, L, 0.0, 0.0, out, nullptr, nullptr,
+                     workspace, workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
 size_t m2_conv1d_strided_backward_workspace_bytes(int32_t ksize, int32_t stride, int32_t padding, int32_t groups,
@@ -1223,7 +1158,7 @@ size_t m2_conv1d_strided_backward_workspace_bytes(int32_t ksize, int32_t stride,
     if (B <= 0 || L <= 0 || Cin <= 0 || Cout <= 0 || ksize <= 0 || stride <= 0 || padding < 0 || groups <= 0 ||
         !geo_ok(g) || (long long)L + 2LL * padding < ksize)
         return 0;
-    return dw_plan(g, B, L).part_floats * sizeof(float) + 256;
+    return loss::dw_plan(g, B, L).part_floats * sizeof(float) + 256;
 }
 
 int32_t m2_conv1d_strided_backward(const float* x_pre, const float* w, const float* dy, int32_t ksize, int32_t stride,
@@ -1249,76 +1184,22 @@ int32_t m2_conv1d_strided_backward(const float* x_pre, const float* w, const flo
         return M2_OK;
     }
     Carve c(workspace, workspace_bytes);
-    const size_t pf = dw_plan(g, B, L).part_floats;
+    const size_t pf = loss::dw_plan(g, B, L).part_floats;
     float* part = pf ? c.take<float>(pf) : nullptr;
     if (!c.ok) return fail(M2_E_WORKSPACE, "m2_conv1d_strided_backward: workspace too small");
     return launch_conv_bwd(x_pre, w, dy, g, B, L, false, in_slope, dx, dw, db, false, part, st);
 }
 
 size_t m2_disc_step_workspace_bytes(const m2_disc* d, int32_t B, int32_t L) {
-    if (!d || B < 0 || L <= 0) return 0;
-    const StepPlan p = step_plan(d, B, L);
-    return (size_t)p.nbs * (2 * p.per + 2 * p.cot + p.pooled) * sizeof(float) + p.part * sizeof(float) +
-           (size_t)p.nbs * kLayers * p.max_chunks * loss::kRedPart * sizeof(double) + 256 * 8;
+    return disc_bytes(d, B, L, loss::DISC_STEP);
 }
 
 int32_t m2_disc_step(const m2_disc* d, const float* real, const float* fake, int32_t B, int32_t L, double* out,
                      float* const* grads, void* workspace, size_t workspace_bytes, void* stream) {
     M2_CHECK_ARG(d && real && fake && out && grads && B >= 0 && L > 0, "m2_disc_step: bad argument");
     for (int i = 0; i < d->n_scales * 2 * kLayers; ++i) M2_CHECK_ARG(grads[i], "m2_disc_step: null gradient");
-    M2_CHECK_SHAPE(d->n_scales == loss::kDiscScales, "m2_disc_step: the rows are laid out for three scales");
-    M2_CHECK_SHAPE(disc_shape_ok(d, B, L),
-                   "m2_disc_step: at most 65535 utterances of 2^28 samples, no shorter than the largest scale");
-    if (B == 0) return M2_OK;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const StepPlan pl = step_plan(d, B, L);
-    const int nbs = pl.nbs;
-    Carve c(workspace, workspace_bytes);
-    float* act[2] = {c.take<float>((size_t)nbs * pl.per), c.take<float>((size_t)nbs * pl.per)};
-    double* dpart = c.take<double>((size_t)nbs * kLayers * pl.max_chunks * loss::kRedPart);
-    float* cot[2] = {c.take<float>((size_t)nbs * pl.cot), c.take<float>((size_t)nbs * pl.cot)};
-    float* pooled = pl.pooled ? c.take<float>((size_t)nbs * pl.pooled) : nullptr;
-    float* part = pl.part ? c.take<float>(pl.part) : nullptr;
-    if (!c.ok) return fail(M2_E_WORKSPACE, "m2_disc_step: workspace too small");
-    for (int b0 = 0; b0 < B; b0 += nbs) {
-        const int nb = std::min(nbs, B - b0);
-        for (int s = 0; s < d->n_scales; ++s) {
-            int len[kLayers];
-            disc_lengths(L, d->scales[s], len);
-            // the forward half: m2_disc_losses's launches
-            float* map[2][kLayers];
-            const int32_t rcf = scale_forward(d, s, real, fake, b0, nb, L, len, act, dpart, pl.max_chunks, out, map, st);
-            if (rcf != M2_OK) return rcf;
-            // the backward half, side by side, while the maps are resident
-            const int Lp = L / d->scales[s];
-            const double cscale = 2.0 / ((double)B * (double)len[kLayers - 1] * (double)d->n_scales);
-            for (int side = 0; side < 2; ++side) {
-                const float* x = (side ? fake : real) + (size_t)b0 * L;
-                if (d->scales[s] > 1) {
-                    hipLaunchKernelGGL(loss::avg_pool_kernel, dim3(cdiv(Lp, 256), nb), dim3(256), 0, st, x, L,
-                                       d->scales[s], Lp, pooled);
-                    M2_LAUNCHED("avg_pool_kernel");
-                    x = pooled;
-                }
-                const size_t nl = (size_t)nb * len[kLayers - 1];
-                hipLaunchKernelGGL(loss::logit_cotangent_kernel, dim3((unsigned)((nl + 255) / 256)), dim3(256), 0, st,
-                                   map[side][kLayers - 1], nl, side ? 0.0 : 1.0, cscale, cot[0]);
-                M2_LAUNCHED("logit_cotangent_kernel");
-                const bool accumulate = b0 > 0 || side > 0;
-                int cur = 0;
-                for (int i = kLayers - 1; i >= 0; --i) {
-                    float* const* gp = grads + ((size_t)s * kLayers + i) * 2;
-                    const int32_t rc = launch_conv_bwd(
-                        i > 0 ? map[side][i - 1] : x, d->w[s][i], cot[cur], kDisc[i], nb, i > 0 ? len[i - 1] : Lp,
-                        loss::conv_path(kDisc[i]) == loss::PATH_MFMA, i > 0 ? loss::kDiscSlope : 1.f,
-                        i > 0 ? cot[cur ^ 1] : nullptr, gp[0], gp[1], accumulate, part, st);
-                    if (rc != M2_OK) return rc;
-                    cur ^= 1;
-                }
-            }
-        }
-    }
-    return M2_OK;
+    return disc_walk(d, loss::DISC_STEP, "m2_disc_step", real, fake, B, L, 0.0, 0.0, out, grads, nullptr, workspace,
+                     workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
 int32_t m2_conv1d_audio_backward(const float* dy, const float* w, int32_t ksize, int32_t padding, int32_t pool,
@@ -1326,7 +1207,7 @@ int32_t m2_conv1d_audio_backward(const float* dy, const float* w, int32_t ksize,
     M2_CHECK_ARG(dy && w && dx && ksize > 0 && padding >= 0 && pool > 0 && B >= 0 && Cout > 0 && L > 0,
                  "m2_conv1d_audio_backward: bad argument");
     M2_CHECK_SHAPE(B <= loss::kMaxGrid && L <= (1 << 28) && pool <= (1 << 16) && padding <= (1 << 12) &&
-                       audio_bwd_ok(Cout, ksize),
+                       loss::audio_bwd_ok(Cout, ksize),
                    "m2_conv1d_audio_backward: at most 65535 utterances of 2^28 samples, pool 2^16, padding 2^12, "
                    "and weights and a 16-channel window that fit LDS");
     M2_CHECK_SHAPE(L / pool + 2 * padding >= ksize && L / pool >= 1,
@@ -1337,10 +1218,7 @@ int32_t m2_conv1d_audio_backward(const float* dy, const float* w, int32_t ksize,
 }
 
 size_t m2_disc_gen_step_workspace_bytes(const m2_disc* d, int32_t B, int32_t L) {
-    if (!d || B < 0 || L <= 0) return 0;
-    const StepPlan p = step_plan(d, B, L);
-    return (size_t)p.nbs * (2 * p.per + 2 * p.cot) * sizeof(float) +
-           (size_t)p.nbs * kLayers * p.max_chunks * loss::kRedPart * sizeof(double) + 256 * 8;
+    return disc_bytes(d, B, L, loss::DISC_GEN_STEP);
 }
 
 int32_t m2_disc_gen_step(const m2_disc* d, const float* real, const float* fake, int32_t B, int32_t L, double w_adv,
@@ -1348,60 +1226,15 @@ int32_t m2_disc_gen_step(const m2_disc* d, const float* real, const float* fake,
                          void* stream) {
     M2_CHECK_ARG(d && fake && out && d_fake && B >= 0 && L > 0, "m2_disc_gen_step: bad argument");
     M2_CHECK_ARG(real || w_fm == 0.0, "m2_disc_gen_step: the feature-matching term needs real");
-    M2_CHECK_SHAPE(d->n_scales == loss::kDiscScales, "m2_disc_gen_step: the rows are laid out for three scales");
-    M2_CHECK_SHAPE(disc_shape_ok(d, B, L),
-                   "m2_disc_gen_step: at most 65535 utterances of 2^28 samples, no shorter than the largest scale");
-    if (B == 0) return M2_OK;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const StepPlan pl = step_plan(d, B, L);
-    const int nbs = pl.nbs;
-    Carve c(workspace, workspace_bytes);
-    float* act[2] = {c.take<float>((size_t)nbs * pl.per), c.take<float>((size_t)nbs * pl.per)};
-    double* dpart = c.take<double>((size_t)nbs * kLayers * pl.max_chunks * loss::kRedPart);
-    float* cot[2] = {c.take<float>((size_t)nbs * pl.cot), c.take<float>((size_t)nbs * pl.cot)};
-    if (!c.ok) return fail(M2_E_WORKSPACE, "m2_disc_gen_step: workspace too small");
-    for (int b0 = 0; b0 < B; b0 += nbs) {
-        const int nb = std::min(nbs, B - b0);
-        for (int s = 0; s < d->n_scales; ++s) {
-            int len[kLayers];
-            disc_lengths(L, d->scales[s], len);
-            // the forward half: m2_disc_losses's launches
-            float* map[2][kLayers];
-            const int32_t rcf = scale_forward(d, s, real, fake, b0, nb, L, len, act, dpart, pl.max_chunks, out, map, st);
-            if (rcf != M2_OK) return rcf;
-            // the fake side backward, data gradients only, while the maps of both sides are resident
-            const size_t nl = (size_t)nb * len[kLayers - 1];
-            const double cscale = w_adv * 2.0 / ((double)B * (double)len[kLayers - 1] * (double)d->n_scales);
-            hipLaunchKernelGGL(loss::logit_cotangent_kernel, dim3((unsigned)((nl + 255) / 256)), dim3(256), 0, st,
-                               map[1][kLayers - 1], nl, 1.0, cscale, cot[0]);
-            M2_LAUNCHED("logit_cotangent_kernel");
-            int cur = 0;
-            for (int i = kLayers - 1; i >= 1; --i) {
-                const int32_t rc = launch_conv_bwd(map[1][i - 1], d->w[s][i], cot[cur], kDisc[i], nb, len[i - 1],
-                                                   loss::conv_path(kDisc[i]) == loss::PATH_MFMA, loss::kDiscSlope,
-                                                   cot[cur ^ 1], nullptr, nullptr, false, nullptr, st);
-                if (rc != M2_OK) return rc;
-                cur ^= 1;
-                if (w_fm != 0.0) {  // the feature-matching term of map i - 1, before the next layer down reads it
-                    const size_t per_utt = (size_t)kDisc[i - 1].Cout * len[i - 1], n = per_utt * nb;
-                    const double fm = w_fm / ((double)(d->n_scales * kFeat) * (double)B * (double)per_utt);
-                    hipLaunchKernelGGL(loss::fm_cotangent_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
-                                       map[1][i - 1], map[0][i - 1], n, (float)fm, cot[cur]);
-                    M2_LAUNCHED("fm_cotangent_kernel");
-                }
-            }
-            // scale index 0 overwrites the slice's rows of d_fake, the later scales add in stream order
-            const int32_t rc = launch_audio_bwd(cot[cur], d->w[s][0], kDisc[0].Cout, kDisc[0].k, kDisc[0].pad,
-                                                d->scales[s], nb, L, s > 0, d_fake + (size_t)b0 * L, st);
-            if (rc != M2_OK) return rc;
-        }
-    }
-    return M2_OK;
+    return disc_walk(d, loss::DISC_GEN_STEP, "m2_disc_gen_step", real, fake, B, L, w_adv, w_fm, out, nullptr, d_fake,
+                     workspace, workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
 size_t m2_loss_spectral_workspace_bytes(const m2_dsp* d, int32_t B, int32_t L) {
     if (!d || B < 0 || L < 0) return 0;
-    return (size_t)B * (1 + L / d->hop) * loss::kSpecPart * sizeof(double) + 256;
+    Sizer s;
+    carve_spectral(s, d, B, L, nullptr);
+    return s.off + 256;
 }
 
 int32_t m2_loss_spectral(const m2_dsp* d, const float* pred, const float* target, int32_t B, int32_t L,
@@ -1414,7 +1247,8 @@ int32_t m2_loss_spectral(const m2_dsp* d, const float* pred, const float* target
     if (B == 0) return M2_OK;
     const int frames = 1 + L / d->hop;
     Carve c(workspace, workspace_bytes);
-    double* part = c.take<double>((size_t)B * frames * loss::kSpecPart);
+    double* part;
+    carve_spectral(c, d, B, L, &part);
     if (!c.ok) return fail(M2_E_WORKSPACE, "m2_loss_spectral: workspace too small");
     hipStream_t st = static_cast<hipStream_t>(stream);
 #define M2_SPEC(NN)                                                                                                  \

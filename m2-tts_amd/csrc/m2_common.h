@@ -135,7 +135,10 @@ struct Carve {
     }
 };
 
-// Byte counter with the same carve rule (for m2_workspace_bytes).
+// Byte counter with the same carve rule.  A workspace layout is written once, as
+// template <typename A> void carve_x(A&, ..., Bufs* out), and run over both: over a
+// Sizer in the _workspace_bytes function (which returns off + 256: the size is exact
+// up to that slack) and over a Carve in the call, so the two cannot differ.
 struct Sizer {
     size_t off = 0;
     template <typename T>

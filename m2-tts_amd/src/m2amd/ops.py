@@ -293,45 +293,46 @@ class Discriminators:
                 maps.append(m)
         return outs, (maps if features else None)
 
-    def losses(self, real: Optional[Tensor], fake: Optional[Tensor]) -> Tensor:
-        """The logit and feature-matching sums of real and/or fake [B,1,L] ->
-        float64 [B, K] on the device, columns ``dsp.loss_columns("disc")``."""
-        real = None if real is None else self._audio(real)
-        fake = None if fake is None else self._audio(fake)
-        ref = real if real is not None else fake
+    def _pair(self, real: Optional[Tensor], fake: Optional[Tensor], need_real=False, need_fake=False):
+        """real and fake as [B,1,L] float32 of one shape; one that is not needed may be None."""
+        real = self._audio(real) if need_real or real is not None else None
+        fake = self._audio(fake) if need_fake or fake is not None else None
         if real is not None and fake is not None and real.shape != fake.shape:
             raise ValueError(f"discriminator: real {tuple(real.shape)} and fake {tuple(fake.shape)} differ")
+        return real, fake
+
+    def _rows_call(self, name: str, real: Optional[Tensor], fake: Optional[Tensor], before=(), after=()) -> Tensor:
+        """m2_disc_<name>(handle, real, fake, B, L, *before, rows, *after, workspace, bytes, stream) with zeroed
+        float64 rows [B, K] and the workspace the call asks for; returns the rows."""
+        ref = fake if fake is not None else real
         B, _, L = ref.shape
         lib = _lib.load()
         out = torch.zeros(B, lib.m2_loss_column_count(1), device=ref.device, dtype=torch.float64)
-        need = int(lib.m2_disc_losses_workspace_bytes(self.handle, B, L))
+        need = int(getattr(lib, f"m2_disc_{name}_workspace_bytes")(self.handle, B, L))
         ws = torch.empty(max(need, 1), dtype=torch.uint8, device=ref.device)
-        _lib.call("m2_disc_losses", self.handle, _ptr(real), _ptr(fake), B, L, _ptr(out), _ptr(ws), ws.numel(),
-                  stream_handle(ref.device))
+        _lib.call(f"m2_disc_{name}", self.handle, _ptr(real), _ptr(fake), B, L, *before, _ptr(out), *after, _ptr(ws),
+                  ws.numel(), stream_handle(ref.device))
         return out
+
+    def losses(self, real: Optional[Tensor], fake: Optional[Tensor]) -> Tensor:
+        """The logit and feature-matching sums of real and/or fake [B,1,L] ->
+        float64 [B, K] on the device, columns ``dsp.loss_columns("disc")``."""
+        real, fake = self._pair(real, fake)
+        return self._rows_call("losses", real, fake)
 
     def step(self, real: Tensor, fake: Tensor):
         """The discriminator step (m2_disc_step): ``losses(real, fake)``'s rows, bit for bit, and the
         gradient of L_D = mean over scales of [mean (D(real) - 1)^2 + mean D(fake)^2] with respect to
         every weight and bias: new float32 tensors in state_dict order, shaped like the parameters."""
-        real, fake = self._audio(real), self._audio(fake)
-        if real.shape != fake.shape:
-            raise ValueError(f"discriminator: real {tuple(real.shape)} and fake {tuple(fake.shape)} differ")
-        B, _, L = real.shape
-        lib = _lib.load()
+        real, fake = self._pair(real, fake, need_real=True, need_fake=True)
         dev = real.device
-        out = torch.zeros(B, lib.m2_loss_column_count(1), device=dev, dtype=torch.float64)
         grads = []
         for _ in self.scales:
             for cin, cout, k, _, _, groups in self.LAYER_TABLE:
                 grads.append(torch.zeros(cout, cin // groups, k, device=dev, dtype=torch.float32))
                 grads.append(torch.zeros(cout, device=dev, dtype=torch.float32))
         ptrs = (ctypes.c_void_p * len(grads))(*[g.data_ptr() for g in grads])
-        need = int(lib.m2_disc_step_workspace_bytes(self.handle, B, L))
-        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
-        _lib.call("m2_disc_step", self.handle, _ptr(real), _ptr(fake), B, L, _ptr(out), ptrs, _ptr(ws), ws.numel(),
-                  stream_handle(dev))
-        return out, grads
+        return self._rows_call("step", real, fake, after=(ptrs,)), grads
 
     def gen_step(self, real: Optional[Tensor], fake: Tensor, w_adv: float, w_fm: float):
         """The generator step through the discriminators (m2_disc_gen_step): ``losses(real, fake)``'s rows,
@@ -341,20 +342,9 @@ class Discriminators:
         w_adv, w_fm = float(w_adv), float(w_fm)
         if real is None and w_fm != 0.0:
             raise ValueError("discriminator: gen_step needs real for the feature-matching term")
-        fake = self._audio(fake)
-        real = None if real is None else self._audio(real)
-        if real is not None and real.shape != fake.shape:
-            raise ValueError(f"discriminator: real {tuple(real.shape)} and fake {tuple(fake.shape)} differ")
-        B, _, L = fake.shape
-        lib = _lib.load()
-        dev = fake.device
-        out = torch.zeros(B, lib.m2_loss_column_count(1), device=dev, dtype=torch.float64)
+        real, fake = self._pair(real, fake, need_fake=True)
         d_fake = torch.empty_like(fake)
-        need = int(lib.m2_disc_gen_step_workspace_bytes(self.handle, B, L))
-        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
-        _lib.call("m2_disc_gen_step", self.handle, _ptr(real), _ptr(fake), B, L, w_adv, w_fm, _ptr(out), _ptr(d_fake),
-                  _ptr(ws), ws.numel(), stream_handle(dev))
-        return out, d_fake
+        return self._rows_call("gen_step", real, fake, (w_adv, w_fm), (_ptr(d_fake),)), d_fake
 
 
 def embed_positional(ids: Tensor, emb: Tensor, pe: Tensor, scale: float) -> Tensor:
