@@ -667,6 +667,21 @@ int32_t m2_profile_kernel_count(void);
 const char* m2_profile_kernel_name(int32_t index);
 /* The same kernel as launched by this model (symbol prefix = rocprofv3 name). */
 const char* m2_profile_kernel_name_for(const m2_model* model, int32_t index);
+/* The launch plan of m2_vocoder(model, mel[B, T], mel_layout) as one line of
+ * text: the path (perlayer | split | f32) and every launch with its variant,
+ * grid, threads and LDS bytes, e.g.
+ *   split stage=1 headmid[n=2 S=126 nch=8 trans=1 grid=2x3 thr=1024 lds=...]
+ *   tailp[nl=6 nch=8 grid=4x3 thr=448 lds=49184] redo=none
+ * (one line; the format is fixed and documented in csrc/vocoder_launch.h).
+ * device_T != 0: as a speculative launch whose frame count is a device word.
+ * Host arithmetic only: nothing is launched.  Writes at most cap bytes
+ * (NUL-terminated) and returns the line's length, or a negative M2_E_* code. */
+int32_t m2_debug_vocoder_plan(const m2_model* model, int32_t B, int32_t T, int32_t mel_layout, int32_t device_T,
+                              char* out, size_t cap);
+/* The device's workgroup slots (CUs x occupancy) that the plan's rules weigh,
+ * queried once: the split-f16 stage2 heads of 16 / 19 / 24 / 27 frames, the
+ * stage2 mid and its small-grid form, the stage2 tail and its small-grid form. */
+int32_t m2_debug_vocoder_slots(int64_t* out8);
 /* Vocoder arithmetic of this model: 0 per-layer fp32 kernels, 1 fused exact-f32
  * MFMA (v_mfma_f32_16x16x4_f32), 2 fused split-f16 MFMA (fp32 operands as
  * f16 hi/lo pairs, 3 products per fp32 product, fp32 accumulation). */

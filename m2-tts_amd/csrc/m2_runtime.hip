@@ -894,10 +894,27 @@ int32_t m2_vocoder_select(m2_model* m, int32_t path) {
 }  // extern "C"
 
 namespace {
+// What a call is, for the launch plan (vocoder_launch.h).
+VocCall voc_call(const m2_model* m, int32_t mel_layout, int32_t B, int32_t T, bool x3, int redo, bool device_T,
+                 unsigned prof_slots) {
+    VocCall c;
+    c.M = m->cfg.mel_channels, c.C = m->cfg.vocoder_channels;
+    c.B = B, c.T = T;
+    c.trans = mel_layout == 1;
+    c.device_T = device_T;
+    c.prof_slots = prof_slots;
+    c.hc = m->vx.hc, c.mp = m->vx.mp, c.tp = m->vx.tp, c.tp2 = m->vx.tp2, c.redo_w = m->redo_w;
+    c.wt4p = m->vw.wt4p, c.hcw = m->vw.hcw;
+    c.fused = m->fused, c.x3 = x3;
+    c.range_policy = m->range_policy, c.redo = redo;
+    return c;
+}
+
 // redo >= 0 (range policy 1, x3): the split kernels raise flag word `redo`
 // instead of the host-mapped flag, and the exact-f32 kernels follow, each
 // workgroup returning at once unless that word is raised - a call whose split
 // audio came out non-finite is recomputed on the device, with no host wait.
+// The call is planned once (plan_vocoder_launch); the launchers decide nothing.
 int32_t vocoder_run(const m2_model* m, const float* mel, int32_t mel_layout, int32_t B, int32_t T, float* out_audio,
                     float* const* buf, hipStream_t st, bool x3, int redo, const int32_t* dT) {
     int32_t rc;
@@ -916,30 +933,20 @@ int32_t vocoder_run(const m2_model* m, const float* mel, int32_t mel_layout, int
         vx.dT = vw.dT = dT;
         vx.head_prio = sw().x3_head_prio;
         vx.prof_slots = rec ? m->prof_mask : 0u;
-        if (x3 && redo >= 0) {
+        const VocLaunchPlan plan = plan_vocoder_launch(voc_call(m, mel_layout, B, T, x3, redo, dT != nullptr, vx.prof_slots),
+                                                       sw(), x3 ? vocoder_x3_slots() : VocSlots{});
+        if (plan.path == VocPath::F32) return launch_vocoder_fused(mel, T, plan, vw, buf[0], buf[1], out_audio, st, mark);
+        if (plan.redo == VocRedoPlan::InTail || plan.redo == VocRedoPlan::Guarded) {
             vx.rflag = m->rflag_dev + redo;
             vx.rclear = m->rflag_dev + (redo ^ 1);
             vx.rqueue = reinterpret_cast<unsigned*>(m->rflag_dev + 4);
-            if (m->redo_w && !sw().redo_launch) {
-                // the pipelined tail redoes its own non-finite strips
-                // in fp32 inside the launch: no guarded launch behind it
-                vx.redo_w = m->redo_w;
-                return launch_vocoder_x3(mel, mel_layout == 1, m->cfg.mel_channels, m->cfg.vocoder_channels, B, T,
-                                         vx, buf[0], buf[1], out_audio, st, mark);
-            }
-            if ((rc = launch_vocoder_x3(mel, mel_layout == 1, m->cfg.mel_channels, m->cfg.vocoder_channels, B, T, vx,
-                                        buf[0], buf[1], out_audio, st, mark)))
-                return rc;
-            vw.guard = m->rflag_dev + redo;
-            vw.guard_queue = reinterpret_cast<const unsigned*>(m->rflag_dev + 4);  // words 4-7 (zeroed by the head)
-            return launch_vocoder_fused(mel, mel_layout == 1, m->cfg.mel_channels, m->cfg.vocoder_channels, B, T, vw,
-                                        buf[0], buf[1], out_audio, st, [](int, bool) {});
         }
-        if (x3)
-            return launch_vocoder_x3(mel, mel_layout == 1, m->cfg.mel_channels, m->cfg.vocoder_channels, B, T, vx,
-                                     buf[0], buf[1], out_audio, st, mark);
-        return launch_vocoder_fused(mel, mel_layout == 1, m->cfg.mel_channels, m->cfg.vocoder_channels, B, T, vw,
-                                    buf[0], buf[1], out_audio, st, mark);
+        if (plan.redo == VocRedoPlan::InTail) vx.redo_w = m->redo_w;  // the tail's local fp32 redo
+        if ((rc = launch_vocoder_x3(mel, T, plan, vx, buf[0], buf[1], out_audio, st, mark))) return rc;
+        if (plan.redo != VocRedoPlan::Guarded) return M2_OK;
+        vw.guard = m->rflag_dev + redo;
+        vw.guard_queue = reinterpret_cast<const unsigned*>(m->rflag_dev + 4);  // words 4-7 (zeroed by the head)
+        return launch_vocoder_fused(mel, T, plan, vw, buf[0], buf[1], out_audio, st, [](int, bool) {});
     }
     M2_CHECK_ARG(!dT, "m2_vocoder: a device frame count needs the fused vocoder");
     int ch = m->cfg.vocoder_channels, L = T;
@@ -1038,9 +1045,22 @@ const char* m2_profile_kernel_name(int32_t index) {
 
 const char* m2_profile_kernel_name_for(const m2_model* m, int32_t index) {
     if (!m || index < 0 || index >= kVocKernels) return "";
-    if (m->x3 && m->tailp && index == 2) return m->vx.tp2 ? kVocTailp2KernelName : kVocTailpKernelName;
-    if (m->x3 && m->midp && index == 1) return kVocMidpKernelName;
+    if (m->x3 && index == 1 && voc_mid_kind(m->vx.mp) == VocMid::Midp) return kVocMidpKernelName;
+    if (m->x3 && index == 2) {
+        const VocTail t = voc_tail_kind(m->vx.tp, m->vx.tp2);
+        if (t != VocTail::X3) return t == VocTail::Tailp2 ? kVocTailp2KernelName : kVocTailpKernelName;
+    }
     return m->x3 ? kVocX3KernelNames[index] : kVocKernelNames[index];
+}
+
+int32_t m2_debug_vocoder_plan(const m2_model* m, int32_t B, int32_t T, int32_t mel_layout, int32_t device_T, char* out,
+                              size_t cap) {
+    M2_CHECK_ARG(m && B > 0 && T > 0 && (mel_layout == 0 || mel_layout == 1), "m2_debug_vocoder_plan: bad argument");
+    // the flag word an m2_vocoder call would get now (device_redo_word, without advancing it)
+    const int redo = m->range_policy == 1 && m->x3 && m->fused && m->rflag_dev ? (int)(m->rseq & 1u) : -1;
+    const VocCall c = voc_call(m, mel_layout, B, T, m->x3, redo, device_T != 0, 0u);
+    const VocLaunchPlan p = plan_vocoder_launch(c, sw(), m->x3 && m->fused ? vocoder_x3_slots() : VocSlots{});
+    return p.print(out, cap);
 }
 
 size_t m2_front_bytes(const m2_model* model, int32_t B, int32_t S) {

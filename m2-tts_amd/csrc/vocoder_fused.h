@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "m2_common.h"
+#include "vocoder_launch.h"
 #include "vocoder_redo.h"
 
 namespace m2 {
@@ -36,9 +37,44 @@ struct VocW {
 
 bool vocoder_fused_supported(int M, int C);
 
+// One kernel instantiation, named once per file in a table of these: the row
+// serves the LDS attribute, the occupancy query and the launch.
+struct KernelRow {
+    const void* fn = nullptr;  // null: a combination that is not instantiated
+    int threads = 0, lds = 0;
+};
+// hipFuncAttributeMaxDynamicSharedMemorySize of every row.  Each vocoder file
+// runs this once, from the initialiser of a function-local static (thread-safe);
+// the answer, a failure included, is kept for every later call.
+inline hipError_t set_rows_lds(const KernelRow* rows, int n) {
+    for (int i = 0; i < n; ++i) {
+        if (!rows[i].fn) continue;
+        if (rows[i].lds > 160 * 1024) return hipErrorInvalidValue;  // the LDS of a CU
+        const hipError_t e = hipFuncSetAttribute(rows[i].fn, hipFuncAttributeMaxDynamicSharedMemorySize, rows[i].lds);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+// Workgroup slots of the device for a row: CUs x its occupancy.
+inline long row_slots(const KernelRow& r) {
+    int ncu = 0, dev = 0, per = 0;
+    (void)hipGetDevice(&dev);
+    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, r.fn, r.threads, r.lds) != hipSuccess || per <= 0) per = 1;
+    return (long)per * ncu;
+}
+// args: the addresses of the kernel's arguments, in order.
+inline int32_t launch_row(const KernelRow& r, const VocGrid& g, hipStream_t st, void** args, const char* name) {
+    if (!r.fn || r.threads != g.threads || r.lds != g.lds) return fail(M2_E_SHAPE, name);  // plan and table disagree
+    const hipError_t e = hipLaunchKernel(r.fn, dim3(g.x, g.y), dim3(g.threads), args, (size_t)g.lds, st);
+    return e == hipSuccess ? M2_OK : hip_status(e, name);
+}
+
 // mark(kernel_index 0..2, begin): measurement hook around the head / mid / tail launches.
-int32_t launch_vocoder_fused(const float* mel, bool trans, int M, int C, int B, int T, const VocW& w, float* U1,
-                             float* U2, float* audio, hipStream_t st, const std::function<void(int, bool)>& mark);
+// plan: the call's launch plan (vocoder_launch.h), on the exact-f32 path or with the
+// guarded redo; guarded: this launch is that redo (w.guard set).
+int32_t launch_vocoder_fused(const float* mel, int T, const VocLaunchPlan& plan, const VocW& w, float* U1, float* U2,
+                             float* audio, hipStream_t st, const std::function<void(int, bool)>& mark);
 
 constexpr int kVocKernels = 3;
 extern const char* const kVocKernelNames[kVocKernels];
@@ -252,8 +288,9 @@ struct MidpSrc {
 };
 bool pack_midp(const MidpSrc& s, std::vector<uint16_t>* w, std::vector<float>* bias, bool* range_ok);
 // dT (dev_frames): when set, L1 is the capacity (4 x capacity frames)
-int32_t launch_vocoder_midp(const void* U1, int L1, int B, const vx_u32x4* W, const float* bias, void* U2,
-                            hipStream_t st, const int32_t* dT = nullptr);
+// nch: the strip length in 16-column chunks, g the launch (plan_vocoder_launch)
+int32_t launch_vocoder_midp(const void* U1, int L1, int nch, const VocGrid& g, const vx_u32x4* W, const float* bias,
+                            void* U2, hipStream_t st, const int32_t* dT = nullptr);
 extern const char* const kVocMidpKernelName;
 
 // Raw fp32 reference weights of the five tail modules (host pointers).
@@ -265,21 +302,26 @@ struct TailpSrc {
 bool pack_tailp(const TailpSrc& s, std::vector<uint16_t>* w, std::vector<float>* bias, bool* range_ok);
 // rd.rw set: range policy "fallback" - a workgroup whose audio strip is not
 // finite recomputes it in fp32 inside the launch (vocoder_redo.h).
-int32_t launch_vocoder_tailp(const void* U2, int L2, int B, const vx_u32x4* W, const float* bias, float* audio,
-                             int* rflag, hipStream_t st, const int32_t* dT = nullptr, const VocRedo& rd = VocRedo{});
+// nl: 6 or 7 computing layers; nch, g as for the mid.
+int32_t launch_vocoder_tailp(const void* U2, int L2, int nl, int nch, const VocGrid& g, const vx_u32x4* W,
+                             const float* bias, float* audio, int* rflag, hipStream_t st, const int32_t* dT = nullptr,
+                             const VocRedo& rd = VocRedo{});
 extern const char* const kVocTailpKernelName;
 // The same five modules at stage2 widths (C = 256: U2 64 channels) for the
 // pipelined stage2 tail (vocoder_tailp2.hip, two waves per layer).
 bool pack_tailp2(const TailpSrc& s, std::vector<uint16_t>* w, std::vector<float>* bias, bool* range_ok);
-int32_t launch_vocoder_tailp2(const void* U2, int L2, int B, const vx_u32x4* W, const float* bias, float* audio,
-                              int* rflag, hipStream_t st, const int32_t* dT = nullptr, const VocRedo& rd = VocRedo{});
+int32_t launch_vocoder_tailp2(const void* U2, int L2, int nl, int nch, const VocGrid& g, const vx_u32x4* W,
+                              const float* bias, float* audio, int* rflag, hipStream_t st, const int32_t* dT = nullptr,
+                              const VocRedo& rd = VocRedo{});
 extern const char* const kVocTailp2KernelName;
 
 bool vocoder_x3_supported(int M, int C);
 int vocoder_x3_mel_pad(int M);  // input-conv channel count after padding to the k-block layout
 // U1/U2: workspace for the intermediates (same bytes as fp32 [B][C/2][4T] / [B][C/4][16T]).
-int32_t launch_vocoder_x3(const float* mel, bool trans, int M, int C, int B, int T, const VocX& w, void* U1, void* U2,
+int32_t launch_vocoder_x3(const float* mel, int T, const VocLaunchPlan& plan, const VocX& w, void* U1, void* U2,
                           float* audio, hipStream_t st, const std::function<void(int, bool)>& mark);
+// The device's workgroup slots for the plan's rules, queried once (thread-safe).
+const VocSlots& vocoder_x3_slots();
 // range_ok is cleared when a weight is outside the f16 range (|w| >= 65504).
 // res: ResBlock conv2 - for 8/16 channels the residual x is folded into the
 // GEMM as an identity block on the padding octets (vocoder_x3.hip, mma_x3).

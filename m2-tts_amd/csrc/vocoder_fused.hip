@@ -44,14 +44,7 @@ struct LB {
     int start;
 };
 
-constexpr int rup16(int n) { return (n + 15) / 16 * 16; }
-// Row stride >= cols with stride = 16 (mod 32): conflict-free B-operand reads.
-constexpr int pstride(int cols) { return ((cols + 15) / 32) * 32 + 16; }
-constexpr int cmax(int a, int b) { return a > b ? a : b; }
-// Compact row stride (multiple of 4, >= cols): up to 4-lane 2-way conflicts
-// between the two 16-lane halves of a read, in exchange for LDS capacity.
-constexpr int cstride(int cols) { return (cols + 3) / 4 * 4 + ((((cols + 3) / 4 * 4) % 32 == 0) ? 4 : 0); }
-constexpr int stride_for(int cols, bool compact) { return compact ? cstride(cols) : pstride(cols); }
+using namespace f32;  // strides, window plans and tilings: vocoder_launch.h
 
 // ---------------------------------------------------------------------------
 // acc[n] += sum_s A(s) * B(s, n) over KS = NTAP*KC k-steps for NT 16-wide
@@ -444,110 +437,6 @@ __device__ __forceinline__ void gstore(float* __restrict__ g, int rows, int Lg, 
     }
 }
 
-// ---------------------------------------------------------------------------
-// Window plans.  All column counts are exact receptive-field arithmetic; the
-// capacities also cover the garbage columns a 16-wide MFMA tile computes past
-// the last needed position (those columns are never stored).
-template <int M, int C, int TF, bool CP = false>
-struct HeadPlan {
-    static constexpr int C1 = C / 2;
-    static constexpr int MEL_N = TF + 6;           // frames [f0-3, f0+TF+3)
-    static constexpr int A0_N = TF + 4;            // input conv out  [f0-2, f0+TF+2)
-    static constexpr int NQ = TF + 2;              // ConvT1 inputs   [f0-1, f0+TF+1)
-    static constexpr int H_N = 4 * TF + 2;         // RB1 conv1 out   [4f0-1, 4f0+4TF+1)
-    static constexpr int O_N = 4 * TF;             // RB1 out         [4f0, 4f0+4TF)
-    static constexpr int P_MEL = stride_for(cmax(MEL_N, rup16(A0_N) + 2), CP);
-    static constexpr int P_A0 = stride_for(cmax(A0_N, rup16(NQ) + 2), CP);
-    static constexpr int P_U = stride_for(cmax(4 * NQ, rup16(H_N) + 4), CP);
-    static constexpr int P_H = stride_for(cmax(H_N, rup16(O_N) + 2), CP);
-    static constexpr int R0 = cmax(M * P_MEL + C * P_A0, C1 * P_H);
-    static constexpr int R1 = C1 * P_U;
-    static constexpr int LDS_FLOATS = R0 + R1;
-};
-
-template <int CI, int W>
-struct MidPlan {  // U1 (CI ch, res 4) -> U2 (CI/2 ch, res 16); W res-4 positions
-    static constexpr int CO = CI / 2;
-    static constexpr int IN_N = W + 4;             // [p0-2, p0+W+2)
-    static constexpr int NQ = W + 2;               // ConvT2 inputs [p0-1, p0+W+1)
-    static constexpr int H_N = 4 * W + 2;          // [4p0-1, 4p0+4W+1)
-    static constexpr int O_N = 4 * W;              // [4p0, 4p0+4W)
-    static constexpr int P_IN = pstride(cmax(IN_N, rup16(NQ) + 2));
-    static constexpr int P_U = pstride(cmax(4 * NQ, rup16(H_N) + 4));
-    static constexpr int P_H = pstride(cmax(H_N, rup16(O_N) + 2));
-    static constexpr int R0 = cmax(CI * P_IN, CO * P_H);
-    static constexpr int R1 = CO * P_U;
-    static constexpr int LDS_FLOATS = R0 + R1;
-};
-
-// Odd row stride >= cols (the two-phase layers' stride-2 B reads).
-constexpr int ostride(int cols) { return ((cols + 15) / 32) * 32 + 17; }
-template <int CI, int W, bool PAIR = false>
-struct TailPlan {  // U2 (CI ch, res 16) -> audio (res 64); W res-16 positions
-    static constexpr int C3 = CI / 2, C4 = CI / 4;
-    static constexpr int IN_N = W + 8;             // [p0-4, p0+W+4)
-    static constexpr int NQ3 = W + 6;              // ConvT3 inputs [p0-3, p0+W+3) -> U3 [2p0-6, ..)
-    static constexpr int H3_N = 2 * W + 8;         // [2p0-4, 2p0+2W+4)
-    static constexpr int O3_N = 2 * W + 6;         // [2p0-3, 2p0+2W+3)
-    static constexpr int NQ4 = 2 * W + 4;          // ConvT4 inputs [2p0-2, 2p0+2W+2) -> U4 [4p0-4, ..)
-    static constexpr int H4_N = 4 * W + 4;         // [4p0-2, 4p0+4W+2)
-    static constexpr int O4_N = 4 * W + 2;         // [4p0-1, 4p0+4W+1)
-    static constexpr int A_N = 4 * W;              // audio [4p0, 4p0+4W)
-    static constexpr int P_IN = pstride(cmax(IN_N, rup16(NQ3) + 2));
-    static constexpr int P_U3 = pstride(cmax(2 * NQ3, cmax(rup16(H3_N) + 3, rup16(NQ4) + 5)));
-    static constexpr int P_H3 = pstride(cmax(H3_N, rup16(O3_N) + 2));
-    // (PAIR: the two-phase ResBlock4 reads up to 2 x 16 columns past its last
-    // needed position pair)
-    static constexpr int P_U4 = PAIR ? ostride(cmax(2 * NQ4, 4 * W + 40)) : pstride(cmax(2 * NQ4, rup16(H4_N) + 3));
-    static constexpr int P_H4 = PAIR ? ostride(cmax(H4_N, 4 * W + 40)) : pstride(cmax(H4_N, rup16(O4_N) + 2));
-    // region A: U2in -> H3 -> U4 ; region B: U3 -> H4
-    static constexpr int RA = cmax(CI * P_IN, cmax(C3 * P_H3, C4 * P_U4));
-    static constexpr int RB = cmax(C3 * P_U3, C4 * P_H4);
-    static constexpr int LDS_FLOATS = RA + RB;
-};
-
-// ---------------------------------------------------------------------------
-// Tiling configurations.  WAVES waves per workgroup; NT_* = 16-position tiles
-// per work item of each layer, chosen so every layer splits into a multiple
-// of WAVES items; MINW = launch-bounds waves per SIMD (VGPR cap).
-struct CfgS1W8 {  // stage1: 8 waves, <= 74 KB LDS (2 workgroups / CU)
-    static constexpr int M = 64, C = 128, TF = 28, W2 = 60, W3 = 240, WAVES = 8, MINW = 5;
-    static constexpr bool CP = false;
-    static constexpr int NT_IN = 2, NT_T1 = 2, NT_R1 = 4, NT_T2 = 4, NT_R2 = 4, NT_T3 = 4, NT_R3 = 4, NT_T4 = 4, NT_R4 = 4;
-};
-struct CfgS1W16 {  // stage1: 16 waves, one workgroup per CU (152/132/131 KB LDS)
-    static constexpr int M = 64, C = 128, TF = 63, W2 = 125, W3 = 500, WAVES = 16, MINW = 4;
-    static constexpr bool CP = false;
-    static constexpr int NT_IN = 3, NT_T1 = 5, NT_R1 = 4, NT_T2 = 4, NT_R2 = 4, NT_T3 = 4, NT_R3 = 4, NT_T4 = 8, NT_R4 = 8;
-};
-struct CfgS1W16s {  // CfgS1W16 with ~2-3 smaller work items per wave for the dynamic schedule
-    static constexpr int M = 64, C = 128, TF = 63, W2 = 125, W3 = 500, WAVES = 16, MINW = 4;
-    static constexpr bool CP = false;
-    static constexpr int NT_IN = 2, NT_T1 = 2, NT_R1 = 2, NT_T2 = 2, NT_R2 = 2, NT_T3 = 2, NT_R3 = 2, NT_T4 = 4, NT_R4 = 4;
-};
-// The 16-wave tiling's mid and tail as two 8-wave workgroups per CU (the
-// windows halved: 1,024 workgroups at B=32 T=500, two rounds as before), so
-// one workgroup's layer barriers overlap the other's MFMA chains (M2_F32_MT).
-// Measured in one process, B=32 T=500 with the two-phase tail layers
-// (profiles/r06/r06z3_mt.txt): the tail 0.1986 -> 0.1948 ms per call (the
-// default, M2_F32_MT=2); the mid 0.228 (its 63-position windows re-read
-// twice the halo).
-struct CfgS1T8 {
-    static constexpr int M = 64, C = 128, TF = 28, W2 = 63, W3 = 250, WAVES = 8, MINW = 5;
-    static constexpr bool CP = false;
-    static constexpr int NT_IN = 2, NT_T1 = 2, NT_R1 = 4, NT_T2 = 4, NT_R2 = 4, NT_T3 = 4, NT_R3 = 4, NT_T4 = 4, NT_R4 = 4;
-};
-struct CfgS2W8 {
-    static constexpr int M = 80, C = 256, TF = 12, W2 = 28, W3 = 120, WAVES = 8, MINW = 5;
-    static constexpr bool CP = false;
-    static constexpr int NT_IN = 2, NT_T1 = 2, NT_R1 = 4, NT_T2 = 4, NT_R2 = 4, NT_T3 = 4, NT_R3 = 4, NT_T4 = 4, NT_R4 = 4;
-};
-struct CfgTinyW8 {  // M2TTSModel(hidden 32, mel 32, vocoder 64) as in the reference smoke tests
-    static constexpr int M = 32, C = 64, TF = 28, W2 = 60, W3 = 240, WAVES = 8, MINW = 5;
-    static constexpr bool CP = false;
-    static constexpr int NT_IN = 2, NT_T1 = 2, NT_R1 = 4, NT_T2 = 4, NT_R2 = 4, NT_T3 = 4, NT_R3 = 4, NT_T4 = 4, NT_R4 = 4;
-};
-
 // Diagnostic build only (-DM2_STAMPS): per-wave s_memtime stamps at phase
 // boundaries, [kernel][workgroup][wave][16]; never part of the product build.
 #ifdef M2_STAMPS
@@ -827,121 +716,105 @@ __global__ __launch_bounds__(Cfg::WAVES * 64, Cfg::WAVES / 4) void voc_redo_kern
 
 // ---------------------------------------------------------------------------
 namespace {
-template <typename K>
-int32_t set_lds(K kernel, size_t bytes) {
-    M2_CHECK_SHAPE(bytes <= 160 * 1024, "fused vocoder: LDS plan exceeds 160 KiB");
-    M2_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)bytes));
-    return M2_OK;
+// One row per kernel instantiation (KernelRow, vocoder_fused.h), by tiling
+// (f32::TilingId): heads [tiling][comp][trans], mids [tiling], tails
+// [tiling][pair], the guarded redo [tiling][pair][comp][trans].  Rows left
+// empty are combinations no form (f32::kF32Forms) takes.
+struct Rows {
+    KernelRow head[kTilings][2][2], mid[kTilings], tail[kTilings][2], redo[kTilings][2][2][2];
+};
+template <class Cfg, bool COMP>
+void head_rows(KernelRow (&r)[2]) {  // r[trans]
+    constexpr int lds = 4 * HeadPlan<Cfg::M, Cfg::C, Cfg::TF, Cfg::CP>::LDS_FLOATS;
+    r[0] = {reinterpret_cast<const void*>(&voc_head_kernel<Cfg, false, COMP>), Cfg::WAVES * 64, lds};
+    r[1] = {reinterpret_cast<const void*>(&voc_head_kernel<Cfg, true, COMP>), Cfg::WAVES * 64, lds};
 }
-
-template <class Cfg, bool PAIR = false, bool COMP = false>
-int32_t voc_redo(const float* mel, bool trans, int B, int T, const VocW& w, float* U1, float* U2, float* audio,
-                 hipStream_t st) {
-    using HP = HeadPlan<Cfg::M, Cfg::C, Cfg::TF, Cfg::CP>;
-    using MP = MidPlan<Cfg::C / 2, Cfg::W2>;
-    using TP = TailPlan<Cfg::C / 4, Cfg::W3, PAIR>;
-    constexpr int threads = Cfg::WAVES * 64;
-    constexpr size_t lds = 4 * (size_t)std::max(std::max(HP::LDS_FLOATS, MP::LDS_FLOATS), TP::LDS_FLOATS);
-    static int full = 0, cus = 0;
-    if (!full) {
-        int32_t rc;
-        if ((rc = set_lds(voc_redo_kernel<Cfg, false, PAIR, COMP>, lds))) return rc;
-        if ((rc = set_lds(voc_redo_kernel<Cfg, true, PAIR, COMP>, lds))) return rc;
-        int occ = 0, dev = 0;
-        M2_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, voc_redo_kernel<Cfg, false, PAIR, COMP>, threads, lds));
-        M2_HIP(hipGetDevice(&dev));
-        M2_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-        cus = std::max(1, cus);
-        full = std::max(1, occ) * cus;
-    }
-    // workgroups of the (usually empty) launch: one per CU by default; the
-    // ordered queue needs no co-residency, so any count is correct
-    // (M2_REDO_GRID=n forces n, 0 = every resident slot)
-    const int grid = sw().redo_grid < 0 ? cus : (sw().redo_grid == 0 ? full : sw().redo_grid);
-    unsigned* q = const_cast<unsigned*>(reinterpret_cast<const unsigned*>(w.guard_queue));
-    if (trans)
-        hipLaunchKernelGGL((voc_redo_kernel<Cfg, true, PAIR, COMP>), dim3(grid), dim3(threads), lds, st, mel, B, T, w, U1, U2, audio,
-                           q);
-    else
-        hipLaunchKernelGGL((voc_redo_kernel<Cfg, false, PAIR, COMP>), dim3(grid), dim3(threads), lds, st, mel, B, T, w, U1, U2,
-                           audio, q);
-    M2_LAUNCHED("voc_redo_kernel");
-    return M2_OK;
+template <class Cfg>
+KernelRow mid_row() {
+    return {reinterpret_cast<const void*>(&voc_mid_kernel<Cfg>), Cfg::WAVES * 64,
+            4 * MidPlan<Cfg::C / 2, Cfg::W2>::LDS_FLOATS};
 }
-
-// The redo's tiling: the 8-wave form of the stage (every stage1 tiling packs
-// the same weights and writes the same U1 / U2 / audio), so it gets up to 256
-// VGPRs per lane at one workgroup per CU.
-template <class Cfg> struct RedoCfg { using type = Cfg; };
-template <> struct RedoCfg<CfgS1W16> { using type = CfgS1W8; };
-template <> struct RedoCfg<CfgS1W16s> { using type = CfgS1W8; };
-
-// MCfg / TCfg: the mid's / tail's tiling (windows W2 / W3, waves), by
-// default the head's.
-// PAIR: the tail's 8-channel layers in the two-phase forms (lconvT2p /
-// lconv3_2p), in the guarded redo as well.
-template <class Cfg, class MCfg = Cfg, class TCfg = Cfg, bool PAIR = false, bool COMP = false>
-int32_t voc_fused(const float* mel, bool trans, int B, int T, const VocW& w, float* U1, float* U2, float* audio,
-                  hipStream_t st, const std::function<void(int, bool)>& mark) {
-    if (w.guard) return voc_redo<typename RedoCfg<Cfg>::type, PAIR, COMP>(mel, trans, B, T, w, U1, U2, audio, st);
-    using HP = HeadPlan<Cfg::M, Cfg::C, Cfg::TF, Cfg::CP>;
-    using MP = MidPlan<MCfg::C / 2, MCfg::W2>;
-    using TP = TailPlan<TCfg::C / 4, TCfg::W3, PAIR>;
-    constexpr int threads = Cfg::WAVES * 64;
-    static bool attr = false;
-    if (!attr) {
-        int32_t rc;
-        if ((rc = set_lds(voc_head_kernel<Cfg, false, COMP>, HP::LDS_FLOATS * 4))) return rc;
-        if ((rc = set_lds(voc_head_kernel<Cfg, true, COMP>, HP::LDS_FLOATS * 4))) return rc;
-        if ((rc = set_lds(voc_mid_kernel<MCfg>, MP::LDS_FLOATS * 4))) return rc;
-        if ((rc = set_lds(voc_tail_kernel<TCfg, PAIR>, TP::LDS_FLOATS * 4))) return rc;
-        attr = true;
-    }
-    mark(0, true);
-    if (trans)
-        hipLaunchKernelGGL((voc_head_kernel<Cfg, true, COMP>), dim3(cdiv(T, Cfg::TF), B), dim3(threads), HP::LDS_FLOATS * 4,
-                           st, mel, T, w, U1);
-    else
-        hipLaunchKernelGGL((voc_head_kernel<Cfg, false, COMP>), dim3(cdiv(T, Cfg::TF), B), dim3(threads), HP::LDS_FLOATS * 4,
-                           st, mel, T, w, U1);
-    mark(0, false);
-    M2_LAUNCHED("voc_head_kernel");
-    mark(1, true);
-    hipLaunchKernelGGL((voc_mid_kernel<MCfg>), dim3(cdiv(4 * T, MCfg::W2), B), dim3(MCfg::WAVES * 64), MP::LDS_FLOATS * 4,
-                       st, U1, 4 * T, w, U2);
-    mark(1, false);
-    M2_LAUNCHED("voc_mid_kernel");
-    mark(2, true);
-    hipLaunchKernelGGL((voc_tail_kernel<TCfg, PAIR>), dim3(cdiv(16 * T, TCfg::W3), B), dim3(TCfg::WAVES * 64),
-                       TP::LDS_FLOATS * 4, st, U2, 16 * T, w, audio);
-    mark(2, false);
-    M2_LAUNCHED("voc_tail_kernel");
-    return M2_OK;
+template <class Cfg, bool PAIR>
+KernelRow tail_row() {
+    return {reinterpret_cast<const void*>(&voc_tail_kernel<Cfg, PAIR>), Cfg::WAVES * 64,
+            4 * TailPlan<Cfg::C / 4, Cfg::W3, PAIR>::LDS_FLOATS};
 }
+// Compiled for the largest of the three bodies' LDS.
+template <class Cfg, bool PAIR, bool COMP>
+void redo_rows(KernelRow (&r)[2]) {  // r[trans]
+    constexpr int lds = 4 * std::max(std::max(HeadPlan<Cfg::M, Cfg::C, Cfg::TF, Cfg::CP>::LDS_FLOATS,
+                                              MidPlan<Cfg::C / 2, Cfg::W2>::LDS_FLOATS),
+                                     TailPlan<Cfg::C / 4, Cfg::W3, PAIR>::LDS_FLOATS);
+    r[0] = {reinterpret_cast<const void*>(&voc_redo_kernel<Cfg, false, PAIR, COMP>), Cfg::WAVES * 64, lds};
+    r[1] = {reinterpret_cast<const void*>(&voc_redo_kernel<Cfg, true, PAIR, COMP>), Cfg::WAVES * 64, lds};
+}
+// (Filled in the order the kernels have always been instantiated in, which is
+// the order of the device code in the object.)
+Rows make_rows() {
+    Rows r;
+    redo_rows<CfgS1W8, true, true>(r.redo[S1W8][1][1]);
+    head_rows<CfgS1W16s, true>(r.head[S1W16s][1]);
+    r.mid[S1W16s] = mid_row<CfgS1W16s>();
+    r.tail[S1W16s][1] = tail_row<CfgS1W16s, true>();
+    head_rows<CfgS1W16, true>(r.head[S1W16][1]);
+    r.mid[S1T8] = mid_row<CfgS1T8>();
+    r.tail[S1W16][1] = tail_row<CfgS1W16, true>();
+    r.mid[S1W16] = mid_row<CfgS1W16>();
+    r.tail[S1T8][1] = tail_row<CfgS1T8, true>();
+    head_rows<CfgS1W8, true>(r.head[S1W8][1]);
+    r.mid[S1W8] = mid_row<CfgS1W8>();
+    r.tail[S1W8][1] = tail_row<CfgS1W8, true>();
+    redo_rows<CfgS1W8, true, false>(r.redo[S1W8][1][0]);
+    head_rows<CfgS1W16s, false>(r.head[S1W16s][0]);
+    head_rows<CfgS1W16, false>(r.head[S1W16][0]);
+    head_rows<CfgS1W8, false>(r.head[S1W8][0]);
+    redo_rows<CfgS1W8, false, true>(r.redo[S1W8][0][1]);
+    r.tail[S1W16s][0] = tail_row<CfgS1W16s, false>();
+    r.tail[S1W16][0] = tail_row<CfgS1W16, false>();
+    r.tail[S1T8][0] = tail_row<CfgS1T8, false>();
+    r.tail[S1W8][0] = tail_row<CfgS1W8, false>();
+    redo_rows<CfgS1W8, false, false>(r.redo[S1W8][0][0]);
+    redo_rows<CfgS2W8, false, true>(r.redo[S2W8][0][1]);
+    head_rows<CfgS2W8, true>(r.head[S2W8][1]);
+    r.mid[S2W8] = mid_row<CfgS2W8>();
+    r.tail[S2W8][0] = tail_row<CfgS2W8, false>();
+    redo_rows<CfgS2W8, false, false>(r.redo[S2W8][0][0]);
+    head_rows<CfgS2W8, false>(r.head[S2W8][0]);
+    redo_rows<CfgTinyW8, false, false>(r.redo[TinyW8][0][0]);
+    head_rows<CfgTinyW8, false>(r.head[TinyW8][0]);
+    r.mid[TinyW8] = mid_row<CfgTinyW8>();
+    r.tail[TinyW8][0] = tail_row<CfgTinyW8, false>();
+    return r;
+}
+const Rows kRows = make_rows();
 
-template <bool PAIR, bool COMP>
-int32_t s1_fused(const float* mel, bool trans, int B, int T, const VocW& w, float* U1, float* U2, float* audio,
-                 hipStream_t st, const std::function<void(int, bool)>& mark, bool w16, int plan) {
-    if (plan == 3)
-        return voc_fused<CfgS1W16s, CfgS1W16s, CfgS1W16s, PAIR, COMP>(mel, trans, B, T, w, U1, U2, audio, st, mark);
-    if (w16) {
-        switch (sw().f32_mt) {
-            case 1:
-                return voc_fused<CfgS1W16, CfgS1T8, CfgS1W16, PAIR, COMP>(mel, trans, B, T, w, U1, U2, audio, st, mark);
-            case 2:
-                return voc_fused<CfgS1W16, CfgS1W16, CfgS1T8, PAIR, COMP>(mel, trans, B, T, w, U1, U2, audio, st, mark);
-            case 3:
-                return voc_fused<CfgS1W16, CfgS1T8, CfgS1T8, PAIR, COMP>(mel, trans, B, T, w, U1, U2, audio, st, mark);
-            case 4:  // the mid's items halved (two per wave), the tail on half windows: 0.1843 ->
-                     // 0.1894 ms alternated (profiles/r06/r06z14_mid_items.txt), a switch only
-                return voc_fused<CfgS1W16, CfgS1W16s, CfgS1T8, PAIR, COMP>(mel, trans, B, T, w, U1, U2, audio, st, mark);
-            default:
-                return voc_fused<CfgS1W16, CfgS1W16, CfgS1W16, PAIR, COMP>(mel, trans, B, T, w, U1, U2, audio, st,
-                                                                           mark);
-        }
-    }
-    return voc_fused<CfgS1W8, CfgS1W8, CfgS1W8, PAIR, COMP>(mel, trans, B, T, w, U1, U2, audio, st, mark);
+// The one-time setup (thread-safe: a function-local static; a failed
+// hipFuncSetAttribute stays the answer of every later call): every row's LDS
+// attribute, the CU count and the redo rows' resident workgroups.
+struct Setup {
+    hipError_t err;
+    int cus;
+    int full[kTilings][2][2];  // redo rows [tiling][pair][comp]: every resident slot
+};
+const Setup& setup() {
+    static const Setup s = [] {
+        Setup r{};
+        r.err = set_rows_lds(reinterpret_cast<const KernelRow*>(&kRows), sizeof(Rows) / sizeof(KernelRow));
+        int dev = 0;
+        if (r.err == hipSuccess) r.err = hipGetDevice(&dev);
+        if (r.err == hipSuccess) r.err = hipDeviceGetAttribute(&r.cus, hipDeviceAttributeMultiprocessorCount, dev);
+        r.cus = std::max(1, r.cus);
+        for (int t = 0; t < kTilings; ++t)
+            for (int pc = 0; pc < 4; ++pc) {
+                const KernelRow& k = kRows.redo[t][pc >> 1][pc & 1][0];
+                int occ = 0;
+                if (k.fn && r.err == hipSuccess)
+                    r.err = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k.fn, k.threads, k.lds);
+                r.full[t][pc >> 1][pc & 1] = std::max(1, occ) * r.cus;
+            }
+        return r;
+    }();
+    return s;
 }
 }  // namespace
 
@@ -949,30 +822,41 @@ bool vocoder_fused_supported(int M, int C) {
     return (M == 64 && C == 128) || (M == 80 && C == 256) || (M == 32 && C == 64);
 }
 
-int32_t launch_vocoder_fused(const float* mel, bool trans, int M, int C, int B, int T, const VocW& w, float* U1,
-                             float* U2, float* audio, hipStream_t st,
-                             const std::function<void(int, bool)>& mark) {
-    if (B == 0 || T == 0) return M2_OK;
-    const int plan = sw().voc_plan;
-    if (M == 64 && C == 128) {
-        // Workgroup rounds: one 16-wave WG per CU; 8-wave WGs pair up.  Pick the
-        // tiling whose workgroup count wastes the least of its last round.
-        const int n16 = B * cdiv(T, CfgS1W16::TF), n8 = B * cdiv(T, CfgS1W8::TF);
-        const double waste16 = (double)cdiv(n16, 256) * 256 / n16, waste8 = (double)cdiv(n8, 512) * 512 / n8;
-        const bool w16 = plan == 2 || (plan < 0 && waste16 <= waste8);
-        const bool pair = sw().f32_pair && w.wt4p, comp = sw().f32_comp && w.hcw;
-        if (pair && comp) return s1_fused<true, true>(mel, trans, B, T, w, U1, U2, audio, st, mark, w16, plan);
-        if (pair) return s1_fused<true, false>(mel, trans, B, T, w, U1, U2, audio, st, mark, w16, plan);
-        if (comp) return s1_fused<false, true>(mel, trans, B, T, w, U1, U2, audio, st, mark, w16, plan);
-        return s1_fused<false, false>(mel, trans, B, T, w, U1, U2, audio, st, mark, w16, plan);
+int32_t launch_vocoder_fused(const float* mel, int T, const VocLaunchPlan& p, const VocW& w, float* U1, float* U2,
+                             float* audio, hipStream_t st, const std::function<void(int, bool)>& mark) {
+    const Setup& su = setup();
+    if (su.err != hipSuccess) return hip_status(su.err, "fused vocoder: one-time kernel setup");
+    const FormRow& f = kF32Forms[p.form];
+    VocW wv = w;
+    int B = p.tail_g.y, L1 = 4 * T, L2 = 16 * T;  // (every grid's y is the batch)
+    if (w.guard) {
+        // The range policy's on-device redo (voc_redo_kernel): workgroups of the
+        // (usually empty) launch: one per CU by default; the ordered queue needs no
+        // co-residency, so any count is correct (M2_REDO_GRID=n forces n, 0 = every
+        // resident slot)
+        const int full = su.full[f.redo][p.pair][p.f32_comp];
+        const int grid = sw().redo_grid < 0 ? su.cus : (sw().redo_grid == 0 ? full : sw().redo_grid);
+        unsigned* q = const_cast<unsigned*>(reinterpret_cast<const unsigned*>(w.guard_queue));
+        void* args[] = {&mel, &B, &T, &wv, &U1, &U2, &audio, &q};
+        return launch_row(kRows.redo[f.redo][p.pair][p.f32_comp][p.trans], {grid, 1, p.redo_g.threads, p.redo_g.lds}, st,
+                          args, "voc_redo_kernel");
     }
-    if (M == 80 && C == 256) {
-        if (sw().f32_comp && w.hcw)
-            return voc_fused<CfgS2W8, CfgS2W8, CfgS2W8, false, true>(mel, trans, B, T, w, U1, U2, audio, st, mark);
-        return voc_fused<CfgS2W8>(mel, trans, B, T, w, U1, U2, audio, st, mark);
-    }
-    if (M == 32 && C == 64) return voc_fused<CfgTinyW8>(mel, trans, B, T, w, U1, U2, audio, st, mark);
-    return fail(M2_E_SHAPE, "fused vocoder: unsupported (mel_channels, vocoder_channels)");
+    int32_t rc;
+    mark(0, true);
+    void* hargs[] = {&mel, &T, &wv, &U1};
+    rc = launch_row(kRows.head[f.head][p.f32_comp][p.trans], p.head_g, st, hargs, "voc_head_kernel");
+    mark(0, false);
+    if (rc) return rc;
+    mark(1, true);
+    void* margs[] = {&U1, &L1, &wv, &U2};
+    rc = launch_row(kRows.mid[f.mid], p.mid_g, st, margs, "voc_mid_kernel");
+    mark(1, false);
+    if (rc) return rc;
+    mark(2, true);
+    void* targs[] = {&U2, &L2, &wv, &audio};
+    rc = launch_row(kRows.tail[f.tail][p.pair], p.tail_g, st, targs, "voc_tail_kernel");
+    mark(2, false);
+    return rc;
 }
 
 #ifdef M2_STAMPS

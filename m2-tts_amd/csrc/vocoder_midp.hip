@@ -183,37 +183,25 @@ __global__ __launch_bounds__(NWAVES * 64, 4) void midp_kernel(const unsigned cha
     }
 }
 
+static_assert(NWAVES * 64 == kMidpThreads && LDS_BYTES == kMidpLds, "the launch plan's numbers (vocoder_launch.h)");
+
+// NCHC 16 (the headline's strip length as a compile-time constant) and 0 (nch).
 template <int NCHC>
-int32_t launch(int nch, const void* U1, int L1, int B, const vx_u32x4* W, const float* bias, void* U2,
-               hipStream_t st, const int32_t* dT) {
-    static bool attr = false;
-    if (!attr) {
-        M2_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(midp_kernel<NCHC>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-        attr = true;
-    }
-    hipLaunchKernelGGL(midp_kernel<NCHC>, dim3(cdiv(L1, 16 * nch), B), dim3(NWAVES * 64), LDS_BYTES, st,
-                       static_cast<const unsigned char*>(U1), L1, nch, W, bias, static_cast<unsigned char*>(U2), dT);
-    M2_LAUNCHED("midp_kernel");
-    return M2_OK;
+KernelRow row() {
+    return {reinterpret_cast<const void*>(&midp_kernel<NCHC>), NWAVES * 64, LDS_BYTES};
 }
+const KernelRow kRows[2] = {row<16>(), row<0>()};  // [nch != 16]
 
 }  // namespace mp
 
 const char* const kVocMidpKernelName = "midp_kernel (ConvT2 + ResBlock2, pipelined)";
 
-int32_t launch_vocoder_midp(const void* U1, int L1, int B, const vx_u32x4* W, const float* bias, void* U2,
-                            hipStream_t st, const int32_t* dT) {
-    if (B == 0 || L1 == 0) return M2_OK;
-    // Strip length (16-column chunks of U1 per workgroup, a launch argument):
-    // the one from 4 to 256 minimising rounds of 256 workgroups (one per CU)
-    // x pipeline steps (stage1 B = 32, L1 = 2000: 8 strips of 16 chunks, one
-    // round; the round-4 sweep at 8 / 16 / 32 measured 23.1 / 20.0 / 29.9 us).
-    // M2_MIDP_NCH forces one.
-    int nch = sw().midp_nch > 0 ? std::min(sw().midp_nch, 4096) : 0;
-    if (!nch) nch = pipe::pick_strip(cdiv(L1, 16), B, 4, 256, 4);
-    return nch == 16 ? mp::launch<16>(nch, U1, L1, B, W, bias, U2, st, dT)
-                     : mp::launch<0>(nch, U1, L1, B, W, bias, U2, st, dT);
+int32_t launch_vocoder_midp(const void* U1, int L1, int nch, const VocGrid& g, const vx_u32x4* W, const float* bias,
+                            void* U2, hipStream_t st, const int32_t* dT) {
+    static const hipError_t attr = set_rows_lds(mp::kRows, 2);  // once, thread-safe; a failure stays
+    if (attr != hipSuccess) return hip_status(attr, "midp_kernel: hipFuncSetAttribute (one-time setup)");
+    void* args[] = {&U1, &L1, &nch, &W, &bias, &U2, &dT};
+    return launch_row(mp::kRows[nch != 16], g, st, args, "midp_kernel");
 }
 
 // ---------------------------------------------------------------------------

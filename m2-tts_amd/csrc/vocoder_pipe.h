@@ -1,7 +1,8 @@
 // What the pipelined split-f16 vocoder kernels share (vocoder_midp.hip,
 // vocoder_tailp.hip, vocoder_tailp2.hip): the device helpers of a pipeline
 // role, the host packers that cut a dense polyphase matrix into MFMA weight
-// fragments, the composed output layer and the strip-length choice.  Slot
+// fragments, the composed output layer.  (The strip-length choice is part of the launch plan:
+// pipe::pick_strip, vocoder_launch.h.)  Slot
 // tables, ring layouts and the roles themselves belong to each kernel.
 #pragma once
 #include <cmath>
@@ -48,20 +49,6 @@ constexpr int last_step(int nch, int nl) { return nch - 1 + off_l(nl - 1); }
 __device__ __forceinline__ int ring_row(int R, int j, int c) {
     const int r = 16 * j + c;
     return r < 0 ? r + R : (r >= R ? r - R : r);
-}
-
-// Strip length (16-column chunks per workgroup): the one in [nmin, 256]
-// minimising rounds of wgs_per_round workgroups x (strip + extra_steps
-// pipeline steps), the shortest on a tie.
-inline int pick_strip(int chunks, int B, int nmin, int wgs_per_round, int extra_steps) {
-    int nch = 0;
-    long best = -1;
-    for (int n = nmin; n <= 256; ++n) {
-        const long wgs = (long)cdiv(chunks, n) * B, rounds = (wgs + wgs_per_round - 1) / wgs_per_round;
-        const long cost = rounds * (n + extra_steps);
-        if (best < 0 || cost < best) best = cost, nch = n;
-    }
-    return nch;
 }
 
 // ---------------------------------------------------------------------------

@@ -487,41 +487,30 @@ __global__ __launch_bounds__(nwaves(NL) * 64, 1) void tailp2_kernel(const unsign
     }
 }
 
+static_assert(nwaves(6) * 64 == tailp2_threads(6) && nwaves(7) * 64 == tailp2_threads(7) &&
+                  lds_bytes(6) == tailp2_lds(6) && lds_bytes(7) == tailp2_lds(7),
+              "the launch plan's numbers (vocoder_launch.h)");
+
+// [nl != 7]
 template <int NL>
-int32_t launch_nl(int nch, const void* U2, int L2, int B, const vx_u32x4* W, const float* bias, float* audio,
-                  int* rflag, hipStream_t st, const int32_t* dT, const VocRedo& rd) {
-    static bool attr = false;
-    if (!attr) {
-        M2_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(tailp2_kernel<NL>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes(NL)));
-        attr = true;
-    }
-    hipLaunchKernelGGL((tailp2_kernel<NL>), dim3(cdiv(L2, 16 * nch), B), dim3(nwaves(NL) * 64), lds_bytes(NL), st,
-                       static_cast<const unsigned char*>(U2), L2, nch, W, bias, audio, rflag, dT, rd);
-    M2_LAUNCHED("tailp2_kernel");
-    return M2_OK;
+KernelRow row() {
+    return {reinterpret_cast<const void*>(&tailp2_kernel<NL>), nwaves(NL) * 64, lds_bytes(NL)};
 }
+const KernelRow kRows[2] = {row<7>(), row<6>()};
 
 }  // namespace tp2
 
 const char* const kVocTailp2KernelName =
     "tailp2_kernel (stage2 ConvT3 + ResBlock3 + ConvT4 + ResBlock4 + output_conv, pipelined)";
 
-int32_t launch_vocoder_tailp2(const void* U2, int L2, int B, const vx_u32x4* W, const float* bias, float* audio,
-                              int* rflag, hipStream_t st, const int32_t* dT, const VocRedo& rd) {
-    if (B == 0 || L2 == 0) return M2_OK;
-    // Strip length (chunks of 16 columns): the one minimising rounds x (nch +
-    // NL pipeline steps) at one workgroup per CU, any length from 8 to 256
-    // (the kernel takes it at run time: 16 x 2600 gets 256 strips of 163
-    // chunks, one round, where the instantiated lengths of round 4 gave 224
-    // strips of 192).  M2_TAILP2_NCH forces one; M2_TAILP2_SEVEN=1 the
-    // seven-layer form (switch table, m2_common.h).
-    const bool seven = sw().tailp2_seven;
-    const int nl = seven ? 7 : 6;
-    int nch = sw().tailp2_nch > 0 ? std::min(sw().tailp2_nch, 4096) : 0;
-    if (!nch) nch = pipe::pick_strip(cdiv(L2, 16), B, 8, 256, nl);
-    return seven ? tp2::launch_nl<7>(nch, U2, L2, B, W, bias, audio, rflag, st, dT, rd)
-                 : tp2::launch_nl<6>(nch, U2, L2, B, W, bias, audio, rflag, st, dT, rd);
+int32_t launch_vocoder_tailp2(const void* U2, int L2, int nl, int nch, const VocGrid& g, const vx_u32x4* W,
+                              const float* bias, float* audio, int* rflag, hipStream_t st, const int32_t* dT,
+                              const VocRedo& rd) {
+    static const hipError_t attr = set_rows_lds(tp2::kRows, 2);  // once, thread-safe; a failure stays
+    if (attr != hipSuccess) return hip_status(attr, "tailp2_kernel: hipFuncSetAttribute (one-time setup)");
+    VocRedo rdv = rd;
+    void* args[] = {&U2, &L2, &nch, &W, &bias, &audio, &rflag, &dT, &rdv};
+    return launch_row(tp2::kRows[nl != 7], g, st, args, "tailp2_kernel");
 }
 
 // ---------------------------------------------------------------------------

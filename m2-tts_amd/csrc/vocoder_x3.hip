@@ -37,6 +37,7 @@
 
 #include "m2_common.h"
 #include "vocoder_fused.h"
+#include "vocoder_launch.h"
 #include "vocoder_midp.h"
 
 namespace m2 {
@@ -51,17 +52,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ f32x4 mfma_h(u32x4 a, u32x4 b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, a), __builtin_bit_cast(h8, b), c, 0, 0, 0);
 }
-
-// Row stride in bytes for C channels: >= 4C, multiple of 16, (RS/16) % 4 == 2
-// (C = 8: 32 B, 2-way conflicts between rows 8 apart are accepted).
-constexpr int rs_for(int C) {
-    int u = (4 * C + 15) / 16;
-    if (C <= 8) return u * 16;
-    while (u % 4 != 2) ++u;
-    return u * 16;
-}
-constexpr int rup16(int n) { return (n + 15) / 16 * 16; }
-constexpr int cmax(int a, int b) { return a > b ? a : b; }
 
 // An LDS activation window: rows of RS bytes, absolute position of row 0.
 struct XW {
@@ -837,174 +827,6 @@ __device__ __forceinline__ void gstore_rows(unsigned char* __restrict__ g, int L
 
 // ---------------------------------------------------------------------------
 // Window plans (rows; the same receptive-field arithmetic as the f32 plans).
-// Two LDS regions per kernel, A then B, with buffers aliased by lifetime.
-// Region-A buffers are sized to the rows actually written; the garbage
-// columns of a partial 16-wide tile may read past them into region B, which
-// only feeds columns that are never stored (an MFMA output column depends
-// on its own B column only).  Region-B buffers keep the full read extent.
-template <int MP, int C, int TF, bool PL = false>
-struct HeadPlan {  // A: a0 | h   B: mel | u
-    static constexpr int C1 = C / 2;
-    static constexpr int RS_M = rs_for(MP), RS_C = rs_for(C), RS_1 = rs_for(C1);
-    static constexpr int MEL_N = TF + 6, A0_N = TF + 4, NQ = TF + 2, H_N = 4 * TF + 2, O_N = 4 * TF;
-    static constexpr int CAP_MEL = cmax(MEL_N, rup16(A0_N) + 2);
-    static constexpr int CAP_U = cmax(4 * NQ, rup16(H_N) + 4);
-    // PL: the phase-planar path keeps h and u as 4 planes of 64 rows
-    static constexpr int RA = cmax(A0_N * RS_C, cmax(H_N, PL ? 4 * 64 : 0) * RS_1);
-    static constexpr int LDS_BYTES = RA + cmax(CAP_MEL * RS_M, cmax(CAP_U, PL ? 4 * 64 + 4 : 0) * RS_1);
-};
-
-template <int CI, int W>
-struct MidPlan {  // A: in | h   B: u
-    static constexpr int CO = CI / 2;
-    static constexpr int RS_I = rs_for(CI), RS_O = rs_for(CO);
-    static constexpr int IN_N = W + 4, NQ = W + 2, H_N = 4 * W + 2, O_N = 4 * W;
-    static constexpr int CAP_U = cmax(4 * NQ, rup16(H_N) + 4);
-    static constexpr int RA = cmax(IN_N * RS_I, H_N * RS_O);
-    static constexpr int LDS_BYTES = RA + CAP_U * RS_O;
-};
-
-template <int CI, int W>
-struct TailPlan {  // A: in | h3 | u4   B: u3 | h4
-    static constexpr int C3 = CI / 2, C4 = CI / 4;
-    static constexpr int RS_I = rs_for(CI), RS_3 = rs_for(C3), RS_4 = rs_for(C4);
-    static constexpr int IN_N = W + 8, NQ3 = W + 6, H3_N = 2 * W + 8, O3_N = 2 * W + 6;
-    static constexpr int NQ4 = 2 * W + 4, H4_N = 4 * W + 4, O4_N = 4 * W + 2, A_N = 4 * W;
-    static constexpr int CAP_U3 = cmax(2 * NQ3, cmax(rup16(H3_N) + 3, rup16(NQ4) + 5));
-    static constexpr int CAP_H4 = cmax(H4_N, rup16(O4_N) + 2);
-    static constexpr int RA = cmax(IN_N * RS_I, cmax(H3_N * RS_3, 2 * NQ4 * RS_4));
-    static constexpr int LDS_BYTES = RA + cmax(CAP_U3 * RS_3, CAP_H4 * RS_4);
-};
-
-// Tilings.  Per kernel: waves per workgroup (*W), window (TF frames / W2 /
-// W3 positions), launch-bound waves per SIMD (*MIN: 4 -> <= 128 VGPRs), and
-// NT_* = tile-chunk size per layer, chosen so each layer's items come to a
-// multiple of the wave count.  Stage1 at B=32, T=500 (bench): head 8 x 32 =
-// 256 workgroups (one per CU), mid 16 x 32 = 512 (two rounds), tail 48 x 32 =
-// 1536 at two per CU (three full rounds).
-#ifndef X3_HEAD_TF  // head tiling experiments (tools/probe): frames per window, waves, tile chunks
-#define X3_HEAD_TF 63
-#define X3_HEAD_HW 16
-#define X3_NT_IN 3
-#define X3_NT_T1 5
-#define X3_NT_R1 4
-#define X3_G_T1 1
-#define X3_G_R1 1
-#endif
-#ifndef X3_PLANAR  // stage1 head: phase-planar ConvT1 / ResBlock1 (0: position-major x3 layers)
-#define X3_PLANAR 1
-#endif
-struct CfgS1 {
-    static constexpr int PDM = 4;
-    static constexpr int M = 64, MP = 64, C = 128;
-    static constexpr int TF = X3_HEAD_TF, HW = X3_HEAD_HW, HMIN = 4;
-    static constexpr int W2 = 125, MW = 16, MMIN = 4;
-    static constexpr int W3 = 168, TW = 8, TMIN = 4;
-    static constexpr int NT_IN = X3_NT_IN, NT_T1 = X3_NT_T1, NT_R1 = X3_NT_R1, NT_T2 = 4, NT_R2 = 4, NT_T3 = 3,
-                         NT_R3 = 3, NT_T4 = 3, NT_R4 = 6;
-    // head ConvT1 / ResBlock1: m-blocks per item sharing B (2: half the B reads)
-    static constexpr int G_T1 = X3_G_T1, G_R1 = X3_G_R1;
-};
-#ifndef X3S2_TF  // stage2 tiling experiments (tools/probe/s2_tiles.sh)
-#define X3S2_TF 16
-#define X3S2_NT_R1 5
-#endif
-#ifndef X3S2_W2
-#define X3S2_W2 30
-#define X3S2_NT_R2 4
-#endif
-#ifndef X3S2_W3
-#define X3S2_W3 120
-#define X3S2_NT_T3 4
-#define X3S2_NT_R3 4
-#endif
-#ifndef X3S2_HW  // stage2 head waves per workgroup (tiling experiments)
-#define X3S2_HW 8
-#endif
-#ifndef X3S2_HBP  // stage2 head: B-fragment reads one k-block ahead (CfgS2::HBP, mma_x3 BP)
-#define X3S2_HBP 1
-#endif
-#ifndef X3S2W_HBP  // the 16-wave stage2 head of large grids (CfgS2H24::HBP)
-#define X3S2W_HBP 2
-#endif
-#ifndef X3S2W_TF  // the 16-wave stage2 head's window (CfgS2H24::TF)
-#define X3S2W_TF 24
-#endif
-#ifndef X3S2A_W2  // the small-grid stage2 mid window (CfgS2Alt::W2)
-#define X3S2A_W2 33
-#endif
-#ifndef X3S2_PDM  // stage2 weight-fragment k-blocks in flight per item (mma_x3)
-#define X3S2_PDM 4
-#endif
-struct CfgS2 {
-    static constexpr int M = 80, MP = 96, C = 256;
-    static constexpr int TF = X3S2_TF, HW = X3S2_HW, HMIN = 2;
-    static constexpr int W2 = X3S2_W2, MW = 8, MMIN = 2;
-    static constexpr int W3 = X3S2_W3, TW = 8, TMIN = 2;
-    static constexpr int NT_IN = 2, NT_T1 = 2, NT_R1 = X3S2_NT_R1, NT_T2 = 4, NT_R2 = X3S2_NT_R2, NT_T3 = X3S2_NT_T3,
-                         NT_R3 = X3S2_NT_R3, NT_T4 = 4, NT_R4 = 4;
-    static constexpr int G_T1 = 1, G_R1 = 1;
-    // weight k-blocks in flight per item (8 VGPRs each).  4, as stage1: 8 and
-    // 12 (the 256-VGPR budget of 8 waves at one workgroup per CU allows them)
-    // measured level or slower - head 25.8 / 26.3 / 27.0 us at 8x500, mid
-    // 184.2 / 184.4 / 185.2 us at 16x2600 (profiles/r04/r04b_pdm_pipeline_ab.txt):
-    // the stage2 head and mid are not bound by the latency of their weight
-    // stream
-    static constexpr int PDM = X3S2_PDM;
-    // head B fragments one k-block ahead (mma_x3 BP; 116 -> 156 VGPRs, one
-    // workgroup per CU either way): head 26.5 -> 25.0 us at 8x500; in the mid
-    // kernels it measured slower (24.0 -> 26.0 us at 8x500, 186 -> 212 us at
-    // 16x2600: 4 -> 3 waves per SIMD), in the 16-wave H24 head level (172 ->
-    // 175 us, spills; its hi-only form, BP 2, 173.6 -> 171.5 us: CfgS2H24) -
-    // profiles/r05/r05g_bpipe_ab.txt, r05r_head_bp2_ab.txt
-    static constexpr int HBP = X3S2_HBP;
-};
-// Stage2 mid / tail tilings for small grids (run<CfgS2> picks per call): at
-// B=8, T=500 the default windows make 576 mid workgroups (1.1 rounds of 512
-// slots at two per CU) and 536 tail workgroups (2.1 rounds of 256 at one
-// per CU); 32 / 125 make 504 and 512 (one and two full rounds), at 1.20x /
-// 1.075x the time per workgroup (5-tile chunks where 4 were enough).
-// Measured B=8 T=500: mid 26.4 -> 22.9 us, tail 35.5 -> 26.1 us; large grids
-// keep the defaults (tools/probe/s2_tiles.sh).  Since round 5 the windows
-// are 30 and 33 positions (same tiles, fewer workgroups: below).
-struct CfgS2Alt : CfgS2 {
-    static constexpr int W2 = X3S2A_W2, NT_R2 = 5;
-    static constexpr int W3 = 125, NT_T3 = 5, NT_R3 = 5;
-};
-constexpr double kAltMidCost = 1.20, kAltTailCost = 1.075;
-// Stage2 head windows of 24 frames for large grids (composed head: less
-// weight streaming per frame; 16x2600 0.569 -> 0.548 ms, 64x500 0.430 ->
-// 0.421 ms per vocoder step, but 8x500 0.072 -> 0.075 ms: 168 workgroups
-// leave CUs idle), taken when the 16-frame grid has >= 1024 workgroups.
-// 16 waves per workgroup there (more latency hiding at one workgroup per CU:
-// head 140.8 -> 135.2 us at 64x500, 170.6 -> 165.4 at 16x2600; at 8x500 the
-// 16-frame, 8-wave head stays, tools/probe/s2_tiles.sh with X3S2_HW=16).
-struct CfgS2H24 : CfgS2 {
-    static constexpr int TF = X3S2W_TF, HW = 16;
-    static constexpr int PDM = 4;  // 16 waves: 128 VGPRs per wave
-    static constexpr int HBP = X3S2W_HBP;
-};
-constexpr long kS2WideHeadWGs = 1024;  // in 16-frame windows
-// Each window's layers run whole 16-row m-tiles: the head's ResBlock1 covers
-// 4 TF + 2 rows (16 and 19 frames: 5 tiles, 24 and 27: 7), the mid's
-// ResBlock2 4 W + 2 and its ConvT2 W + 2 rows per phase (28 and 30
-// positions: 8 and 2 tiles, 32 and 33: 10 with NT_R2 = 5, and 3).  So the
-// 19 / 27-frame heads and the 30 / 33-position mids cost what the 16 / 24 /
-// 28 / 32 ones do per workgroup and make fewer workgroups; run<CfgS2> takes
-// the fewer rounds of workgroup slots, the smaller window when the rounds tie.
-// Bit-identical audio either way (every output sums the same products in the
-// same order).  Alternated twice (profiles/r05/r05ab_windows_ab.txt): head
-// 38.9 -> 27.2 us at 16x262 (272 -> 224 workgroups: one round of 256),
-// 146.3 -> 132.9 at 128x262, 141.2 -> 128.0 at 64x500; mid 184.4 -> 176.6 us
-// at 16x2600, 149.1 -> 145.2 at 128x262, 26.7 -> 25.2 at 16x262 (W33:
-// 512 workgroups, one round of two per CU).
-struct CfgS2T19 : CfgS2 {
-    static constexpr int TF = 19;
-};
-struct CfgS2H27 : CfgS2H24 {
-    static constexpr int TF = 27;
-};
-
 // Diagnostic build only (-DM2_STAMPS): per-wave s_memtime stamps at phase
 // boundaries, [kernel][workgroup][wave][16] (tools/probe/stamps.py --x3).
 #ifdef M2_STAMPS
@@ -1038,42 +860,6 @@ __device__ unsigned long long g_x3_stamps[3][4096][16][16];
     } while (0)
 #endif
 
-// Window x and utterance y of a head workgroup, XCD-aware: workgroups go to
-// the 8 XCDs round-robin by linear id, and with x fastest the 8 windows of an
-// utterance land on 8 different XCDs, each of which fetches the mel lines
-// its window shares with its neighbours ([M][T] rows: a 69-frame window of a
-// channel row spans 3-4 lines of 128 B): FETCH_SIZE grew 0.22 MB per
-// utterance against 0.13 MB of mel at T = 500 (profiles/r04/r04c_head_fetch_*).
-// With B a multiple of 8 XCD k could take every window of utterances
-// b = k mod 8, so shared lines are fetched once per utterance: FETCH 9.66 ->
-// 7.71 MB per launch at B=32 ((FETCH - the 2.7 MB of weights per 8 XCDs) /
-// mel 1.7 -> 1.22), but the headline step +0.3 % (0.07158 / 0.07148 /
-// 0.07172 vs 0.07145 / 0.07138 / 0.07123 ms alternated,
-// profiles/r04/r04h_head_*, r04k_headline_xcd_ab.txt): the over-read lines
-// are served by the Infinity Cache, and the plain order spreads an
-// utterance's edge windows over the XCDs.  Kept as a build option
-// (-DX3_HEAD_XCD=1); the plain order is the default.
-#ifndef X3_HEAD_XCD
-#define X3_HEAD_XCD 0
-#endif
-__device__ __forceinline__ void head_tile(int& x, int& y) {
-    x = blockIdx.x;
-    y = blockIdx.y;
-    if (X3_HEAD_XCD && (gridDim.y & 7) == 0) {
-        const int L = blockIdx.y * gridDim.x + blockIdx.x, k = L & 7, s = L >> 3, nx = gridDim.x;
-        y = 8 * (s / nx) + k;
-        x = s - (s / nx) * nx;
-    }
-}
-
-// The stage1 head runs ConvT1 / ResBlock1 phase-planar when one item per wave
-// covers them: planes of 64 rows hold TF + 2 <= 65 input columns and the
-// (phase, m-block) items of the C/2-channel layers number exactly HW.
-template <class Cfg>
-constexpr bool head_planar() {
-    return X3_PLANAR && Cfg::TF + 1 <= 64 && 4 * (Cfg::C / 2 / 16) == Cfg::HW && Cfg::G_T1 == 1 && Cfg::G_R1 == 1;
-}
-
 // COMP (stage1 planar head): input_conv composed into ConvT1
 // (head_convT1c_planar; w.hc / w.hcb / w.hce).
 template <class Cfg, bool TRANS, bool COMP = false>
@@ -1090,8 +876,7 @@ __global__ __launch_bounds__(Cfg::HW * 64, Cfg::HMIN) void x3_head_kernel(const 
         else if (pr >= 3) __builtin_amdgcn_s_setprio(3);
     }
     constexpr int M = Cfg::M, MP = Cfg::MP, C = Cfg::C, TF = Cfg::TF;
-    int wx, wy;
-    head_tile(wx, wy);
+    const int wx = blockIdx.x, wy = blockIdx.y;
     if (w.dT) {  // speculative launch: T was the capacity
         T = dev_frames(w.dT, T);
         if (wx * TF >= T) return;
@@ -1106,12 +891,12 @@ __global__ __launch_bounds__(Cfg::HW * 64, Cfg::HMIN) void x3_head_kernel(const 
     XW uw{lds + Pl::RA, 4 * f0 - 4};
     constexpr int NW = Cfg::HW;
     using I0 = Conv3Items<MP, C, Cfg::NT_IN, Pl::A0_N, 1>;
-    using I1 = ConvTItems<C, C1, 4, Cfg::NT_T1, Pl::NQ, Cfg::G_T1>;
-    using I2 = Conv3Items<C1, C1, Cfg::NT_R1, Pl::H_N, Cfg::G_R1>;
-    using I3 = Conv3Items<C1, C1, Cfg::NT_R1, Pl::O_N, Cfg::G_R1>;
+    using I1 = ConvTItems<C, C1, 4, Cfg::NT_T1, Pl::NQ, 1>;
+    using I2 = Conv3Items<C1, C1, Cfg::NT_R1, Pl::H_N, 1>;
+    using I3 = Conv3Items<C1, C1, Cfg::NT_R1, Pl::O_N, 1>;
     // One item per wave in every layer (stage1): weight fragments handed
     // from layer to layer across the barriers (APipe).
-    constexpr bool ONE = Cfg::G_T1 == 1 && Cfg::G_R1 == 1 && I0::N == NW && I1::N == NW && I2::N == NW &&
+    constexpr bool ONE = I0::N == NW && I1::N == NW && I2::N == NW &&
                          I3::N == NW && pd_of<MP, 3, 1>() == 4 && pd_of<C, 2, 1>() == 4 && pd_of<C1, 3, 1>() == 4;
     // phase-planar ConvT1 / ResBlock1: planes of 64 rows hold TF + 2 <= 65
     // input columns, one item per wave = (phase, m-block)
@@ -1216,54 +1001,31 @@ __global__ __launch_bounds__(Cfg::HW * 64, Cfg::HMIN) void x3_head_kernel(const 
         XSTAMP(0, 1);
         __syncthreads();
         XSTAMP(0, 2);
-        if constexpr (PLANAR) {
-            // phase-planar ConvT1 / ResBlock1 (u planes in region B, h planes in region A)
-            unsigned char* up = lds + Pl::RA;
-            unsigned char* hp = lds;
-            xconv3<MP, C, Cfg::NT_IN, ACT_NONE, false, Pl::RS_M, Pl::RS_C, Pl::A0_N, 1, NW>(
-                w.wi, w.bi, melw, a0w, f0 - 2, T, &ap, w.wt[0] + (size_t)wv * nkb_of<C, 2>() * 128 + (threadIdx.x & 63));
-            XSTAMP(0, 3);
-            __syncthreads();
-            XSTAMP(0, 4);
-            constexpr int MB1 = C1 / 16;
-            head_convT1_planar<C, C1, Pl::RS_C, Pl::RS_1>(w.wt[0], w.bt[0], a0w, up, f0, 4 * T, &ap,
-                                                        w.w1[0] + (size_t)(wv % MB1) * nkb_of<C1, 3>() * 128 +
-                                                            (threadIdx.x & 63));
-            XSTAMP(0, 5);
-            __syncthreads();
-            XSTAMP(0, 6);
-            head_rb1_planar<C1, Pl::RS_1, false>(w.w1[0], w.b1[0], up, hp, nullptr, f0, TF, 4 * T, &ap,
-                                                 w.w2[0] + (size_t)(wv % MB1) * nkb_of<C1, 3>() * 128 +
-                                                     (threadIdx.x & 63),
-                                                 nullptr);
-            XSTAMP(0, 7);
-            __syncthreads();
-            XSTAMP(0, 8);
-            head_rb1_planar<C1, Pl::RS_1, true>(w.w2[0], w.b2[0], hp, nullptr, up, f0, TF, 4 * T, &ap, nullptr,
-                                                U1 + (size_t)b * 4 * T * 4 * C1);
-            XSTAMP(0, 9);
-            XSTAMP_RT(0, 15);
-            return;
-        }
+        static_assert(PLANAR, "one item per wave: the phase-planar head");
+        // phase-planar ConvT1 / ResBlock1 (u planes in region B, h planes in region A)
+        unsigned char* up = lds + Pl::RA;
+        unsigned char* hp = lds;
         xconv3<MP, C, Cfg::NT_IN, ACT_NONE, false, Pl::RS_M, Pl::RS_C, Pl::A0_N, 1, NW>(
-            w.wi, w.bi, melw, a0w, f0 - 2, T, &ap, I1::wp(w.wt[0], wv));
+            w.wi, w.bi, melw, a0w, f0 - 2, T, &ap, w.wt[0] + (size_t)wv * nkb_of<C, 2>() * 128 + (threadIdx.x & 63));
         XSTAMP(0, 3);
         __syncthreads();
         XSTAMP(0, 4);
-        xconvT<C, C1, 4, Cfg::NT_T1, Pl::RS_C, Pl::RS_1, Pl::NQ, 1, NW>(w.wt[0], w.bt[0], a0w, uw, f0 - 1, 4 * T,
-                                                                     &ap, I2::wp(w.w1[0], wv));
+        constexpr int MB1 = C1 / 16;
+        head_convT1_planar<C, C1, Pl::RS_C, Pl::RS_1>(w.wt[0], w.bt[0], a0w, up, f0, 4 * T, &ap,
+                                                    w.w1[0] + (size_t)(wv % MB1) * nkb_of<C1, 3>() * 128 +
+                                                        (threadIdx.x & 63));
         XSTAMP(0, 5);
         __syncthreads();
         XSTAMP(0, 6);
-        xconv3<C1, C1, Cfg::NT_R1, ACT_LEAKY, false, Pl::RS_1, Pl::RS_1, Pl::H_N, 1, NW>(
-            w.w1[0], w.b1[0], uw, hw, 4 * f0 - 1, 4 * T, &ap, I3::wp(w.w2[0], wv));
+        head_rb1_planar<C1, Pl::RS_1, false>(w.w1[0], w.b1[0], up, hp, nullptr, f0, TF, 4 * T, &ap,
+                                             w.w2[0] + (size_t)(wv % MB1) * nkb_of<C1, 3>() * 128 +
+                                                 (threadIdx.x & 63),
+                                             nullptr);
         XSTAMP(0, 7);
         __syncthreads();
         XSTAMP(0, 8);
-        // ResBlock1 conv2 + x straight to U1 (rows of hi[C1] lo[C1]): no LDS
-        // round trip, no last barrier, no separate store phase
-        xconv3<C1, C1, Cfg::NT_R1, ACT_NONE, true, Pl::RS_1, Pl::RS_1, Pl::O_N, 1, NW, true>(
-            w.w2[0], w.b2[0], hw, uw, 4 * f0, 4 * T, &ap, nullptr, U1 + (size_t)b * 4 * T * 4 * C1);
+        head_rb1_planar<C1, Pl::RS_1, true>(w.w2[0], w.b2[0], hp, nullptr, up, f0, TF, 4 * T, &ap, nullptr,
+                                            U1 + (size_t)b * 4 * T * 4 * C1);
         XSTAMP(0, 9);
         XSTAMP_RT(0, 15);
         return;
@@ -1276,18 +1038,16 @@ __global__ __launch_bounds__(Cfg::HW * 64, Cfg::HMIN) void x3_head_kernel(const 
         XSTAMP(0, 3);
         __syncthreads();
         XSTAMP(0, 4);
-        xconvT<C, C1, 4, Cfg::NT_T1, Pl::RS_C, Pl::RS_1, Pl::NQ, Cfg::G_T1>(w.wt[0], w.bt[0], a0w, uw, f0 - 1,
-                                                                            4 * T);
+        xconvT<C, C1, 4, Cfg::NT_T1, Pl::RS_C, Pl::RS_1, Pl::NQ>(w.wt[0], w.bt[0], a0w, uw, f0 - 1, 4 * T);
         XSTAMP(0, 5);
         __syncthreads();
         XSTAMP(0, 6);
-        xconv3<C1, C1, Cfg::NT_R1, ACT_LEAKY, false, Pl::RS_1, Pl::RS_1, Pl::H_N, Cfg::G_R1>(w.w1[0], w.b1[0], uw,
-                                                                                            hw, 4 * f0 - 1, 4 * T);
+        xconv3<C1, C1, Cfg::NT_R1, ACT_LEAKY, false, Pl::RS_1, Pl::RS_1, Pl::H_N>(w.w1[0], w.b1[0], uw, hw, 4 * f0 - 1,
+                                                                                 4 * T);
         XSTAMP(0, 7);
         __syncthreads();
         XSTAMP(0, 8);
-        xconv3<C1, C1, Cfg::NT_R1, ACT_NONE, true, Pl::RS_1, Pl::RS_1, Pl::O_N, Cfg::G_R1>(w.w2[0], w.b2[0], hw, uw,
-                                                                                           4 * f0, 4 * T);
+        xconv3<C1, C1, Cfg::NT_R1, ACT_NONE, true, Pl::RS_1, Pl::RS_1, Pl::O_N>(w.w2[0], w.b2[0], hw, uw, 4 * f0, 4 * T);
     }
     XSTAMP(0, 9);
     __syncthreads();
@@ -1312,16 +1072,13 @@ __global__ __launch_bounds__(Cfg::HW * 64, Cfg::HMIN) void x3_head_kernel(const 
 // planes where midp_kernel reads ring R0.  No loader wave, no U1 in global
 // memory, one launch boundary less.  Every output keeps its operation
 // sequence: U2 is bit-identical to the two launches'.
-// The mid's roles take 12 of the 16 waves (HEADMID_T2W 8: ConvT2 on eight
-// waves, one m-block each, and all 16); the others only keep the step
+// The mid's roles take 12 of the 16 waves; the others only keep the step
 // barriers.  Each role fetches its weight fragments when it starts, as in
 // midp_kernel.
-#ifndef HEADMID_T2W
-#define HEADMID_T2W 4
-#endif
 struct HmPlan {
     using Pl = HeadPlan<CfgS1::MP, CfgS1::C, CfgS1::TF, true>;
-    static constexpr int S_MAX = 4 * CfgS1::TF - 2;  // owned columns + one on either side = the valid positions
+    static constexpr int S_MAX = kHeadmidSMax;  // owned columns + one on either side = the valid positions
+    static_assert(Pl::LDS_BYTES == kHeadmidLds, "the plan's LDS bytes");
     struct Lay {
         static constexpr bool PLANES = true;
         static constexpr int R0_OFF = 0, R1_OFF = 0, R2_OFF = mp::RROWS * mp::RS1;  // (no R0)
@@ -1402,62 +1159,30 @@ __global__ __launch_bounds__(CfgS1::HW * 64, CfgS1::HMIN) void headmid_kernel(co
     unsigned char* u2row = U2 + (size_t)b * 4 * L1 * 128;
     const u32x4* W = w.mp;
     const float* bias = w.mpb;
-    constexpr bool T8 = HEADMID_T2W == 8;
-    const int layer = T8 ? (wv < 8 ? 0 : (wv < 12 ? 1 : 2)) : (wv < 12 ? wv >> 2 : 3);
+    const int layer = wv < 12 ? wv >> 2 : 3;
     if (layer == 2) __builtin_amdgcn_s_setprio(2);  // later layers: younger waves, the step waits for them
     else if (layer == 1) __builtin_amdgcn_s_setprio(1);
     else __builtin_amdgcn_s_setprio(0);
-    if constexpr (T8) {
-        switch (wv) {
-            case 0: mp::layer_role<0, 0, Lay, 0, 1>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
-            case 1: mp::layer_role<0, 0, Lay, 1, 1>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
-            case 2: mp::layer_role<0, 1, Lay, 0, 1>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
-            case 3: mp::layer_role<0, 1, Lay, 1, 1>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
-            case 4: mp::layer_role<0, 2, Lay, 0, 1>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
-            case 5: mp::layer_role<0, 2, Lay, 1, 1>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
-            case 6: mp::layer_role<0, 3, Lay, 0, 1>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
-            case 7: mp::layer_role<0, 3, Lay, 1, 1>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
-            case 8: mp::layer_role<1, 0, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
-            case 9: mp::layer_role<1, 1, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
-            case 10: mp::layer_role<1, 2, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
-            case 11: mp::layer_role<1, 3, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
-            case 12: mp::layer_role<2, 0, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
-            case 13: mp::layer_role<2, 1, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
-            case 14: mp::layer_role<2, 2, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
-            default: mp::layer_role<2, 3, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
-        }
-    } else {
-        switch (wv) {
-            case 0: mp::layer_role<0, 0, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
-            case 1: mp::layer_role<0, 1, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
-            case 2: mp::layer_role<0, 2, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
-            case 3: mp::layer_role<0, 3, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
-            case 4: mp::layer_role<1, 0, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
-            case 5: mp::layer_role<1, 1, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
-            case 6: mp::layer_role<1, 2, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
-            case 7: mp::layer_role<1, 3, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
-            case 8: mp::layer_role<2, 0, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
-            case 9: mp::layer_role<2, 1, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
-            case 10: mp::layer_role<2, 2, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
-            case 11: mp::layer_role<2, 3, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
-            default:  // no role: the step barriers only
+    switch (wv) {
+        case 0: mp::layer_role<0, 0, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
+        case 1: mp::layer_role<0, 1, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
+        case 2: mp::layer_role<0, 2, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
+        case 3: mp::layer_role<0, 3, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
+        case 4: mp::layer_role<1, 0, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
+        case 5: mp::layer_role<1, 1, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
+        case 6: mp::layer_role<1, 2, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
+        case 7: mp::layer_role<1, 3, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
+        case 8: mp::layer_role<2, 0, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
+        case 9: mp::layer_role<2, 1, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
+        case 10: mp::layer_role<2, 2, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
+        case 11: mp::layer_role<2, 3, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
+        default:  // no role: the step barriers only
 #pragma unroll 1
-                for (int s = -1; s <= nch + 2; ++s) pipe::step_barrier();
-                break;
-        }
+            for (int s = -1; s <= nch + 2; ++s) pipe::step_barrier();
+            break;
     }
 }
 
-// Why a call does not take headmid_kernel (null: it does).
-inline const char* headmid_excluded(const VocX& w, bool comp, bool s1) {
-    if (!sw().headmid) return "M2_HEADMID=0";
-    if (!s1) return "not the stage1 shapes";
-    if (w.dT) return "the frame count is on the device: the grid covers the capacity";
-    if (!w.mp || !w.hc || !comp) return "no split packs of the composed head and the pipelined mid (or M2_HEAD_INCONV)";
-    if (sw().midp_nch > 0) return "M2_MIDP_NCH forces the mid's strip length";
-    if (w.prof_slots & 3u) return "events around the head or the mid: the fused launch has no boundary between them";
-    return nullptr;
-}
 std::atomic<long> g_headmid_launches{0};
 
 template <class Cfg>
@@ -1571,195 +1296,117 @@ __global__ __launch_bounds__(Cfg::TW * 64, Cfg::TMIN) void x3_tail_kernel(const 
     XSTAMP(2, 15);
 }
 
-template <typename K>
-int32_t set_lds(K kernel, size_t bytes) {
-    M2_CHECK_SHAPE(bytes <= 160 * 1024, "x3 vocoder: LDS plan exceeds 160 KiB");
-    M2_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)bytes));
-    return M2_OK;
+// One row per kernel instantiation (KernelRow, vocoder_fused.h): the row serves
+// the LDS attribute, the occupancy query and the launch.  Heads by
+// [VocHead][comp][trans] (the 19 / 24 / 27-frame stage2 heads exist composed
+// only: their other rows stay empty), mids and tails by [stage1, stage2,
+// stage2 alt], headmid by [nch == 16][trans].
+struct Rows {
+    KernelRow head[5][2][2], mid[3], tail[3], headmid[2][2];
+};
+// r[trans] of a head / headmid variant
+template <class Cfg, bool COMP>
+void head_rows(KernelRow (&r)[2]) {
+    r[0] = {reinterpret_cast<const void*>(&x3_head_kernel<Cfg, false, COMP>), Cfg::HW * 64, HeadPlanOf<Cfg>::LDS_BYTES};
+    r[1] = {reinterpret_cast<const void*>(&x3_head_kernel<Cfg, true, COMP>), Cfg::HW * 64, HeadPlanOf<Cfg>::LDS_BYTES};
 }
-
-// Workgroup slots of the device for a kernel (CUs x its occupancy), queried
-// once per kernel: the vocoder calls this on every launch decision.
-template <typename K>
-long grid_slots(K kernel, int threads, size_t lds) {
-    int ncu = 0, dev = 0, per = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, reinterpret_cast<const void*>(kernel), threads, lds) !=
-            hipSuccess || per <= 0)
-        per = 1;
-    return (long)per * ncu;
+template <int NCHC>
+void headmid_rows(KernelRow (&r)[2]) {
+    r[0] = {reinterpret_cast<const void*>(&headmid_kernel<false, NCHC>), CfgS1::HW * 64, kHeadmidLds};
+    r[1] = {reinterpret_cast<const void*>(&headmid_kernel<true, NCHC>), CfgS1::HW * 64, kHeadmidLds};
 }
-inline long rounds_of(long n, long slots) { return (n + slots - 1) / slots; }
-
 template <class Cfg>
-int32_t run(const float* mel, bool trans, int B, int T, const VocX& w, void* U1, void* U2, float* audio,
+KernelRow mid_row() {
+    return {reinterpret_cast<const void*>(&x3_mid_kernel<Cfg>), Cfg::MW * 64, MidPlan<Cfg::C / 2, Cfg::W2>::LDS_BYTES};
+}
+template <class Cfg>
+KernelRow tail_row() {
+    return {reinterpret_cast<const void*>(&x3_tail_kernel<Cfg>), Cfg::TW * 64, TailPlan<Cfg::C / 4, Cfg::W3>::LDS_BYTES};
+}
+// (Filled in the order the kernels have always been instantiated in, which is
+// the order of the device code in the object.)
+Rows make_rows() {
+    Rows r;
+    head_rows<CfgS1, false>(r.head[(int)VocHead::S1][0]);
+    head_rows<CfgS1, true>(r.head[(int)VocHead::S1][1]);
+    r.mid[0] = mid_row<CfgS1>();
+    r.tail[0] = tail_row<CfgS1>();
+    headmid_rows<16>(r.headmid[1]);
+    headmid_rows<0>(r.headmid[0]);
+    r.tail[2] = tail_row<CfgS2Alt>();
+    r.mid[2] = mid_row<CfgS2Alt>();
+    head_rows<CfgS2, false>(r.head[(int)VocHead::S2T16][0]);
+    head_rows<CfgS2, true>(r.head[(int)VocHead::S2T16][1]);
+    r.mid[1] = mid_row<CfgS2>();
+    r.tail[1] = tail_row<CfgS2>();
+    head_rows<CfgS2H24, true>(r.head[(int)VocHead::S2H24][1]);
+    head_rows<CfgS2T19, true>(r.head[(int)VocHead::S2T19][1]);
+    head_rows<CfgS2H27, true>(r.head[(int)VocHead::S2H27][1]);
+    return r;
+}
+const Rows kRows = make_rows();
+
+// The one-time setup: every row's LDS attribute, then the workgroup slots the
+// plan's rules weigh.  Thread-safe (a function-local static); a failed
+// hipFuncSetAttribute stays the answer of every later call.
+struct Setup {
+    hipError_t err;
+    VocSlots slots;
+};
+const Setup& setup() {
+    static const Setup s = [] {
+        Setup r;
+        r.err = set_rows_lds(reinterpret_cast<const KernelRow*>(&kRows), sizeof(Rows) / sizeof(KernelRow));
+        auto head = [](VocHead h) { return row_slots(kRows.head[(int)h][1][0]); };  // composed, [B, M, T]
+        r.slots = {head(VocHead::S2T16), head(VocHead::S2T19), head(VocHead::S2H24), head(VocHead::S2H27),
+                   row_slots(kRows.mid[1]), row_slots(kRows.mid[2]), row_slots(kRows.tail[1]), row_slots(kRows.tail[2])};
+        return r;
+    }();
+    return s;
+}
+
+// Launches what the plan names (plan_vocoder_launch, vocoder_launch.h).
+int32_t run(const float* mel, int T, const VocLaunchPlan& p, const VocX& w, void* U1, void* U2, float* audio,
             hipStream_t st, const std::function<void(int, bool)>& mark) {
-    using HP = HeadPlan<Cfg::MP, Cfg::C, Cfg::TF, head_planar<Cfg>()>;
-    using HP24 = HeadPlan<CfgS2H24::MP, CfgS2H24::C, CfgS2H24::TF, false>;
-    using HP19 = HeadPlan<CfgS2T19::MP, CfgS2T19::C, CfgS2T19::TF, false>;
-    using HP27 = HeadPlan<CfgS2H27::MP, CfgS2H27::C, CfgS2H27::TF, false>;
-    using MP = MidPlan<Cfg::C / 2, Cfg::W2>;
-    using TP = TailPlan<Cfg::C / 4, Cfg::W3>;
-    constexpr bool S2 = std::is_same<Cfg, CfgS2>::value, S1 = std::is_same<Cfg, CfgS1>::value;
-    using MPA = MidPlan<CfgS2Alt::C / 2, CfgS2Alt::W2>;
-    using TPA = TailPlan<CfgS2Alt::C / 4, CfgS2Alt::W3>;
-    static bool attr = false;
-    if (!attr) {
-        int32_t rc;
-        if ((rc = set_lds(x3_head_kernel<Cfg, false>, HP::LDS_BYTES))) return rc;
-        if ((rc = set_lds(x3_head_kernel<Cfg, true>, HP::LDS_BYTES))) return rc;
-        if ((rc = set_lds(x3_head_kernel<Cfg, false, true>, HP::LDS_BYTES))) return rc;
-        if ((rc = set_lds(x3_head_kernel<Cfg, true, true>, HP::LDS_BYTES))) return rc;
-        if ((rc = set_lds(x3_mid_kernel<Cfg>, MP::LDS_BYTES))) return rc;
-        if ((rc = set_lds(x3_tail_kernel<Cfg>, TP::LDS_BYTES))) return rc;
-        if constexpr (S2) {
-            if ((rc = set_lds(x3_head_kernel<CfgS2H24, false, true>, HP24::LDS_BYTES))) return rc;
-            if ((rc = set_lds(x3_head_kernel<CfgS2H24, true, true>, HP24::LDS_BYTES))) return rc;
-            if ((rc = set_lds(x3_head_kernel<CfgS2T19, false, true>, HP19::LDS_BYTES))) return rc;
-            if ((rc = set_lds(x3_head_kernel<CfgS2T19, true, true>, HP19::LDS_BYTES))) return rc;
-            if ((rc = set_lds(x3_head_kernel<CfgS2H27, false, true>, HP27::LDS_BYTES))) return rc;
-            if ((rc = set_lds(x3_head_kernel<CfgS2H27, true, true>, HP27::LDS_BYTES))) return rc;
-            if ((rc = set_lds(x3_mid_kernel<CfgS2Alt>, MPA::LDS_BYTES))) return rc;
-            if ((rc = set_lds(x3_tail_kernel<CfgS2Alt>, TPA::LDS_BYTES))) return rc;
-        }
-        if constexpr (S1) {
-            if ((rc = set_lds(headmid_kernel<false, 16>, HmPlan::Pl::LDS_BYTES))) return rc;
-            if ((rc = set_lds(headmid_kernel<true, 16>, HmPlan::Pl::LDS_BYTES))) return rc;
-            if ((rc = set_lds(headmid_kernel<false, 0>, HmPlan::Pl::LDS_BYTES))) return rc;
-            if ((rc = set_lds(headmid_kernel<true, 0>, HmPlan::Pl::LDS_BYTES))) return rc;
-        }
-        attr = true;
-    }
-    bool alt_mid = false, alt_tail = false;
-    if constexpr (S2) {
-        static const long sm0 = grid_slots(x3_mid_kernel<Cfg>, Cfg::MW * 64, MP::LDS_BYTES),
-                          sm1 = grid_slots(x3_mid_kernel<CfgS2Alt>, Cfg::MW * 64, MPA::LDS_BYTES),
-                          st0 = grid_slots(x3_tail_kernel<Cfg>, Cfg::TW * 64, TP::LDS_BYTES),
-                          st1 = grid_slots(x3_tail_kernel<CfgS2Alt>, Cfg::TW * 64, TPA::LDS_BYTES);
-        if (!w.mp && sw().s2_mid_alt >= 0)
-            alt_mid = sw().s2_mid_alt == 1;
-        else if (!w.mp)
-            alt_mid = rounds_of((long)cdiv(4 * T, CfgS2Alt::W2) * B, sm1) * kAltMidCost <
-                      (double)rounds_of((long)cdiv(4 * T, Cfg::W2) * B, sm0);
-        if (!w.tp && !w.tp2)
-            alt_tail = rounds_of((long)cdiv(16 * T, CfgS2Alt::W3) * B, st1) * kAltTailCost <
-                       (double)rounds_of((long)cdiv(16 * T, Cfg::W3) * B, st0);
-    }
-    auto* u1 = static_cast<unsigned char*>(U1);
-    auto* u2 = static_cast<unsigned char*>(U2);
-    auto tail = [&]() -> int32_t {
-        mark(2, true);
-        if (w.tp2) {  // stage2: the pipelined tail (vocoder_tailp2.hip)
-            const int32_t rc = launch_vocoder_tailp2(u2, 16 * T, B, w.tp2, w.tp2b, audio, w.rflag, st, w.dT,
-                                                     VocRedo{w.redo_w, mel, trans});
-            mark(2, false);
-            return rc;
-        }
-        if (w.tp) {  // stage1: the pipelined tail (vocoder_tailp.hip)
-            const int32_t rc = launch_vocoder_tailp(u2, 16 * T, B, w.tp, w.tpb, audio, w.rflag, st, w.dT,
-                                                    VocRedo{w.redo_w, mel, trans});
-            mark(2, false);
-            return rc;
-        }
-        if (S2 && alt_tail)
-            hipLaunchKernelGGL((x3_tail_kernel<CfgS2Alt>), dim3(cdiv(16 * T, CfgS2Alt::W3), B), dim3(Cfg::TW * 64),
-                               TPA::LDS_BYTES, st, u2, 16 * T, w, audio);
-        else
-            hipLaunchKernelGGL((x3_tail_kernel<Cfg>), dim3(cdiv(16 * T, Cfg::W3), B), dim3(Cfg::TW * 64),
-                               TP::LDS_BYTES, st, u2, 16 * T, w, audio);
-        mark(2, false);
-        M2_LAUNCHED("x3_tail_kernel");
-        return M2_OK;
-    };
-    // the composed input_conv o ConvT1 head when packed (stage1; 22.1 -> 19.7
-    // us, profiles/ab/r02l_head_comp.txt); M2_HEAD_INCONV=1 runs the two
-    // layers (A/B and test switch, m2_common.h switch table)
-    const bool comp = w.hc && !sw().head_inconv;
-    if constexpr (S1) {
-        // stage1, host-known T, split packs: the head and the mid in one
-        // launch (headmid_kernel); headmid_excluded names what keeps a call
-        // on the three launches.  n strips of S <= 250 columns per utterance.
-        if (!headmid_excluded(w, comp, S1)) {
-            const int n = cdiv(4 * T, HmPlan::S_MAX), S = cdiv(4 * T, n), nch = cdiv(S, 16);
-            const dim3 g(n, B), b(Cfg::HW * 64);
-            const int lds = HmPlan::Pl::LDS_BYTES;
-            if (nch == 16 && trans)
-                hipLaunchKernelGGL((headmid_kernel<true, 16>), g, b, lds, st, mel, T, w, u2, S, nch);
-            else if (nch == 16)
-                hipLaunchKernelGGL((headmid_kernel<false, 16>), g, b, lds, st, mel, T, w, u2, S, nch);
-            else if (trans)
-                hipLaunchKernelGGL((headmid_kernel<true, 0>), g, b, lds, st, mel, T, w, u2, S, nch);
-            else
-                hipLaunchKernelGGL((headmid_kernel<false, 0>), g, b, lds, st, mel, T, w, u2, S, nch);
-            M2_LAUNCHED("headmid_kernel");
-            g_headmid_launches.fetch_add(1, std::memory_order_relaxed);
-            return tail();
-        }
-    }
-    mark(0, true);
-    const dim3 hg(cdiv(T, Cfg::TF), B), hb(Cfg::HW * 64);
-    // stage2, composed head: the 16-wave heads (24 / 27 frames) on large
-    // grids, the 8-wave heads (16 / 19) below; within a pair the fewer rounds
-    // of workgroup slots, the smaller window on a tie (M2_S2_HEAD_TF forces)
-    int hv = 16;
-    if constexpr (S2) {
-        static const long s16 = grid_slots(x3_head_kernel<Cfg, false, true>, Cfg::HW * 64, HP::LDS_BYTES),
-                          s19 = grid_slots(x3_head_kernel<CfgS2T19, false, true>, CfgS2T19::HW * 64, HP19::LDS_BYTES),
-                          s24 = grid_slots(x3_head_kernel<CfgS2H24, false, true>, CfgS2H24::HW * 64, HP24::LDS_BYTES),
-                          s27 = grid_slots(x3_head_kernel<CfgS2H27, false, true>, CfgS2H27::HW * 64, HP27::LDS_BYTES);
-        auto rounds = [&](int tf, long slots) { return rounds_of((long)cdiv(T, tf) * B, slots); };
-        if (sw().s2_head_tf)
-            hv = sw().s2_head_tf;
-        else if ((long)cdiv(T, 16) * B >= kS2WideHeadWGs)
-            hv = rounds(27, s27) < rounds(24, s24) ? 27 : 24;
-        else
-            hv = rounds(19, s19) < rounds(16, s16) ? 19 : 16;
-    }
-    auto head = [&](auto cfg) {
-        using HC = decltype(cfg);
-        using HPc = HeadPlan<HC::MP, HC::C, HC::TF, false>;
-        const dim3 g(cdiv(T, HC::TF), B), b(HC::HW * 64);
-        if (trans)
-            hipLaunchKernelGGL((x3_head_kernel<HC, true, true>), g, b, HPc::LDS_BYTES, st, mel, T, w, u1);
-        else
-            hipLaunchKernelGGL((x3_head_kernel<HC, false, true>), g, b, HPc::LDS_BYTES, st, mel, T, w, u1);
-    };
-    if (S2 && comp && hv != 16) {
-        if constexpr (S2) {
-            if (hv == 19)
-                head(CfgS2T19{});
-            else if (hv == 24)
-                head(CfgS2H24{});
-            else
-                head(CfgS2H27{});
-        }
-    } else if (comp && trans)
-        hipLaunchKernelGGL((x3_head_kernel<Cfg, true, true>), hg, hb, HP::LDS_BYTES, st, mel, T, w, u1);
-    else if (comp)
-        hipLaunchKernelGGL((x3_head_kernel<Cfg, false, true>), hg, hb, HP::LDS_BYTES, st, mel, T, w, u1);
-    if (!comp && trans)
-        hipLaunchKernelGGL((x3_head_kernel<Cfg, true>), hg, hb, HP::LDS_BYTES, st, mel, T, w, u1);
-    else if (!comp)
-        hipLaunchKernelGGL((x3_head_kernel<Cfg, false>), hg, hb, HP::LDS_BYTES, st, mel, T, w, u1);
-    mark(0, false);
-    M2_LAUNCHED("x3_head_kernel");
-    mark(1, true);
-    if (w.mp) {  // stage1: the pipelined mid stage (vocoder_midp.hip)
-        const int32_t rc = launch_vocoder_midp(u1, 4 * T, B, w.mp, w.mpb, u2, st, w.dT);
-        if (rc) return rc;
-    } else if (S2 && alt_mid) {
-        hipLaunchKernelGGL((x3_mid_kernel<CfgS2Alt>), dim3(cdiv(4 * T, CfgS2Alt::W2), B), dim3(Cfg::MW * 64),
-                           MPA::LDS_BYTES, st, u1, 4 * T, w, u2);
-        M2_LAUNCHED("x3_mid_kernel");
+    if (setup().err != hipSuccess) return hip_status(setup().err, "x3 vocoder: hipFuncSetAttribute (one-time setup)");
+    int32_t rc;
+    int L1 = 4 * T, L2 = 16 * T;
+    VocX wv = w;
+    if (p.headmid) {
+        void* args[] = {&mel, &T, &wv, &U2, const_cast<int*>(&p.hm_S), const_cast<int*>(&p.hm_nch)};
+        if ((rc = launch_row(kRows.headmid[p.hm_nch == 16][p.trans], p.head_g, st, args, "headmid_kernel"))) return rc;
+        g_headmid_launches.fetch_add(1, std::memory_order_relaxed);
     } else {
-        hipLaunchKernelGGL((x3_mid_kernel<Cfg>), dim3(cdiv(4 * T, Cfg::W2), B), dim3(Cfg::MW * 64), MP::LDS_BYTES, st,
-                           u1, 4 * T, w, u2);
-        M2_LAUNCHED("x3_mid_kernel");
+        mark(0, true);
+        void* hargs[] = {&mel, &T, &wv, &U1};
+        rc = launch_row(kRows.head[(int)p.head][p.comp][p.trans], p.head_g, st, hargs, "x3_head_kernel");
+        mark(0, false);
+        if (rc) return rc;
+        mark(1, true);
+        if (p.mid == VocMid::Midp) {  // stage1: the pipelined mid stage (vocoder_midp.hip)
+            rc = launch_vocoder_midp(U1, L1, p.mid_nch, p.mid_g, w.mp, w.mpb, U2, st, w.dT);
+        } else {
+            void* margs[] = {&U1, &L1, &wv, &U2};
+            rc = launch_row(kRows.mid[p.mid == VocMid::X3Alt ? 2 : p.stage == 2], p.mid_g, st, margs,
+                            "x3_mid_kernel");
+        }
+        if (rc) return rc;
+        mark(1, false);
     }
-    mark(1, false);
-    return tail();
+    mark(2, true);
+    if (p.tail == VocTail::Tailp2)  // stage2: the pipelined tail (vocoder_tailp2.hip)
+        rc = launch_vocoder_tailp2(U2, L2, p.tail_nl, p.tail_nch, p.tail_g, w.tp2, w.tp2b, audio, w.rflag, st, w.dT,
+                                   VocRedo{w.redo_w, mel, p.trans});
+    else if (p.tail == VocTail::Tailp)  // stage1: the pipelined tail (vocoder_tailp.hip)
+        rc = launch_vocoder_tailp(U2, L2, p.tail_nl, p.tail_nch, p.tail_g, w.tp, w.tpb, audio, w.rflag, st, w.dT,
+                                  VocRedo{w.redo_w, mel, p.trans});
+    else {
+        void* targs[] = {&U2, &L2, &wv, &audio};
+        rc = launch_row(kRows.tail[p.tail == VocTail::X3Alt ? 2 : p.stage == 2], p.tail_g, st, targs,
+                        "x3_tail_kernel");
+    }
+    mark(2, false);
+    return rc;
 }
 
 }  // namespace x3
@@ -1782,12 +1429,19 @@ bool vocoder_x3_supported(int M, int C) { return (M == 64 && C == 128) || (M == 
 
 int vocoder_x3_mel_pad(int M) { return M == 80 ? 96 : M; }
 
-int32_t launch_vocoder_x3(const float* mel, bool trans, int M, int C, int B, int T, const VocX& w, void* U1, void* U2,
+const VocSlots& vocoder_x3_slots() { return x3::setup().slots; }
+
+extern "C" int32_t m2_debug_vocoder_slots(int64_t* out8) {
+    if (!out8) return fail(M2_E_ARG, "m2_debug_vocoder_slots: null output");
+    const VocSlots& s = vocoder_x3_slots();
+    const long v[8] = {s.head16, s.head19, s.head24, s.head27, s.mid, s.mid_alt, s.tail, s.tail_alt};
+    for (int i = 0; i < 8; ++i) out8[i] = v[i];
+    return M2_OK;
+}
+
+int32_t launch_vocoder_x3(const float* mel, int T, const VocLaunchPlan& plan, const VocX& w, void* U1, void* U2,
                           float* audio, hipStream_t st, const std::function<void(int, bool)>& mark) {
-    if (B == 0 || T == 0) return M2_OK;
-    if (M == 64 && C == 128) return x3::run<x3::CfgS1>(mel, trans, B, T, w, U1, U2, audio, st, mark);
-    if (M == 80 && C == 256) return x3::run<x3::CfgS2>(mel, trans, B, T, w, U1, U2, audio, st, mark);
-    return fail(M2_E_SHAPE, "x3 vocoder: unsupported (mel_channels, vocoder_channels)");
+    return x3::run(mel, T, plan, w, U1, U2, audio, st, mark);
 }
 
 // ---------------------------------------------------------------------------

@@ -71,6 +71,9 @@ _SIGNATURES = {
     "m2_profile_kernel_count": (c_i32, []),
     "m2_profile_kernel_name": (ctypes.c_char_p, [c_i32]),
     "m2_profile_kernel_name_for": (ctypes.c_char_p, [c_vp, c_i32]),
+    "m2_debug_vocoder_plan": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, ctypes.c_char_p, c_size]),
+    "m2_debug_vocoder_slots": (c_i32, [ctypes.POINTER(c_i64)]),
+    "m2_debug_headmid_launches": (c_i64, []),
     "m2_profile_select": (c_i32, [c_vp, ctypes.c_uint32]),
     "m2_profile_stride": (c_i32, [c_vp, c_i32]),
     "m2_vocoder_path": (c_i32, [c_vp]),

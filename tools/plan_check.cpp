@@ -10,16 +10,23 @@
 // packers were merged into vocoder_pipe.h: the LCG weights are non-zero
 // everywhere, so a wrong slot, a lost duplicate zeroing or a changed summation
 // order in a packer changes a hash.
+// The vocoder's launch plan (csrc/vocoder_launch.h) runs here too: plan_vocoder_launch against
+// the decision rules the launchers carried before it (old_* below), over a sweep of calls, switch
+// tables and workgroup-slot counts, with the plans' invariants and three pinned lines.
 // The training losses' plans (csrc/losses_plan.h) run here too: the discriminator
 // calls' sizes and workspace layout against the formulas they replaced, and the
 // backward kernels' launch plans against their limits.
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
+#include <string>
 #include <utility>
 #include <vector>
 
 #include "losses_plan.h"
 #include "m2_model.h"
+#include "vocoder_launch.h"
 #include "vocoder_pipe.h"
 
 using namespace m2;
@@ -139,6 +146,310 @@ static void check_strips() {
     std::printf("pick_strip:");
     expect("same_as_old_loop", diff == 0, true);
     std::printf("\n");
+}
+
+// ---- the vocoder's launch plan (csrc/vocoder_launch.h) -------------------------------
+
+// The launch decisions as vocoder_run, x3::run<Cfg>, the three pipelined launchers and
+// launch_vocoder_fused / s1_fused carried them before plan_vocoder_launch (transcribed, sw() made
+// an argument; kept here only as the reference of the comparison below).
+static const char* old_headmid_excluded(const VocCall& w, const Switches& s, bool comp, bool s1) {
+    if (!s.headmid) return "M2_HEADMID=0";
+    if (!s1) return "not the stage1 shapes";
+    if (w.device_T) return "the frame count is on the device: the grid covers the capacity";
+    if (!w.mp || !w.hc || !comp) return "no split packs of the composed head and the pipelined mid (or M2_HEAD_INCONV)";
+    if (s.midp_nch > 0) return "M2_MIDP_NCH forces the mid's strip length";
+    if (w.prof_slots & 3u) return "events around the head or the mid: the fused launch has no boundary between them";
+    return nullptr;
+}
+static long old_rounds_of(long n, long slots) { return (n + slots - 1) / slots; }
+
+struct OldSplit {
+    const char* why = nullptr;  // headmid_excluded
+    int n = 0, S = 0, nch = 0;  // headmid
+    int head_tf = 0, head_waves = 0;
+    bool comp = false, alt_mid = false, alt_tail = false;
+    int midp_nch = 0;                  // 0: not the pipelined mid
+    int tail_nl = 0, tail_nch = 0;     // 0: not a pipelined tail
+    int redo = 0;                      // 0 none, 1 in the tail, 2 guarded launch, 3 host fallback
+};
+
+static OldSplit old_split(const VocCall& w, const Switches& s, const VocSlots& sl) {
+    OldSplit o;
+    const bool S1 = w.M == 64, S2 = w.M == 80;
+    const int B = w.B, T = w.T;
+    // vocoder_run / vocoder_entry: the three redo forms
+    if (w.redo >= 0) o.redo = w.redo_w && !s.redo_launch ? 1 : 2;
+    else if (w.range_policy == 1) o.redo = 3;
+    // x3::run<Cfg>
+    if (S2) {
+        if (!w.mp && s.s2_mid_alt >= 0)
+            o.alt_mid = s.s2_mid_alt == 1;
+        else if (!w.mp)
+            o.alt_mid = old_rounds_of((long)cdiv(4 * T, 33) * B, sl.mid_alt) * 1.20 <
+                        (double)old_rounds_of((long)cdiv(4 * T, 30) * B, sl.mid);
+        if (!w.tp && !w.tp2)
+            o.alt_tail = old_rounds_of((long)cdiv(16 * T, 125) * B, sl.tail_alt) * 1.075 <
+                         (double)old_rounds_of((long)cdiv(16 * T, 120) * B, sl.tail);
+    }
+    // the tail lambda: launch_vocoder_tailp2 / launch_vocoder_tailp
+    if (w.tp2) {
+        const bool seven = s.tailp2_seven;
+        o.tail_nl = seven ? 7 : 6;
+        int nch = s.tailp2_nch > 0 ? std::min(s.tailp2_nch, 4096) : 0;
+        if (!nch) nch = old_strip(16 * T, B, 8, 256, o.tail_nl);
+        o.tail_nch = nch;
+    } else if (w.tp) {
+        o.tail_nl = s.tailp_seven ? 7 : 6;
+        int nch = s.tailp_nch > 0 ? std::min(s.tailp_nch, 4096) : 0;
+        if (!nch) nch = old_strip(16 * T, B, 8, 768, o.tail_nl + 1);
+        o.tail_nch = nch;
+    }
+    o.comp = w.hc && !s.head_inconv;
+    if (S1) {
+        o.why = old_headmid_excluded(w, s, o.comp, S1);
+        if (!o.why) {
+            o.n = cdiv(4 * T, 4 * 63 - 2), o.S = cdiv(4 * T, o.n), o.nch = cdiv(o.S, 16);
+            return o;
+        }
+    } else {
+        o.why = old_headmid_excluded(w, s, o.comp, S1);
+    }
+    int hv = 16;
+    if (S2) {
+        auto rounds = [&](int tf, long slots) { return old_rounds_of((long)cdiv(T, tf) * B, slots); };
+        if (s.s2_head_tf)
+            hv = s.s2_head_tf;
+        else if ((long)cdiv(T, 16) * B >= 1024)
+            hv = rounds(27, sl.head27) < rounds(24, sl.head24) ? 27 : 24;
+        else
+            hv = rounds(19, sl.head19) < rounds(16, sl.head16) ? 19 : 16;
+    }
+    if (S2 && o.comp && hv != 16) {
+        if (hv == 19) o.head_tf = 19, o.head_waves = 8;
+        else if (hv == 24) o.head_tf = 24, o.head_waves = 16;
+        else o.head_tf = 27, o.head_waves = 16;
+    } else {
+        o.head_tf = S1 ? 63 : 16, o.head_waves = S1 ? 16 : 8;
+    }
+    if (w.mp) {  // launch_vocoder_midp
+        int nch = s.midp_nch > 0 ? std::min(s.midp_nch, 4096) : 0;
+        if (!nch) nch = old_strip(4 * T, B, 4, 256, 4);
+        o.midp_nch = nch;
+    }
+    return o;
+}
+
+struct OldF32 {
+    const char *head, *mid, *tail;
+    bool pair, comp;
+};
+static OldF32 old_f32(const VocCall& c, const Switches& s) {
+    const int plan = s.voc_plan, B = c.B, T = c.T;
+    if (c.M == 64 && c.C == 128) {
+        const int n16 = B * cdiv(T, 63), n8 = B * cdiv(T, 28);
+        const double waste16 = (double)cdiv(n16, 256) * 256 / n16, waste8 = (double)cdiv(n8, 512) * 512 / n8;
+        const bool w16 = plan == 2 || (plan < 0 && waste16 <= waste8);
+        const bool pair = s.f32_pair && c.wt4p, comp = s.f32_comp && c.hcw;
+        // s1_fused
+        if (plan == 3) return {"S1W16s", "S1W16s", "S1W16s", pair, comp};
+        if (w16) {
+            switch (s.f32_mt) {
+                case 1: return {"S1W16", "S1T8", "S1W16", pair, comp};
+                case 2: return {"S1W16", "S1W16", "S1T8", pair, comp};
+                case 3: return {"S1W16", "S1T8", "S1T8", pair, comp};
+                case 4: return {"S1W16", "S1W16s", "S1T8", pair, comp};
+                default: return {"S1W16", "S1W16", "S1W16", pair, comp};
+            }
+        }
+        return {"S1W8", "S1W8", "S1W8", pair, comp};
+    }
+    if (c.M == 80 && c.C == 256) return {"S2W8", "S2W8", "S2W8", false, s.f32_comp && c.hcw};
+    return {"TinyW8", "TinyW8", "TinyW8", false, false};
+}
+
+// grid.x windows of `width` cover [0, L) exactly once: the last one starts inside, none starts past the end
+static bool covers(int gx, long width, long L) { return gx >= 1 && (gx - 1) * width < L && gx * width >= L; }
+
+static VocCall voc_call_of(int stage, int B, int T) {
+    VocCall c;
+    c.M = stage == 1 ? 64 : 80, c.C = stage == 1 ? 128 : 256;
+    c.B = B, c.T = T;
+    c.hc = true, c.mp = stage == 1, c.tp = stage == 1, c.tp2 = stage == 2, c.redo_w = true;
+    c.wt4p = stage == 1, c.hcw = true;
+    c.fused = c.x3 = true;
+    return c;
+}
+
+static const VocSlots kSlotsDefault{256, 256, 256, 256, 512, 512, 256, 256};  // MI355X, as the tilings' notes have it
+
+static int g_plans = 0, g_plan_diff = 0, g_plan_inv = 0;
+
+// One call: the plan against the old rules, and the plan's invariants.
+static void check_plan(const VocCall& c, const Switches& s, const VocSlots& sl) {
+    const VocLaunchPlan p = plan_vocoder_launch(c, s, sl);
+    ++g_plans;
+    const int B = c.B, T = c.T;
+    bool same = true, inv = true;
+    auto grid_ok = [&](const VocGrid& g) { return g.x >= 1 && g.y == B && g.threads >= 64 && g.lds >= 0 && g.lds <= 160 * 1024; };
+    if (!c.x3) {
+        const OldF32 o = old_f32(c, s);
+        const f32::FormRow& f = f32::kF32Forms[p.form];
+        const f32::Tiling &h = f32::kTiling[f.head], &m = f32::kTiling[f.mid], &t = f32::kTiling[f.tail];
+        same = p.path == VocPath::F32 && !std::strcmp(h.name, o.head) && !std::strcmp(m.name, o.mid) &&
+               !std::strcmp(t.name, o.tail) && p.pair == o.pair && p.f32_comp == o.comp && p.trans == c.trans &&
+               p.redo == VocRedoPlan::None;
+        inv = grid_ok(p.head_g) && grid_ok(p.mid_g) && grid_ok(p.tail_g) && covers(p.head_g.x, h.tf, T) &&
+              covers(p.mid_g.x, m.w2, 4L * T) && covers(p.tail_g.x, t.w3, 16L * T) && p.head_g.threads == h.threads &&
+              p.mid_g.threads == m.threads && p.tail_g.threads == t.threads;
+    } else {
+        const OldSplit o = old_split(c, s, sl);
+        same = p.path == VocPath::Split && p.trans == c.trans && p.headmid == (o.n > 0) &&
+               (p.no_headmid == nullptr) == (o.why == nullptr) &&
+               (!o.why || !std::strcmp(p.no_headmid, o.why)) && p.comp == o.comp &&
+               (int)p.redo == o.redo;
+        if (p.headmid) {
+            same = same && p.hm_n == o.n && p.hm_S == o.S && p.hm_nch == o.nch && p.head_g.x == o.n;
+            inv = inv && grid_ok(p.head_g) && p.hm_S <= x3::kHeadmidSMax && p.hm_S >= 1 && covers(p.hm_n, p.hm_S, 4L * T) &&
+                  16 * p.hm_nch >= p.hm_S && p.mid_g.threads == 0;
+        } else {
+            same = same && p.head_tf == o.head_tf && p.head_g.threads == o.head_waves * 64 &&
+                   (p.mid == VocMid::Midp) == (o.midp_nch > 0) && p.mid_nch == o.midp_nch &&
+                   (p.mid == VocMid::X3Alt) == o.alt_mid;
+            inv = inv && grid_ok(p.head_g) && grid_ok(p.mid_g) && covers(p.head_g.x, p.head_tf, T) &&
+                  covers(p.mid_g.x, p.mid == VocMid::Midp ? 16L * p.mid_nch : p.mid_w, 4L * T);
+        }
+        const bool tailp = p.tail == VocTail::Tailp || p.tail == VocTail::Tailp2;
+        same = same && tailp == (o.tail_nl > 0) && p.tail_nl == o.tail_nl && p.tail_nch == o.tail_nch &&
+               (p.tail == VocTail::Tailp2) == (c.tp2 && o.tail_nl > 0) && (p.tail == VocTail::X3Alt) == o.alt_tail;
+        inv = inv && grid_ok(p.tail_g) && covers(p.tail_g.x, tailp ? 16L * p.tail_nch : p.tail_w, 16L * T);
+        // exactly one redo strategy, and only the guarded one has a launch of its own
+        const int strategies = (p.redo == VocRedoPlan::None) + (p.redo == VocRedoPlan::InTail) +
+                               (p.redo == VocRedoPlan::Guarded) + (p.redo == VocRedoPlan::Host);
+        inv = inv && strategies == 1 && (p.redo == VocRedoPlan::Guarded) == (p.redo_g.threads > 0) &&
+              p.redo_g.lds <= 160 * 1024 && (p.redo != VocRedoPlan::InTail || tailp) &&
+              ((c.range_policy == 1) == (p.redo != VocRedoPlan::None));
+        if (p.redo == VocRedoPlan::Guarded) {
+            const OldF32 of = old_f32(c, s);
+            // RedoCfg: the 8-wave form of the stage
+            const char* want = c.M == 64 ? "S1W8" : (c.M == 80 ? "S2W8" : "TinyW8");
+            same = same && !std::strcmp(f32::kTiling[f32::kF32Forms[p.form].redo].name, want) && p.pair == of.pair &&
+                   p.f32_comp == of.comp;
+        }
+    }
+    char line[512];
+    const int len = p.print(line, sizeof line);
+    inv = inv && len > 0 && len < (int)sizeof line && (int)std::strlen(line) == len;
+    if ((!same || !inv) && g_plan_diff + g_plan_inv < 5)
+        std::printf("  stage %d B %d T %d: %s%s| %s\n", c.M == 64 ? 1 : 2, B, T, same ? "" : "DIFFERS ", inv ? "" : "INVARIANT ", line);
+    g_plan_diff += !same;
+    g_plan_inv += !inv;
+}
+
+static void expect_line(const char* what, const VocCall& c, const char* want) {
+    char line[512];
+    plan_vocoder_launch(c, Switches{}, kSlotsDefault).print(line, sizeof line);
+    const bool ok = !std::strcmp(line, want);
+    std::printf("  %s: %s%s\n", what, line, ok ? "" : " (UNEXPECTED)");
+    g_bad += !ok;
+}
+
+static void check_launch_plans() {
+    // the switch tables: the default, then each vocoder switch alone at each legal value and an illegal one
+    std::vector<Switches> sws(1);
+    auto with = [&](auto set) {
+        Switches s;
+        set(s);
+        sws.push_back(s);
+    };
+    with([](Switches& s) { s.headmid = false; });
+    for (const int v : {1, 5, 16, 4096, 5000, -3}) with([v](Switches& s) { s.midp_nch = v; });
+    for (const int v : {8, 9, 21, 4096, 5000, -3}) with([v](Switches& s) { s.tailp_nch = v; });
+    for (const int v : {8, 9, 4096, 5000, -3}) with([v](Switches& s) { s.tailp2_nch = v; });
+    with([](Switches& s) { s.tailp_seven = true; });
+    with([](Switches& s) { s.tailp2_seven = true; });
+    with([](Switches& s) { s.head_inconv = true; });
+    for (const int v : {0, 1, 2}) with([v](Switches& s) { s.s2_mid_alt = v; });
+    for (const int v : {16, 19, 24, 27, 20}) with([v](Switches& s) { s.s2_head_tf = v; });
+    for (const int v : {0, 2, 3, 7}) with([v](Switches& s) { s.voc_plan = v; });
+    for (const int v : {0, 1, 2, 3, 4, 7}) with([v](Switches& s) { s.f32_mt = v; });
+    with([](Switches& s) { s.f32_pair = false; });
+    with([](Switches& s) { s.f32_comp = false; });
+    with([](Switches& s) { s.redo_launch = true; });
+    // the slot counts: the default, each count alone at 256 / 512 / 768, all of them at each, and 304 CUs
+    std::vector<VocSlots> slots(1, kSlotsDefault);
+    for (const long v : {256L, 512L, 768L}) {
+        for (int f = 0; f < 8; ++f) {
+            VocSlots sl = kSlotsDefault;
+            (&sl.head16)[f] = v;
+            slots.push_back(sl);
+        }
+        slots.push_back({v, v, v, v, v, v, v, v});
+    }
+    slots.push_back({304, 304, 304, 304, 608, 608, 304, 304});
+    std::vector<int> Ts;
+    for (int t = 1; t <= 300; ++t) Ts.push_back(t);
+    Ts.push_back(500), Ts.push_back(2600);
+    // the handles: every pack, the x3 mid / tail kept (M2_VOC_MID_X3 / M2_VOC_TAIL_X3), no composed head,
+    // the exact-f32 path with and without its stage1 packs; the range policies
+    struct Handle {
+        bool mp, tail, hc, x3, f32_packs;
+    };
+    const Handle handles[] = {{true, true, true, true, true},   {false, true, true, true, true},
+                              {true, false, true, true, true},  {false, false, true, true, true},
+                              {true, true, false, true, true},  {true, true, true, false, true},
+                              {true, true, true, false, false}};
+    struct Policy {
+        int policy, redo;
+    };
+    const Policy policies[] = {{0, -1}, {1, -1}, {1, 0}, {1, 1}};
+    for (int stage = 1; stage <= 2; ++stage)
+        for (const int B : {1, 2, 3, 8, 16, 32, 64, 128})
+            for (const int T : Ts) {
+                const VocCall base = voc_call_of(stage, B, T);
+                // calls x (switch tables with the default slots, slot counts with the default switches)
+                for (int layout = 0; layout < 2; ++layout)
+                    for (int dev = 0; dev < 2; ++dev)
+                        for (const unsigned prof : {0u, 1u, 2u, 4u}) {
+                            VocCall c = base;
+                            c.trans = layout, c.device_T = dev, c.prof_slots = prof;
+                            for (const Switches& s : sws) check_plan(c, s, kSlotsDefault);
+                            for (size_t i = 1; i < slots.size(); ++i) check_plan(c, sws[0], slots[i]);
+                        }
+                // handles x policies x switch tables
+                for (const Handle& h : handles)
+                    for (const Policy& pol : policies) {
+                        VocCall c = base;
+                        c.mp = c.mp && h.mp, c.tp = c.tp && h.tail, c.tp2 = c.tp2 && h.tail, c.hc = h.hc;
+                        c.redo_w = c.tp || c.tp2;
+                        c.x3 = h.x3, c.wt4p = c.wt4p && h.f32_packs, c.hcw = h.f32_packs;
+                        c.range_policy = pol.policy, c.redo = h.x3 ? pol.redo : -1;
+                        for (const Switches& s : sws) check_plan(c, s, kSlotsDefault);
+                        check_plan(c, sws[0], slots.back());
+                    }
+            }
+    {  // the tiny shape (exact-f32 only) and a handle without the fused kernels
+        VocCall c = voc_call_of(1, 2, 40);
+        c.M = 32, c.C = 64, c.x3 = c.hc = c.mp = c.tp = c.redo_w = c.wt4p = c.hcw = false;
+        check_plan(c, sws[0], kSlotsDefault);
+        c.fused = false;
+        char line[64];
+        plan_vocoder_launch(c, sws[0], kSlotsDefault).print(line, sizeof line);
+        g_plan_diff += std::strcmp(line, "perlayer") != 0;
+    }
+    std::printf("launch plans: %d plans over %zu switch tables and %zu slot sets, %d differ from the old rules, %d break "
+                "an invariant\n",
+                g_plans, sws.size(), slots.size(), g_plan_diff, g_plan_inv);
+    g_bad += g_plan_diff + g_plan_inv;
+    // the headline and the two stage2 bench lines, literally ([B, M, T] mel, host T, default switches)
+    expect_line("stage1 B=32 T=500", voc_call_of(1, 32, 500), "split stage=1 headmid[n=8 S=250 nch=16 trans=0 grid=8x32 thr=1024 lds=148608] "
+                "tailp[nl=6 nch=21 grid=24x32 thr=448 lds=49184] redo=none");
+    expect_line("stage2 B=8 T=500", voc_call_of(2, 8, 500), "split stage=2 head[tf=16 comp=1 trans=0 grid=32x8 thr=512 lds=81600] "
+                "x3mid[alt=1 w=33 grid=61x8 thr=512 lds=81216] tailp2[nl=6 nch=16 grid=32x8 thr=768 lds=98352] redo=none "
+                "no-headmid=\"not the stage1 shapes\"");
+    expect_line("stage2 B=16 T=2600", voc_call_of(2, 16, 2600), "split stage=2 head[tf=24 comp=1 trans=0 grid=109x16 thr=1024 lds=116416] "
+                "x3mid[alt=0 w=30 grid=347x16 thr=512 lds=73152] tailp2[nl=6 nch=163 grid=16x16 thr=768 lds=98352] "
+                "redo=none no-headmid=\"not the stage1 shapes\"");
 }
 
 // ---- the training losses' plans (csrc/losses_plan.h) ---------------------------------
@@ -362,6 +673,7 @@ static void check_geometries() {
 
 int main() {
     check_strips();
+    check_launch_plans();
     check_disc_plans();
     check_geometries();
     const m2_config stage1{256, 64, 64, 2, 2, 2, 128, 1000}, stage2{256, 96, 80, 3, 3, 2, 256, 1000};
