@@ -499,9 +499,11 @@ int32_t m2_eval_mcd(const float* pred, const float* target, const int32_t* cols,
                     int32_t n_mels, int32_t Tp, int32_t Tt, int32_t pred_transposed, double* out, void* stream);
 
 /* ---- training losses (src/training/losses.py) ------------------------------
- * Forward values, and the backward of the discriminator step (the gradient
- * of the adversarial discriminator loss with respect to the discriminators'
- * parameters; nothing else has a gradient).  Per-utterance rows of double sums as above, columns named by
+ * Forward values, the backward of the discriminator step (the gradient of
+ * the adversarial discriminator loss with respect to the discriminators'
+ * parameters), and the generator step's gradients with respect to the audio:
+ * through the discriminators, and of the spectral and perceptual sums.
+ * Per-utterance rows of double sums as above, columns named by
  * m2_loss_column_count(kind) / m2_loss_column_name(kind, i): kind 0 =
  * m2_loss_spectral, 1 = m2_disc_losses.  Fixed-order reductions: equal inputs
  * give equal bits, and a batched row equals the row of the utterance alone.
@@ -602,7 +604,26 @@ int32_t m2_eval_mcd(const float* pred, const float* target, const int32_t* cols,
  * respect to x [B,1,L], given dy [B,Cout,L/pool + 2 padding - k + 1]; dx
  * [B,1,L] is overwritten (the dropped tail samples with 0) or, with
  * `accumulate`, added to (the tail left alone).  Cout k floats of weights and
- * a 16-channel window of 256 + k - 1 samples must fit 48 KiB of LDS. */
+ * a 16-channel window of 256 + k - 1 samples must fit 48 KiB of LDS.
+ *
+ * m2_loss_spectral_backward: d_pred [B,L], the gradient with respect to pred of
+ *   c_mag mag_abs + c_phase phase_abs + c_perc mel_log_abs
+ * summed over the batch (m2_loss_spectral's columns at the handle's n_fft and
+ * hop; host coefficients, so a mean is 1 / count), overwritten or, with
+ * `accumulate`, added to as one fp32 addition per sample.  Same arguments,
+ * limits and framing as m2_loss_spectral, and the same spectra bit for bit.
+ * Per bin the cotangent g = d/dRe P + i d/dIm P is formed in double and rounded
+ * once: (c_mag sign(|P| - |T|) + kappa_t) P/|P| + c_phase sign(angle P -
+ * angle T) (-Im P + i Re P)/|P|^2, kappa_t = c_perc sum_j sign(ln(w_j S_P +
+ * 1e-8) - ln(w_j S_T + 1e-8)) w_j / (w_j S_P + 1e-8), S_X = sum_f |X_f|;
+ * sign(0) = 0, and g = 0 where |P| = 0 (torch's abs and angle backward).  The
+ * derivative is taken on the kernel's own fp32 spectrum.  A frame's cotangent
+ * is win[n] Re sum_{f <= n_fft/2} g_f e^(+2 pi i f n / n_fft), held in the
+ * workspace ([B, frames, n_fft] floats); each sample then gathers padded
+ * positions i, -i and 2 (L - 1) - i (the adjoint of reflect padding), frames
+ * ascending, in fp32.  No floating-point atomics: equal inputs give equal bits
+ * and a batched row equals the row of the utterance alone.  cot_pred (or
+ * NULL): g as complex64 [B, frames, n_fft/2+1].  target gets no gradient. */
 typedef struct m2_disc m2_disc;
 int32_t m2_loss_column_count(int32_t kind);
 const char* m2_loss_column_name(int32_t kind, int32_t index);
@@ -644,6 +665,11 @@ size_t m2_loss_spectral_workspace_bytes(const m2_dsp* dsp, int32_t B, int32_t L)
 int32_t m2_loss_spectral(const m2_dsp* dsp, const float* pred, const float* target, int32_t B, int32_t L,
                          const float* mel_weights, int32_t n_weights, double* out, void* spec_pred, void* spec_target,
                          void* workspace, size_t workspace_bytes, void* stream);
+size_t m2_loss_spectral_backward_workspace_bytes(const m2_dsp* dsp, int32_t B, int32_t L);
+int32_t m2_loss_spectral_backward(const m2_dsp* dsp, const float* pred, const float* target, int32_t B, int32_t L,
+                                  const float* mel_weights, int32_t n_weights, double c_mag, double c_phase,
+                                  double c_perc, int32_t accumulate, float* d_pred, void* cot_pred, void* workspace,
+                                  size_t workspace_bytes, void* stream);
 
 /* ---- measurement ----------------------------------------------------------
  * Kernel timing with HIP events recorded on the launch stream around each of

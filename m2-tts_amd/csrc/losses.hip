@@ -1,8 +1,9 @@
 // Training losses on the GPU: the sums behind the reference's
 // src/training/losses.py (SpectralLoss, PerceptualLoss, MultiScaleDiscriminator,
-// AdversarialLoss), batched over utterances, and two gradients: the
+// AdversarialLoss), batched over utterances, and three gradients: the
 // discriminator loss with respect to the discriminators' parameters, and the
-// generator's adversarial and feature-matching terms with respect to the audio.
+// generator's adversarial and feature-matching terms and its spectral and
+// perceptual terms with respect to the audio.
 //
 //   conv      Conv1d(k, stride, zero padding, groups) + bias, with a leaky
 //             slope on the input (the discriminators' feature maps are the
@@ -39,6 +40,10 @@
 //             padding), pred and target through one complex FFT as in
 //             eval_metrics.hip; magnitudes and angles in double from the fp32
 //             spectrum; DC and Nyquist imaginary parts are +0.
+//             m2_loss_spectral_backward: spectral_grad_frame_kernel forms the
+//             same spectrum, the cotangent of pred's bins in double and its
+//             inverse FFT times the window per frame; spectral_fold_kernel
+//             gathers the frames and the reflections into each sample.
 // Every reduction is a lane-strided sum, an xor-shuffle tree and the wave
 // partials in order: no floating-point atomics, equal inputs give equal bits,
 // and a batched row equals the row of the utterance run alone.
@@ -673,6 +678,112 @@ __global__ __launch_bounds__(NT) void spectral_finish_kernel(const double* __res
     }
 }
 
+__device__ __forceinline__ double sign_of(double v) { return v > 0.0 ? 1.0 : v < 0.0 ? -1.0 : 0.0; }
+
+// grid (frames, B): the cotangent of frame t of pred under
+//   c_mag sum | |P| - |T| | + c_ph sum |angle P - angle T| + c_perc sum_j |ln(w_j S_P + 1e-8) - ln(w_j S_T + 1e-8)|,
+// the sums spectral_frame_kernel takes, from the same loader and FFT (so the
+// spectra, S_P and S_T are that kernel's bit for bit).  g = d/dRe P + i d/dIm P
+// per bin, in double, rounded once: (c_mag sign(|P| - |T|) + kappa) P / |P| +
+// c_ph sign(angle P - angle T) (-Im P + i Re P) / |P|^2, kappa = c_perc sum_j
+// sign(ln .. - ln ..) w_j / (w_j S_P + 1e-8); sign(0) = 0 and g = 0 where
+// |P| = 0.  g goes into the buffer the spectrum is not in, zero above N/2, and
+// through the unnormalised inverse FFT: fr [B, frames, N] receives
+// win[n] Re sum_f g_f e^(+2 pi i f n / N), the frame's cotangent.  cot (or
+// null) receives g [B, frames, N/2 + 1].
+template <int N>
+__global__ __launch_bounds__(NT) void spectral_grad_frame_kernel(const float* __restrict__ pred,
+                                                                 const float* __restrict__ target, int L, int hop,
+                                                                 const float* __restrict__ win,
+                                                                 const float2* __restrict__ tw,
+                                                                 const float* __restrict__ mel_w, int n_w, double c_mag,
+                                                                 double c_ph, double c_perc, float* __restrict__ fr,
+                                                                 float2* __restrict__ cot) {
+    __shared__ float2 a[N], b[N];
+    __shared__ double red[NT / 64];
+    constexpr int F = N / 2 + 1;
+    const int t = blockIdx.x, u = blockIdx.y, frames = gridDim.x;
+    dsp::load_pair_frame<N, true>(pred + (size_t)u * L, target + (size_t)u * L, L, hop, t, win, a);
+    const size_t row = (size_t)u * frames + t;
+    // The same windowed samples on both sides: P = T and every sign is 0.  The paired FFT rounds its
+    // real and imaginary halves differently, so its two spectra would differ there by rounding residue.
+    int differs = 0;
+    for (int n = threadIdx.x; n < N; n += NT) differs |= a[n].x != a[n].y;
+    if (!__syncthreads_or(differs)) {
+        for (int n = threadIdx.x; n < N; n += NT) fr[row * N + n] = 0.f;
+        if (cot)
+            for (int f = threadIdx.x; f < F; f += NT) cot[row * F + f] = make_float2(0.f, 0.f);
+        return;
+    }
+    float2* Z = dsp::fft_lds<N, false>(a, b, tw);
+    float2* G = Z == a ? b : a;
+    double sP = 0.0, sT = 0.0;
+    for (int f = threadIdx.x; f < F; f += NT) {
+        const float2 zf = Z[f], zn = Z[(N - f) & (N - 1)];
+        const bool real_bin = f == 0 || f == N / 2;
+        const float pr = 0.5f * (zf.x + zn.x), pi = real_bin ? 0.f : 0.5f * (zf.y - zn.y);
+        const float tr = 0.5f * (zf.y + zn.y), ti = real_bin ? 0.f : 0.5f * (zn.x - zf.x);
+        sP += sqrt((double)pr * pr + (double)pi * pi);
+        sT += sqrt((double)tr * tr + (double)ti * ti);
+    }
+    sP = block_sum(sP, red);
+    sT = block_sum(sT, red);
+    double kappa = 0.0;
+    if (c_perc != 0.0) {  // the same for every thread of the workgroup
+        for (int j = threadIdx.x; j < n_w; j += NT) {
+            const double wj = (double)mel_w[j];
+            kappa += sign_of(log(wj * sP + 1e-8) - log(wj * sT + 1e-8)) * wj / (wj * sP + 1e-8);
+        }
+        kappa = c_perc * block_sum(kappa, red);
+    }
+    for (int f = threadIdx.x; f < N; f += NT) {
+        float2 g = make_float2(0.f, 0.f);
+        if (f < F) {
+            const float2 zf = Z[f], zn = Z[(N - f) & (N - 1)];
+            const bool real_bin = f == 0 || f == N / 2;
+            const float pr = 0.5f * (zf.x + zn.x), pi = real_bin ? 0.f : 0.5f * (zf.y - zn.y);
+            const float tr = 0.5f * (zf.y + zn.y), ti = real_bin ? 0.f : 0.5f * (zn.x - zf.x);
+            const double mp = sqrt((double)pr * pr + (double)pi * pi), mt = sqrt((double)tr * tr + (double)ti * ti);
+            if (mp > 0.0) {
+                const double radial = (c_mag * sign_of(mp - mt) + kappa) / mp;
+                const double turn =
+                    c_ph * sign_of(atan2((double)pi, (double)pr) - atan2((double)ti, (double)tr)) / (mp * mp);
+                g = make_float2((float)(radial * pr - turn * pi), (float)(radial * pi + turn * pr));
+            }
+            if (cot) cot[row * F + f] = g;
+        }
+        G[f] = g;
+    }
+    __syncthreads();
+    const float2* Y = dsp::fft_lds<N, true>(G, Z, tw);
+    float* o = fr + row * N;
+    for (int n = threadIdx.x; n < N; n += NT) o[n] = win[n] * Y[n].x;
+}
+
+// The adjoint of torch.stft's framing (centre, reflect padding): d_pred [B, L]
+// from the frames' cotangents fr [B, frames, N].  grid (cdiv(L, 256), B), one
+// thread per sample i.  Padded position p is sample n = p + N/2 - t hop of the
+// frames t with 0 <= n < N; sample i gathers positions i, then -i
+// (1 <= i <= N/2), then 2 (L - 1) - i (L - 1 - N/2 <= i <= L - 2), the frames
+// of each ascending, into one fp32 sum, stored or, with `accumulate`, added to
+// what is there as one fp32 addition.  Any hop >= 1.
+__global__ __launch_bounds__(256) void spectral_fold_kernel(const float* __restrict__ fr, int N, int hop, int frames,
+                                                            int L, int accumulate, float* __restrict__ d_pred) {
+    const int i = blockIdx.x * 256 + threadIdx.x, u = blockIdx.y;
+    if (i >= L) return;
+    const float* fu = fr + (size_t)u * frames * N;
+    float s = 0.f;
+    for (int k = 0; k < 3; ++k) {
+        if (k == 1 && !(i >= 1 && i <= N / 2)) continue;
+        if (k == 2 && !(i >= L - 1 - N / 2 && i <= L - 2)) continue;
+        const int q = (k == 0 ? i : k == 1 ? -i : 2 * (L - 1) - i) + N / 2;  // in [0, L + N)
+        const int t0 = q < N ? 0 : (q - N) / hop + 1, t1 = min(frames - 1, q / hop);
+        for (int t = t0; t <= t1; ++t) s += fu[(size_t)t * N + (q - t * hop)];
+    }
+    float* o = d_pred + (size_t)u * L + i;
+    *o = accumulate ? *o + s : s;
+}
+
 }  // namespace loss
 }  // namespace m2
 
@@ -1263,6 +1374,44 @@ int32_t m2_loss_spectral(const m2_dsp* d, const float* pred, const float* target
     hipLaunchKernelGGL(loss::spectral_finish_kernel, dim3(B), dim3(dsp::NT), 0, st, part, frames, d->n_fft / 2 + 1,
                        out);
     M2_LAUNCHED("spectral_finish_kernel");
+    return M2_OK;
+}
+
+size_t m2_loss_spectral_backward_workspace_bytes(const m2_dsp* d, int32_t B, int32_t L) {
+    if (!d || B < 0 || L < 0) return 0;
+    Sizer s;
+    loss::carve_spectral_bwd(s, d->n_fft, d->hop, B, L, nullptr);
+    return s.off + 256;
+}
+
+int32_t m2_loss_spectral_backward(const m2_dsp* d, const float* pred, const float* target, int32_t B, int32_t L,
+                                  const float* mel_weights, int32_t n_weights, double c_mag, double c_phase,
+                                  double c_perc, int32_t accumulate, float* d_pred, void* cot_pred, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+    M2_CHECK_ARG(d && pred && target && d_pred && B >= 0 && L > 0 && n_weights >= 0 && (mel_weights || n_weights == 0),
+                 "m2_loss_spectral_backward: bad argument");
+    M2_CHECK_SHAPE(L > d->n_fft / 2, "m2_loss_spectral_backward: reflect padding needs more than n_fft / 2 samples");
+    M2_CHECK_SHAPE(B <= loss::kMaxGrid && L <= (1 << 30),
+                   "m2_loss_spectral_backward: at most 65535 utterances of 2^30 samples");
+    if (B == 0) return M2_OK;
+    const int frames = loss::spectral_frames(L, d->hop);
+    Carve c(workspace, workspace_bytes);
+    float* fr;
+    loss::carve_spectral_bwd(c, d->n_fft, d->hop, B, L, &fr);
+    if (!c.ok) return fail(M2_E_WORKSPACE, "m2_loss_spectral_backward: workspace too small");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+#define M2_SPEC_GRAD(NN)                                                                                             \
+    hipLaunchKernelGGL((loss::spectral_grad_frame_kernel<NN>), dim3(frames, B), dim3(dsp::NT), 0, st, pred, target, \
+                       L, d->hop, d->win, d->tw, mel_weights, n_weights, c_mag, c_phase, c_perc, fr,                 \
+                       static_cast<float2*>(cot_pred))
+    if (d->n_fft == 512) M2_SPEC_GRAD(512);
+    else if (d->n_fft == 1024) M2_SPEC_GRAD(1024);
+    else M2_SPEC_GRAD(2048);
+#undef M2_SPEC_GRAD
+    M2_LAUNCHED("spectral_grad_frame_kernel");
+    hipLaunchKernelGGL(loss::spectral_fold_kernel, dim3(cdiv(L, 256), B), dim3(256), 0, st, fr, d->n_fft, d->hop, frames,
+                       L, accumulate ? 1 : 0, d_pred);
+    M2_LAUNCHED("spectral_fold_kernel");
     return M2_OK;
 }
 

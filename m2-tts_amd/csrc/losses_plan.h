@@ -1,6 +1,6 @@
 // The host-only half of losses.hip: the geometry of the discriminators' convs,
 // the plans that decide LDS sizes, grids and split counts, and the workspace
-// layout of the discriminator calls.  Pure arithmetic on the host: nothing
+// layout of the discriminator calls and of the spectral backward.  Pure arithmetic on the host: nothing
 // here touches a device, so tools/plan_check.cpp runs all of it on the CPU.
 #pragma once
 
@@ -202,6 +202,15 @@ void carve_disc(A& a, const DiscPlan& p, DiscBufs* out) {
     b.pooled = floats(nbs * p.pooled);
     b.part = floats(p.part);
     if (out) *out = b;
+}
+
+// m2_loss_spectral_backward's workspace: the frames' cotangents [B, frames, n_fft] between
+// spectral_grad_frame_kernel and spectral_fold_kernel (n_fft / hop floats per sample).
+inline int spectral_frames(int L, int hop) { return 1 + L / hop; }
+template <typename A>
+void carve_spectral_bwd(A& a, int n_fft, int hop, int B, int L, float** frames) {
+    float* p = a.template take<float>((size_t)B * spectral_frames(L, hop) * n_fft);
+    if (frames) *frames = p;
 }
 
 }  // namespace loss

@@ -122,6 +122,9 @@ _SIGNATURES = {
     "m2_conv1d_audio_backward": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "m2_loss_spectral_workspace_bytes": (c_size, [c_vp, c_i32, c_i32]),
     "m2_loss_spectral": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_size, c_vp]),
+    "m2_loss_spectral_backward_workspace_bytes": (c_size, [c_vp, c_i32, c_i32]),
+    "m2_loss_spectral_backward": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_f64, c_f64, c_f64, c_i32, c_vp,
+                                          c_vp, c_vp, c_size, c_vp]),
     "m2_front_bytes": (c_size, [c_vp, c_i32, c_i32]),
     "m2_inference_workspace_bytes": (c_size, [c_vp, c_i32, c_i32, c_i32]),
     "m2_inference_front": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_vp, c_size, c_vp, c_size, c_vp, c_vp]),

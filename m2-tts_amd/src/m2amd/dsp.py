@@ -236,6 +236,47 @@ class Dsp:
             return out, torch.view_as_complex(sp).transpose(1, 2), torch.view_as_complex(st).transpose(1, 2)
         return out
 
+    def loss_spectral_backward(self, pred: Tensor, target: Tensor, mel_weights: Optional[Tensor], c_mag: float,
+                               c_phase: float, c_perc: float, out: Optional[Tensor] = None,
+                               accumulate: bool = False, cotangent: bool = False):
+        """The gradient with respect to pred [B, L] of c_mag * mag_abs + c_phase * phase_abs +
+        c_perc * mel_log_abs summed over the batch: ``loss_spectral``'s columns at this handle's
+        n_fft and hop, differentiated on the spectra that call forms (m2_loss_spectral_backward).
+        -> float32 [B, L] on the device; ``out`` (contiguous float32, B * L elements) is written
+        and returned when given, overwritten or, with ``accumulate``, added to.  With ``cotangent``
+        also the complex64 cotangent [B, F, T] of pred's spectrum, d/dRe + i d/dIm per bin.  The
+        coefficients are host numbers; target gets no gradient."""
+        y, q = self._audio(pred), self._audio(target)
+        if y.shape != q.shape:
+            raise ValueError(f"loss_spectral_backward: pred {tuple(y.shape)} and target {tuple(q.shape)} differ")
+        B, L = y.shape
+        if L <= self.n_fft // 2:
+            raise RuntimeError(f"loss_spectral_backward: reflect padding of n_fft {self.n_fft} needs more than "
+                               f"{self.n_fft // 2} samples, got {L}")
+        w = None
+        if mel_weights is not None:
+            require_device(mel_weights, what="m2 dsp")
+            w = mel_weights.float().contiguous()
+        if out is None:
+            if accumulate:
+                raise ValueError("loss_spectral_backward: accumulate needs out")
+            out = torch.empty(B, L, device=y.device, dtype=torch.float32)
+        else:
+            require_device(out, what="m2 dsp")
+            if out.dtype != torch.float32 or out.numel() != B * L or not out.is_contiguous() or out.device != y.device:
+                raise ValueError(f"loss_spectral_backward: out must be contiguous float32 of {B * L} elements on "
+                                 f"{y.device}, got {out.dtype} {tuple(out.shape)} on {out.device}")
+        cot = torch.empty(B, self.frames(L), self.F, 2, device=y.device, dtype=torch.float32) if cotangent else None
+        need = int(_lib.load().m2_loss_spectral_backward_workspace_bytes(self.handle, B, L))
+        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=y.device)
+        _lib.call("m2_loss_spectral_backward", self.handle, y.data_ptr(), q.data_ptr(), B, L,
+                  None if w is None else w.data_ptr(), 0 if w is None else w.numel(), float(c_mag), float(c_phase),
+                  float(c_perc), int(bool(accumulate)), out.data_ptr(), None if cot is None else cot.data_ptr(),
+                  ws.data_ptr(), ws.numel(), stream_handle(y.device))
+        if cotangent:
+            return out, torch.view_as_complex(cot).transpose(1, 2)
+        return out
+
 
 
 _CACHE: Dict[Tuple, Dsp] = {}

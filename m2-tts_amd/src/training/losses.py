@@ -8,7 +8,7 @@ m2amd.dsp), which write per-utterance rows of double sums; a few torch ops on
 the device turn those rows into the reference's means, so a call needs no host
 synchronisation.
 
-**Values, and two gradients.**  By default every returned value is a 0-dim
+**Values, and three gradients.**  By default every returned value is a 0-dim
 float32 tensor on the inputs' device with ``requires_grad=False``: the values
 carry no autograd graph, the same contract M2TTSModel.forward has in this
 tree, and score a checkpoint with the objective it was trained on.
@@ -50,20 +50,44 @@ by ``grad_output``, on the device.
   and 2 (p - t) / n, a few device-side torch ops); ``generator_loss`` and
   ``feature_matching_loss`` stay plain values.  ``total_loss`` carries a graph
   only when every term of it with a non-zero weight has a gradient, i.e. with
-  ``spectral_loss_weight == perceptual_loss_weight == 0`` or without audio;
-  otherwise it stays graph-free and a one-time warning names the terms
-  without a gradient, because a ``backward()`` that silently omitted two
-  terms would be worse than none.
+  ``spectral_loss_weight == perceptual_loss_weight == 0``, without audio, or
+  with the spectral switch below; otherwise it stays graph-free and a one-time
+  warning names the terms without a gradient, because a ``backward()`` that
+  silently omitted two terms would be worse than none.
+
+**The spectral and perceptual gradient** has a switch of its own, default off
+and not in the state_dict: ``CombinedTTSLoss.enable_backward(spectral=True)``,
+or ``SpectralLoss.enable_backward()`` / ``PerceptualLoss.enable_backward()`` on
+either module alone.  ``enable_backward()`` and ``enable_backward(False)`` leave
+it off, and everything above is then exactly as described.  With it on,
+gradients enabled and a predicted audio that requires grad,
+``SpectralLoss.forward`` / ``stft_loss``, ``PerceptualLoss.forward`` and the
+``spectral_loss`` and ``perceptual_loss`` entries of generator mode carry a
+once-differentiable ``grad_fn`` that reaches the predicted audio (the target
+gets nothing), and generator mode's ``total_loss`` follows its rule: at the
+default weights every term now has a gradient, so ``total_loss.backward()``
+fills ``mel_pred``, ``duration_pred`` and ``audio_pred`` gradients.  Values are
+computed as without the switch and are bit-equal.  The gradient is computed in
+``backward``, from the saved audio pair, by m2_loss_spectral_backward: the
+forward's framing and FFT, the cotangent of every bin in double, an inverse FFT
+per frame and a fixed-order gather into each sample (the STFT's adjoint).  Its
+coefficients are host numbers from the shapes (``spectral_backward_calls``);
+the total runs three calls, n_fft 512, 1024 and 2048, the 1024 one carrying the
+perceptual term with its weight, each accumulating onto a copy of the generator
+step's gradient, and ``grad_output`` multiplies on the device: no host
+synchronisation, and a forward that is never backpropagated costs nothing
+extra.  In a frame that reflect padding makes symmetric (frame 0; the last when
+L = 1 mod hop) the imaginary parts are rounding residue and so is the sign of
+the phase term in every bin, in any float32 evaluation including the
+reference's; the kernel differentiates on its own spectrum.
 
 One difference from the reference: there a generator ``backward()`` also fills
 the discriminators' ``.grad``, which its trainer zeroes before the next
 discriminator step, so nothing reads them; here the generator step leaves the
 42 parameters' ``.grad`` alone.
 
-``spectral_loss`` and ``perceptual_loss`` have no gradient yet (they need the
-STFT's adjoint), nor does anything go through
-``MultiScaleDiscriminator.forward`` or into ``M2TTSModel``, and the trainers
-are not part of this package.
+Nothing goes through ``MultiScaleDiscriminator.forward`` or into
+``M2TTSModel`` yet, and the trainers are not part of this package.
 
 The discriminators' parameters live in plain ``nn.Conv1d`` modules built in the
 reference's order, so ``torch.manual_seed(s); CombinedTTSLoss()`` gives the
@@ -86,6 +110,9 @@ logger = logging.getLogger(__name__)
 
 Tensor = torch.Tensor
 SAMPLE_RATE = 22050  # names the m2_dsp tables; no loss depends on it
+# PerceptualLoss's framing and feature count (the reference's _mel_features): its forward and its
+# gradient both read them from here
+PERCEPTUAL_N_FFT, PERCEPTUAL_HOP, PERCEPTUAL_MELS = 1024, 256, 80
 
 
 def _require(*tensors, what: str):
@@ -118,14 +145,105 @@ def _spectral_rows(p: Tensor, t: Tensor, n_fft: int, hop: int, cache: Optional[d
     return rows
 
 
+def spectral_backward_calls(B: int, L: int, n_fft_list=(512, 1024, 2048), hop_length_factor: float = 0.25,
+                            spectral_weight: float = 1.0, perceptual_weight: float = 0.0):
+    """The Dsp.loss_spectral_backward calls behind the gradient of spectral_weight * SpectralLoss +
+    perceptual_weight * PerceptualLoss for audio [B, L]: [(n_fft, hop, c_mag, c_phase, c_perc)], host
+    numbers from the shapes.  Per n_fft the means over B F frames bins, averaged over the sizes:
+    c_mag = spectral_weight / (len(n_fft_list) B F frames), c_phase = 0.1 c_mag; the perceptual mean
+    over B PERCEPTUAL_MELS frames joins the call at PerceptualLoss's framing (1024, 256):
+    c_perc = perceptual_weight / (B PERCEPTUAL_MELS frames).
+    Terms of weight 0 make no call."""
+    calls: Dict[Tuple[int, int], list] = {}
+    if B <= 0:
+        return []
+    if spectral_weight:
+        for n_fft in n_fft_list:
+            hop = int(n_fft * hop_length_factor)
+            c = float(spectral_weight) / (len(n_fft_list) * B * (n_fft // 2 + 1) * (1 + L // hop))
+            e = calls.setdefault((n_fft, hop), [0.0, 0.0, 0.0])
+            e[0] += c
+            e[1] += 0.1 * c
+    if perceptual_weight:
+        e = calls.setdefault((PERCEPTUAL_N_FFT, PERCEPTUAL_HOP), [0.0, 0.0, 0.0])
+        e[2] += float(perceptual_weight) / (B * PERCEPTUAL_MELS * (1 + L // PERCEPTUAL_HOP))
+    return [(n_fft, hop, c[0], c[1], c[2]) for (n_fft, hop), c in calls.items()]
+
+
+def _spectral_gradient(pred: Tensor, target: Tensor, calls, base: Optional[Tensor] = None) -> Tensor:
+    """float32 [B, L]: a copy of ``base`` (or nothing) plus the gradients of ``calls`` with respect to
+    pred, each call accumulating onto the one before in stream order."""
+    from m2amd.dsp import get_dsp
+    with torch.no_grad():
+        p, t = _audio_pair(pred, target, "SpectralLoss")
+        out = None if base is None else base.detach().float().reshape(p.shape).clone(
+            memory_format=torch.contiguous_format)
+        for n_fft, hop, c_mag, c_phase, c_perc in calls:
+            d = get_dsp(SAMPLE_RATE, n_fft, hop, n_fft, device=p.device)
+            out = d.loss_spectral_backward(p, t, PerceptualLoss.mel_weights(p.device, n_fft // 2 + 1), c_mag, c_phase,
+                                           c_perc, out=out, accumulate=out is not None)
+        return torch.zeros_like(p) if out is None else out
+
+
+class _AttachSpectral(torch.autograd.Function):
+    """_AttachGradients whose last input, the predicted audio, gets the spectral and perceptual
+    gradient of ``calls`` as well: computed in backward from the saved audio pair, so a forward that
+    is never backpropagated launches nothing, and accumulated onto a copy of ``base`` (the audio's
+    kept gradient, or None)."""
+
+    @staticmethod
+    def forward(ctx, value, grads, base, calls, target, *inputs):
+        ctx.grads = [g.to(x.dtype).reshape(x.shape) for g, x in zip(grads, inputs[:-1])]
+        ctx.base, ctx.calls = base, calls
+        ctx.save_for_backward(inputs[-1], target)
+        return value.clone()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        pred, target = ctx.saved_tensors
+        need = ctx.needs_input_grad[5:]
+        audio = None
+        if need[-1]:
+            g = _spectral_gradient(pred, target, ctx.calls, ctx.base)
+            audio = (grad_output.to(g.dtype) * g).to(pred.dtype).reshape(pred.shape)
+        return (None,) * 5 + tuple(grad_output.to(g.dtype) * g if n else None
+                                   for g, n in zip(ctx.grads, need[:-1])) + (audio,)
+
+
+def _attach_spectral(value: Tensor, pairs, audio_pred: Tensor, audio_target: Tensor, calls, base=None) -> Tensor:
+    """``value`` (no graph) with a grad_fn that reaches the inputs of ``pairs`` as _attach does and
+    audio_pred through ``calls`` (spectral_backward_calls) on top of ``base``."""
+    with torch.enable_grad():
+        return _AttachSpectral.apply(value, [g for _, g in pairs], base, calls, audio_target.detach(),
+                                     *[x for x, _ in pairs], audio_pred)
+
+
+def _switched(module, pred: Optional[Tensor]) -> bool:
+    """Whether ``module``'s own switch gives a term of ``pred`` a graph: the switch, grad mode, and pred itself."""
+    return module.backward_enabled and torch.is_grad_enabled() and pred is not None and pred.requires_grad
+
+
 class SpectralLoss(nn.Module):
     """Multi-scale spectral loss: per n_fft, mean | |P| - |T| | + 0.1 mean |angle P - angle T|
-    over torch.stft(hop n_fft * factor, Hann, centre, reflect padding), averaged over the sizes."""
+    over torch.stft(hop n_fft * factor, Hann, centre, reflect padding), averaged over the sizes.
+    After enable_backward() the value carries the gradient with respect to pred_audio."""
+
+    backward_enabled = False  # set by enable_backward(); a plain attribute, not in the state_dict
 
     def __init__(self, n_fft_list=[512, 1024, 2048], hop_length_factor=0.25):
         super().__init__()
         self.n_fft_list = n_fft_list
         self.hop_length_factor = hop_length_factor
+
+    def enable_backward(self, enabled: bool = True):
+        """Let the loss carry its gradient with respect to the predicted audio (module docstring)."""
+        self.backward_enabled = bool(enabled)
+        return self
+
+    def _calls(self, shape, weight: float = 1.0, n_fft_list=None):
+        return spectral_backward_calls(shape[0], shape[1], self.n_fft_list if n_fft_list is None else n_fft_list,
+                                       self.hop_length_factor, weight, 0.0)
 
     def _stft_loss(self, p: Tensor, t: Tensor, n_fft: int, cache: Optional[dict]) -> Tensor:
         r = _spectral_rows(p, t, n_fft, int(n_fft * self.hop_length_factor), cache)
@@ -135,7 +253,10 @@ class SpectralLoss(nn.Module):
         """The loss of one STFT size."""
         with torch.no_grad():
             p, t = _audio_pair(pred_audio, target_audio, "SpectralLoss")
-            return self._stft_loss(p, t, n_fft, None).float()
+            value = self._stft_loss(p, t, n_fft, None).float()
+        if _switched(self, pred_audio):
+            return _attach_spectral(value, [], pred_audio, target_audio, self._calls(p.shape, 1.0, [n_fft]))
+        return value
 
     def _value(self, p: Tensor, t: Tensor, cache: Optional[dict]) -> Tensor:
         total = 0
@@ -146,7 +267,10 @@ class SpectralLoss(nn.Module):
     def forward(self, pred_audio, target_audio):
         with torch.no_grad():
             p, t = _audio_pair(pred_audio, target_audio, "SpectralLoss")
-            return self._value(p, t, None).float()
+            value = self._value(p, t, None).float()
+        if _switched(self, pred_audio):
+            return _attach_spectral(value, [], pred_audio, target_audio, self._calls(p.shape))
+        return value
 
 
 class _DiscriminatorStep(torch.autograd.Function):
@@ -354,14 +478,24 @@ class PerceptualLoss(nn.Module):
     ln(w_j sum_f |X| + 1e-8) of a frame's magnitude sum."""
 
     _WEIGHTS: Dict[Tuple, Tensor] = {}
+    backward_enabled = False  # set by enable_backward(); a plain attribute, not in the state_dict
 
     def __init__(self, model_type="mel"):
         super().__init__()
         self.model_type = model_type
         self.feature_extractor = self._mel_features
 
+    def enable_backward(self, enabled: bool = True):
+        """Let the loss carry its gradient with respect to the predicted audio (module docstring)."""
+        self.backward_enabled = bool(enabled)
+        return self
+
+    @staticmethod
+    def _calls(shape, weight: float = 1.0):
+        return spectral_backward_calls(shape[0], shape[1], (), 0.25, 0.0, weight)
+
     @classmethod
-    def mel_weights(cls, device, freq_bins: int = 513, n_mels: int = 80) -> Tensor:
+    def mel_weights(cls, device, freq_bins: int = PERCEPTUAL_N_FFT // 2 + 1, n_mels: int = PERCEPTUAL_MELS) -> Tensor:
         """The filter rows' values, by the reference's float32 expressions."""
         key = (torch.device(device), freq_bins, n_mels)
         w = cls._WEIGHTS.get(key)
@@ -371,24 +505,28 @@ class PerceptualLoss(nn.Module):
             w = cls._WEIGHTS[key] = f[:, 0].contiguous().to(device)
         return w
 
-    def _mel_features(self, audio, n_mels=80):
+    def _mel_features(self, audio, n_mels=PERCEPTUAL_MELS):
         """ln(mel + 1e-8) [B, n_mels, T] of audio [B, 1, L]: torch.stft(1024, 256) magnitudes, summed per frame."""
         _require(audio, what="PerceptualLoss")
         from m2amd.dsp import get_dsp
         with torch.no_grad():
             y = audio.detach().float().reshape(audio.shape[0], -1)
-            _, spec, _ = get_dsp(SAMPLE_RATE, 1024, 256, 1024, device=y.device).loss_spectral(y, y, spectra=True)
+            _, spec, _ = get_dsp(SAMPLE_RATE, PERCEPTUAL_N_FFT, PERCEPTUAL_HOP, PERCEPTUAL_N_FFT,
+                                  device=y.device).loss_spectral(y, y, spectra=True)
             mag = spec.abs().sum(dim=1, keepdim=True)
-            return torch.log(self.mel_weights(y.device, 513, n_mels).view(1, -1, 1) * mag + 1e-8)
+            return torch.log(self.mel_weights(y.device, PERCEPTUAL_N_FFT // 2 + 1, n_mels).view(1, -1, 1) * mag + 1e-8)
 
     def _value(self, p: Tensor, t: Tensor, cache: Optional[dict]) -> Tensor:
-        r = _spectral_rows(p, t, 1024, 256, cache)
-        return r["mel_log_abs"] / (r["frames"] * 80)
+        r = _spectral_rows(p, t, PERCEPTUAL_N_FFT, PERCEPTUAL_HOP, cache)
+        return r["mel_log_abs"] / (r["frames"] * PERCEPTUAL_MELS)
 
     def forward(self, pred_audio, target_audio):
         with torch.no_grad():
             p, t = _audio_pair(pred_audio, target_audio, "PerceptualLoss")
-            return self._value(p, t, None).float()
+            value = self._value(p, t, None).float()
+        if _switched(self, pred_audio):
+            return _attach_spectral(value, [], pred_audio, target_audio, self._calls(p.shape))
+        return value
 
 
 class CombinedTTSLoss(nn.Module):
@@ -424,12 +562,15 @@ class CombinedTTSLoss(nn.Module):
     backward_enabled = False  # set by enable_backward(); a plain attribute, not in the state_dict
     _warned_partial_total = False
 
-    def enable_backward(self, enabled: bool = True):
-        """Switch the gradients of the discriminator step and of the generator step on or off
-        (module docstring)."""
+    def enable_backward(self, enabled: bool = True, spectral: bool = False):
+        """Switch the gradients of the discriminator step and of the generator step on or off;
+        ``spectral`` also switches on those of spectral_loss and perceptual_loss, which
+        enable_backward() and enable_backward(False) leave off (module docstring)."""
         self.backward_enabled = bool(enabled)
         if self.adversarial_loss is not None:
             self.adversarial_loss.enable_backward(enabled)
+        self.spectral_loss.enable_backward(bool(enabled) and bool(spectral))
+        self.perceptual_loss.enable_backward(bool(enabled) and bool(spectral))
         return self
 
     def _wants_gradient(self, pred: Optional[Tensor]) -> bool:
@@ -524,6 +665,9 @@ class CombinedTTSLoss(nn.Module):
                  "duration_loss": gen and self._wants_gradient(duration_pred),
                  "adversarial": gen and self._wants_gradient(audio_pred)}
         grads: Dict[str, Tuple[Tensor, Tensor]] = {}
+        # the terms whose gradient is computed in backward, by name: the module behind each
+        lazy = {k: m for k, m in (("spectral_loss", self.spectral_loss), ("perceptual_loss", self.perceptual_loss))
+                if gen and audio_target is not None and _switched(m, audio_pred)}
         with torch.no_grad():
             v: Dict[str, Tensor] = {}  # float64 on the device
             v["mel_loss"] = self._mel_loss(mel_pred, mel_target, mel_lengths)
@@ -573,14 +717,27 @@ class CombinedTTSLoss(nn.Module):
             pairs = [(x, weights[k] * g) for k, (x, g) in grads.items() if k in weights and weights[k] != 0]
             if "adversarial" in grads:
                 pairs.append(grads["adversarial"])
-        if grads:
+        if grads or lazy:
             for k in ("mel_loss", "duration_loss"):
                 if k in grads:
                     losses[k] = _attach(losses[k], [grads[k]])
+            for k, m in lazy.items():
+                losses[k] = _attach_spectral(losses[k], [], audio_pred, audio_target, m._calls(p.shape))
             have = {"mel_loss": "mel_loss", "duration_loss": "duration_loss", "generator_loss": "adversarial",
-                    "feature_matching_loss": "adversarial"}
-            missing = [k for k, w in weights.items() if w != 0 and have.get(k) not in grads]
-            if not missing:
+                    "feature_matching_loss": "adversarial", "spectral_loss": "spectral_loss",
+                    "perceptual_loss": "perceptual_loss"}
+            missing = [k for k, w in weights.items() if w != 0 and have.get(k) not in grads and have.get(k) not in lazy]
+            calls = spectral_backward_calls(
+                p.shape[0], p.shape[1], self.spectral_loss.n_fft_list, self.spectral_loss.hop_length_factor,
+                self.spectral_loss_weight if "spectral_loss" in lazy else 0.0,
+                self.perceptual_loss_weight if "perceptual_loss" in lazy else 0.0) if lazy else []
+            if not missing and calls:
+                # the audio's kept gradient (the generator step's d_fake) is the base the calls add to
+                base = grads["adversarial"][1] if "adversarial" in grads else None
+                others = [pair for pair in pairs if pair[0] is not audio_pred]
+                losses["total_loss"] = _attach_spectral(losses["total_loss"], others, audio_pred, audio_target, calls,
+                                                        base)
+            elif not missing:
                 losses["total_loss"] = _attach(losses["total_loss"], pairs)
             elif not self._warned_partial_total:
                 self._warned_partial_total = True

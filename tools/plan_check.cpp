@@ -15,7 +15,8 @@
 // tables and workgroup-slot counts, with the plans' invariants and three pinned lines.
 // The training losses' plans (csrc/losses_plan.h) run here too: the discriminator
 // calls' sizes and workspace layout against the formulas they replaced, and the
-// backward kernels' launch plans against their limits.
+// backward kernels' launch plans against their limits, and the spectral backward's
+// workspace carve against its frame count.
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -671,11 +672,42 @@ static void check_geometries() {
     std::printf(" (%d dw plans, %d dx geometries on the MFMA)\n", mfma_dw, mfma_dx);
 }
 
+// carve_spectral_bwd: one buffer of n_fft floats per frame, 1 + L / hop frames per utterance.  The
+// Sizer's count is that product, a Carve over exactly that many bytes places the buffer at the
+// base and one byte fewer is refused; at hop n_fft / 4 it is 16 bytes per sample and frame 0's share.
+static void check_spectral_bwd() {
+    int bad = 0, carved = 0;
+    for (const int n_fft : {512, 1024, 2048})
+        for (const int hop : {n_fft / 4, 200, 1})
+            for (const int B : {1, 2, 32})
+                for (const int L : {n_fft / 2 + 1, 777, 2624, 32000}) {
+                    if (L <= n_fft / 2) continue;
+                    const int frames = loss::spectral_frames(L, hop);
+                    const size_t want = (size_t)B * frames * n_fft * sizeof(float);
+                    Sizer s;
+                    loss::carve_spectral_bwd(s, n_fft, hop, B, L, nullptr);
+                    bad += frames != 1 + L / hop || s.off != want;
+                    if (hop == n_fft / 4) bad += want != (size_t)B * (16 * (size_t)(L / hop) * hop + 4 * n_fft);
+                    if (want > ((size_t)64 << 20)) continue;
+                    ++carved;
+                    std::vector<char> mem(want);
+                    Carve c(mem.data(), mem.size()), less(mem.data(), mem.size() - 1);
+                    float *fr = nullptr, *none = nullptr;
+                    loss::carve_spectral_bwd(c, n_fft, hop, B, L, &fr);
+                    loss::carve_spectral_bwd(less, n_fft, hop, B, L, &none);
+                    bad += !c.ok || less.ok || reinterpret_cast<char*>(fr) != mem.data() || none != nullptr;
+                }
+    std::printf("spectral_bwd:");
+    expect("carve_exact", bad == 0 && carved > 0, true);
+    std::printf(" (%d carved)\n", carved);
+}
+
 int main() {
     check_strips();
     check_launch_plans();
     check_disc_plans();
     check_geometries();
+    check_spectral_bwd();
     const m2_config stage1{256, 64, 64, 2, 2, 2, 128, 1000}, stage2{256, 96, 80, 3, 3, 2, 256, 1000};
     for (const bool huge : {false, true}) {
         check(2 * huge, "stage1", stage1, huge);

@@ -17,7 +17,13 @@ that computes both and one that computes the weight gradient alone.  The
 generator step is the generator-mode call again with the three predictions
 requiring grad (generator_step_ms, against generator_ms: generator_step_over_forward),
 generator_terms(...).backward(), m2_disc_gen_step alone, and the first-layer
-audio gradient kernel summed over the three scales.  Each
+audio gradient kernel summed over the three scales.  The spectral switch
+(enable_backward(spectral=True)): the generator-mode call alone
+(generator_spectral_call_ms), the call with total_loss.backward()
+(generator_spectral_step_ms, against generator_step_ms), and the three
+m2_loss_spectral_backward calls of the default weights on their own
+(spectral_backward_ms, against spectral_and_perceptual_ms:
+spectral_backward_over_forward).  Each
 figure is the median of --iters timed calls after --warmup untimed ones.
 """
 import argparse
@@ -110,6 +116,24 @@ def main():
     out["generator_step_ms"] = timed(lambda: loss(**kg, optimize_discriminator=False), args.warmup, args.iters)
     out["generator_step_over_forward"] = out["generator_step_ms"] / out["generator_ms"]
     out["generator_terms_backward_ms"] = timed(gen_step, args.warmup, args.iters)
+    # the spectral switch: the same call (its spectral gradient is computed in backward, so the call
+    # alone costs what generator_step_ms does), the call with total_loss.backward(), and the three
+    # m2_loss_spectral_backward calls alone against the forward line spectral_and_perceptual_ms
+    from training.losses import _spectral_gradient, spectral_backward_calls
+    loss.enable_backward(spectral=True)
+
+    def spectral_step():
+        for k in ("mel_pred", "duration_pred", "audio_pred"):
+            kg[k].grad = None
+        loss(**kg, optimize_discriminator=False)["total_loss"].backward()
+
+    out["generator_spectral_call_ms"] = timed(lambda: loss(**kg, optimize_discriminator=False), args.warmup, args.iters)
+    out["generator_spectral_step_ms"] = timed(spectral_step, args.warmup, args.iters)
+    out["generator_spectral_step_over_generator_step"] = out["generator_spectral_step_ms"] / out["generator_step_ms"]
+    calls = spectral_backward_calls(B, L, loss.spectral_loss.n_fft_list, loss.spectral_loss.hop_length_factor,
+                                    loss.spectral_loss_weight, loss.perceptual_loss_weight)
+    out["spectral_backward_ms"] = timed(lambda: _spectral_gradient(fake, real, calls), args.warmup, args.iters)
+    out["spectral_backward_over_forward"] = out["spectral_backward_ms"] / out["spectral_and_perceptual_ms"]
     loss.enable_backward(False)
     out["gen_step_ms"] = timed(lambda: h.gen_step(real, fake, loss.adversarial_loss_weight,
                                                   loss.feature_matching_weight), args.warmup, args.iters)
