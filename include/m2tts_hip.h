@@ -671,6 +671,95 @@ int32_t m2_loss_spectral_backward(const m2_dsp* dsp, const float* pred, const fl
                                   double c_perc, int32_t accumulate, float* d_pred, void* cot_pred, void* workspace,
                                   size_t workspace_bytes, void* stream);
 
+/* ---- vocoder training: a forward that keeps a tape, and the backward ---------
+ * The gradient of SimpleVocoder (kernel size 3) with respect to its 28
+ * parameters and its input mel, exact f32, without a model handle: an
+ * optimizer step changes every parameter, so these calls read the parameters
+ * where they are.  params: 28 device pointers in state_dict order and PyTorch
+ * layouts (input_conv.{weight,bias}, upsamples.k.{weight,bias},
+ * resblocks.k.conv1.{weight,bias}, resblocks.k.conv2.{weight,bias},
+ * output_conv.{weight,bias}; ConvTranspose1d weights [Cin, Cout, 2r]).
+ * Shapes: mel [B,M,T], M >= 1; C a multiple of 16 in [16, 256]; at most 65535
+ * utterances, 2^22 frames each and 2^24 in all (else M2_E_SHAPE).  B = 0 or
+ * T = 0 launches nothing and returns M2_OK.  No call synchronises.
+ *
+ * m2_vocoder_train_forward: audio [B,1,64T], bit for bit what a stand-alone
+ * SimpleVocoder's per-op forward gives (the same kernels, m2_conv1d and
+ * m2_conv_transpose1d with their fused activation and residual), each layer
+ * writing into the tape.  The tape holds 14 float32 maps [B, channels,
+ * length], each on a 256-byte boundary (m2_vocoder_tape_map: offset in floats
+ * from the tape's base), c_k = C / 2^(k+1), L_k = T x 4, 16, 32, 64:
+ *   0       h      [C, T]      input_conv(mel)
+ *   1 + 3k  a_k    [c_k, L_k]  leaky(ConvT_k(x_k), 0.1), post-activation
+ *   2 + 3k  lv_k   [c_k, L_k]  leaky(conv1_k(a_k), 0.1), post-activation
+ *   3 + 3k  x_k+1  [c_k, L_k]  conv2_k(lv_k) + a_k
+ *   13      y      [1, 64 T]   the audio (tanh' = 1 - y^2)
+ * Slope 0.1 keeps the sign, so the backward reads LeakyReLU's predicate
+ * (value > 0) from the stored value.  About 10.7 MB per utterance at stage1,
+ * T = 500.  A tape smaller than m2_vocoder_tape_bytes is M2_E_ARG.
+ *
+ * m2_vocoder_backward: given d_audio [B,1,64T], the cotangent of the audio,
+ * d_mel [B,M,T] (or NULL: the input conv's data gradient is skipped;
+ * otherwise always overwritten) and grads: 28 device pointers shaped like the
+ * parameters, each overwritten or, with `accumulate`, added to as one fp32
+ * addition per element; a NULL entry skips that tensor.  mel, params and the
+ * tape are those of the forward call.  No floating-point atomics: weight and
+ * bias gradients reduce over (utterance, position) through partials in the
+ * workspace that are added in a fixed order, so equal inputs give equal bits;
+ * d_mel has no reduction over the batch, so a batched row equals the row of
+ * the utterance computed alone.  A workspace smaller than
+ * m2_vocoder_backward_workspace_bytes is M2_E_ARG (two cotangent maps and g_v
+ * of the widest layer, 4 C T floats per utterance each, the partials, and one
+ * weight and one bias of the largest size: with `accumulate` a gradient is
+ * formed there exactly as without it and then added onto the caller's).
+ * The launches: voc_out_bwd_kernel (tanh', the output conv's data gradient and
+ * its weight / bias partials in one pass), per stage voc_res_dx_kernel (the
+ * resblock's data gradient, conv2^T(g_r) and g_a kept in LDS), the weight
+ * gradients on the exact-f32 MFMA (m2_conv1d_strided_backward's kernels) or,
+ * below 16 output channels, voc_dw_narrow_kernel, and the ConvTranspose1d's
+ * gradients as those of the strided Conv1d with the roles swapped
+ * (m2_conv1d_strided on g_u with the ConvT weight read as [Cout', Cin', 2r]).
+ *
+ * m2_debug_vocoder_grad_plan: the tape and workspace sizes and every launch
+ * of m2_vocoder_backward(M, C, B, T) with all gradients asked for, as one
+ * line of text (the format is fixed and documented in
+ * csrc/vocoder_grad_plan.h).  Host arithmetic only.  Writes at most cap bytes
+ * (NUL-terminated) and returns the line's length, or a negative M2_E_* code.
+ *
+ * The three kernels alone:
+ * m2_vocoder_out_backward: y = tanh(conv(x [B,c,L]; w [1,c,3], padding 1) + b),
+ *   gy and y [B,1,L] -> gx [B,c,L], dw [1,c,3], db [1] (each may be NULL),
+ *   overwritten.
+ * m2_resblock_backward: x_out = conv2(lv) + a, lv = leaky(conv1(a)), all
+ *   [B,c,L], c <= 128, w1 and w2 [c,c,3]; from g_r, the cotangent of x_out,
+ *   g_v (the cotangent of conv1's output) and g_u = leaky'(a) x the cotangent
+ *   of a.
+ * m2_conv1d_narrow_dw: dw [Cout,Cin,k] and db [Cout] (either may be NULL) of
+ *   y = conv1d(x [B,Cin,L]; stride, padding) + b given dy, overwritten, for
+ *   Cout < 16 and
+ *   windows that fit 48 KiB of LDS (else M2_E_SHAPE; the query returns 0). */
+size_t m2_vocoder_tape_bytes(int32_t M, int32_t C, int32_t B, int32_t T);
+int32_t m2_vocoder_tape_map(int32_t M, int32_t C, int32_t B, int32_t T, int32_t index, size_t* offset_floats,
+                            int32_t* channels, int32_t* length);
+int32_t m2_vocoder_train_forward(const float* const* params, int32_t M, int32_t C, const float* mel, int32_t B,
+                                 int32_t T, float* audio, void* tape, size_t tape_bytes, void* stream);
+size_t m2_vocoder_backward_workspace_bytes(int32_t M, int32_t C, int32_t B, int32_t T);
+int32_t m2_vocoder_backward(const float* const* params, int32_t M, int32_t C, const float* mel, int32_t B, int32_t T,
+                            const void* tape, const float* d_audio, float* d_mel, float* const* grads,
+                            int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream);
+int32_t m2_debug_vocoder_grad_plan(int32_t M, int32_t C, int32_t B, int32_t T, char* out, size_t cap);
+size_t m2_vocoder_out_backward_workspace_bytes(int32_t B, int32_t c, int32_t L);
+int32_t m2_vocoder_out_backward(const float* gy, const float* y, const float* x, const float* w, int32_t B, int32_t c,
+                                int32_t L, float* gx, float* dw, float* db, void* workspace, size_t workspace_bytes,
+                                void* stream);
+int32_t m2_resblock_backward(const float* g_r, const float* lv, const float* a, const float* w1, const float* w2,
+                             int32_t B, int32_t c, int32_t L, float* g_v, float* g_u, void* stream);
+size_t m2_conv1d_narrow_dw_workspace_bytes(int32_t ksize, int32_t stride, int32_t padding, int32_t B, int32_t Cin,
+                                           int32_t Cout, int32_t L);
+int32_t m2_conv1d_narrow_dw(const float* x, const float* dy, int32_t ksize, int32_t stride, int32_t padding, int32_t B,
+                            int32_t Cin, int32_t Cout, int32_t L, float* dw, float* db, void* workspace,
+                            size_t workspace_bytes, void* stream);
+
 /* ---- measurement ----------------------------------------------------------
  * Kernel timing with HIP events recorded on the launch stream around each of
  * the fused vocoder's kernels (bench.py's roofline).  enable: allocate event

@@ -54,6 +54,7 @@
 #include <vector>
 
 #include "audio_dsp.h"
+#include "conv_launch.h"
 #include "losses_plan.h"
 
 namespace m2 {
@@ -522,7 +523,6 @@ __global__ __launch_bounds__(NT) void conv_dw_direct_kernel(const float* __restr
 
 // db[co] = (accumulate ? db[co] : 0) + sum over utterances and positions of dy.  grid (Cout),
 // kDbThreads threads: few workgroups (64 on the first layer) each stream a whole channel.
-constexpr int kDbThreads = 1024;
 __global__ __launch_bounds__(kDbThreads) void conv_db_kernel(const float* __restrict__ dy, int nb, int Cout, int Lo,
                                                              int accumulate, float* __restrict__ db) {
     __shared__ double red[kDbThreads / 64];
@@ -787,6 +787,87 @@ __global__ __launch_bounds__(256) void spectral_fold_kernel(const float* __restr
 }  // namespace loss
 }  // namespace m2
 
+namespace m2 {
+namespace loss {
+
+// The launchers of one layer (conv_launch.h), shared with the vocoder's backward.  Grids and LDS
+// bytes are the rows of losses_plan.h.
+static dim3 grid_of(const LaunchRow& r) { return dim3(r.gx, r.gy, r.gz); }
+
+int32_t launch_conv(const float* x, const float* w, const float* b, float* y, const ConvGeo& g, int nb, int Lraw,
+                    int pool, bool packed, float in_slope, float slope, hipStream_t st) {
+    const int L = Lraw / pool, Lo = conv_out_len(L, g);
+    const Path path = conv_path(g);
+    if (pool != 1 && path != PATH_DIRECT) return fail(M2_E_INTERNAL, "launch_conv: only the direct kernel pools");
+    const LaunchRow r = conv_row(g, nb, L);
+    if (path == PATH_MFMA) {
+        const WStride ws = w_stride(g, packed);
+        hipLaunchKernelGGL(conv_mfma_kernel, grid_of(r), dim3(r.threads), r.lds, st, x, w, b, y, g, L, Lo, ws.sCo,
+                           ws.sCi, ws.sK, in_slope, slope);
+    } else if (path == PATH_WAVE) {
+        hipLaunchKernelGGL(conv_wave_kernel, grid_of(r), dim3(r.threads), 0, st, x, w, b, y, g, L, Lo, in_slope, slope);
+    } else {
+        hipLaunchKernelGGL(conv_direct_kernel, grid_of(r), dim3(r.threads), 0, st, x, w, b, y, g, Lraw, pool, L, Lo,
+                           in_slope, slope);
+    }
+    M2_LAUNCHED(r.kernel);
+    return M2_OK;
+}
+
+int32_t launch_dw_finish(const float* part, size_t n, int splits, bool accumulate, float* dw, hipStream_t st) {
+    hipLaunchKernelGGL(dw_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, part, n, splits,
+                       accumulate ? 1 : 0, dw);
+    M2_LAUNCHED("dw_finish_kernel");
+    return M2_OK;
+}
+
+int32_t launch_conv_db(const float* dy, int nb, int Cout, int Lo, bool accumulate, float* db, hipStream_t st) {
+    hipLaunchKernelGGL(conv_db_kernel, dim3(Cout), dim3(kDbThreads), 0, st, dy, nb, Cout, Lo, accumulate ? 1 : 0, db);
+    M2_LAUNCHED("conv_db_kernel");
+    return M2_OK;
+}
+
+int32_t launch_conv_bwd(const float* x_pre, const float* w, const float* dy, const ConvGeo& g, int nb, int L,
+                        bool packed, float in_slope, float* dx, float* dw, float* db, bool accumulate, float* part,
+                        hipStream_t st) {
+    const int Lo = conv_out_len(L, g), Cg = g.Cin / g.groups;
+    const size_t n = (size_t)g.Cout * Cg * g.k;
+    std::vector<LaunchRow> rows;
+    conv_bwd_rows(g, nb, L, dx != nullptr, dw != nullptr, false, rows);
+    size_t i = 0;
+    if (dx) {
+        const WStride ws = w_stride(g, packed);
+        const LaunchRow& r = rows[i++];
+        if (dx_mfma_ok(g))
+            hipLaunchKernelGGL(conv_dx_mfma_kernel, grid_of(r), dim3(r.threads), r.lds, st, x_pre, w, dy, dx, g, L, Lo,
+                               ws.sCo, ws.sCi, ws.sK, in_slope, cdiv(g.k, g.stride), dx_phases(g));
+        else
+            hipLaunchKernelGGL(conv_dx_direct_kernel, grid_of(r), dim3(r.threads), 0, st, x_pre, w, dy, dx, g, L, Lo,
+                               ws.sCo, ws.sCi, ws.sK, in_slope);
+        M2_LAUNCHED(r.kernel);
+    }
+    if (dw) {
+        const DwPlan p = dw_plan(g, nb, L);
+        const LaunchRow& r = rows[i++];
+        if (p.mfma) {
+            hipLaunchKernelGGL(conv_dw_mfma_kernel, grid_of(r), dim3(r.threads), r.lds, st, x_pre, dy, part, g, nb, L,
+                               Lo, in_slope, p.nciB, p.cps);
+            M2_LAUNCHED(r.kernel);
+            const int32_t rc = launch_dw_finish(part, n, p.splits, accumulate, dw, st);
+            if (rc != M2_OK) return rc;
+        } else {
+            hipLaunchKernelGGL(conv_dw_direct_kernel, grid_of(r), dim3(r.threads), 0, st, x_pre, dy, dw, g, nb, L, Lo,
+                               in_slope, accumulate ? 1 : 0);
+            M2_LAUNCHED(r.kernel);
+        }
+    }
+    if (db) return launch_conv_db(dy, nb, g.Cout, Lo, accumulate, db, st);
+    return M2_OK;
+}
+
+}  // namespace loss
+}  // namespace m2
+
 // Packed weights of the discriminators of one MultiScaleDiscriminator.
 struct m2_disc {
     int n_scales;
@@ -809,29 +890,8 @@ bool geo_ok(const ConvGeo& g) {
            g.Cin % g.groups == 0 && g.Cout % g.groups == 0;
 }
 
-// One layer over nb utterances; packed: w is [k, Cin/g, Cout] (MFMA path only).
-int32_t launch_conv(const float* x, const float* w, const float* b, float* y, const ConvGeo& g, int nb, int Lraw,
-                    int pool, bool packed, float in_slope, float slope, hipStream_t st) {
-    const int L = Lraw / pool, Lo = loss::conv_out_len(L, g);
-    const loss::Path path = loss::conv_path(g);
-    if (pool != 1 && path != loss::PATH_DIRECT) return fail(M2_E_INTERNAL, "launch_conv: only the direct kernel pools");
-    if (path == loss::PATH_MFMA) {
-        const loss::WStride ws = loss::w_stride(g, packed);
-        const dim3 grid(cdiv(Lo, loss::kNP), cdiv(g.Cout, loss::kCoWg), nb);
-        hipLaunchKernelGGL(loss::conv_mfma_kernel, grid, dim3(256), loss::kCch * loss::spanp_of(g) * sizeof(float), st,
-                           x, w, b, y, g, L, Lo, ws.sCo, ws.sCi, ws.sK, in_slope, slope);
-        M2_LAUNCHED("conv_mfma_kernel");
-    } else if (path == loss::PATH_WAVE) {
-        hipLaunchKernelGGL(loss::conv_wave_kernel, dim3(cdiv(Lo, 4), g.Cout, nb), dim3(256), 0, st, x, w, b, y, g, L,
-                           Lo, in_slope, slope);
-        M2_LAUNCHED("conv_wave_kernel");
-    } else {
-        hipLaunchKernelGGL(loss::conv_direct_kernel, dim3(cdiv(Lo, 256), g.Cout, nb), dim3(256), 0, st, x, w, b, y, g,
-                           Lraw, pool, L, Lo, in_slope, slope);
-        M2_LAUNCHED("conv_direct_kernel");
-    }
-    return M2_OK;
-}
+using loss::launch_conv;
+using loss::launch_conv_bwd;
 
 // The handle keeps the weights of the layers on the MFMA path packed as [k, Cin/g, Cout].
 bool disc_packed(int layer) { return loss::conv_path(kDisc[layer]) == loss::PATH_MFMA; }
@@ -864,50 +924,6 @@ int32_t run_scale(const m2_disc* d, int s, const float* x, int nb, int L, float*
 }
 
 // ---- backward ----------------------------------------------------------------------
-
-// The gradients of one layer over nb utterances: x_pre [nb, Cin, L], dy [nb, Cout, Lo];
-// dx (or null) is overwritten; dw (or null: no weight gradient, no partials) and db (or null)
-// are overwritten or, with `accumulate`, added to.  packed: w is [k, Cin/g, Cout].  part holds
-// dw_plan's part_floats.
-int32_t launch_conv_bwd(const float* x_pre, const float* w, const float* dy, const ConvGeo& g, int nb, int L,
-                        bool packed, float in_slope, float* dx, float* dw, float* db, bool accumulate, float* part,
-                        hipStream_t st) {
-    const int Lo = loss::conv_out_len(L, g), Cg = g.Cin / g.groups;
-    const size_t n = (size_t)g.Cout * Cg * g.k;
-    if (dx) {
-        const loss::WStride ws = loss::w_stride(g, packed);
-        if (loss::dx_mfma_ok(g)) {
-            const int J = cdiv(g.k, g.stride), M = (L - 1 + g.pad) / g.stride + 1;
-            const dim3 grid(cdiv(M, loss::kDxM), (unsigned)loss::dx_grid_y(g), nb);
-            hipLaunchKernelGGL(loss::conv_dx_mfma_kernel, grid, dim3(256), loss::dx_lds_bytes(g), st, x_pre, w, dy, dx,
-                               g, L, Lo, ws.sCo, ws.sCi, ws.sK, in_slope, J, loss::dx_phases(g));
-            M2_LAUNCHED("conv_dx_mfma_kernel");
-        } else {
-            hipLaunchKernelGGL(loss::conv_dx_direct_kernel, dim3(cdiv(L, 256), g.Cin, nb), dim3(256), 0, st, x_pre, w,
-                               dy, dx, g, L, Lo, ws.sCo, ws.sCi, ws.sK, in_slope);
-            M2_LAUNCHED("conv_dx_direct_kernel");
-        }
-    }
-    const loss::DwPlan p = dw ? loss::dw_plan(g, nb, L) : loss::DwPlan();
-    if (dw && p.mfma) {
-        hipLaunchKernelGGL(loss::conv_dw_mfma_kernel, dim3(p.blocks, cdiv(g.Cout, 16), p.splits), dim3(256), p.lds, st,
-                           x_pre, dy, part, g, nb, L, Lo, in_slope, p.nciB, p.cps);
-        M2_LAUNCHED("conv_dw_mfma_kernel");
-        hipLaunchKernelGGL(loss::dw_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, part, n,
-                           p.splits, accumulate ? 1 : 0, dw);
-        M2_LAUNCHED("dw_finish_kernel");
-    } else if (dw) {
-        hipLaunchKernelGGL(loss::conv_dw_direct_kernel, dim3((unsigned)n), dim3(dsp::NT), 0, st, x_pre, dy, dw, g, nb,
-                           L, Lo, in_slope, accumulate ? 1 : 0);
-        M2_LAUNCHED("conv_dw_direct_kernel");
-    }
-    if (db) {
-        hipLaunchKernelGGL(loss::conv_db_kernel, dim3(g.Cout), dim3(loss::kDbThreads), 0, st, dy, nb, g.Cout, Lo,
-                           accumulate ? 1 : 0, db);
-        M2_LAUNCHED("conv_db_kernel");
-    }
-    return M2_OK;
-}
 
 // The forward half of one (slice, scale) of m2_disc_losses, shared with the two steps so that
 // their rows are its rows bit for bit: each side that is given runs into act[side] (map[side][i]

@@ -5,6 +5,7 @@
 #pragma once
 
 #include <algorithm>
+#include <vector>
 
 #include "m2_common.h"
 
@@ -40,6 +41,7 @@ constexpr int kDwCiMax = 64;     // input channels per conv_dw_mfma workgroup
 constexpr int kMaxSplits = 64;   // split-K partials of one weight gradient
 constexpr size_t kPartFloats = (size_t)8 << 20;  // floats the partials of one layer may take (beyond one copy of dw)
 constexpr int kAuP = 256;        // pooled positions per conv_dx_audio workgroup
+constexpr int kDbThreads = 1024; // threads of a conv_db_kernel workgroup
 
 __host__ __device__ inline int conv_out_len(int L, const ConvGeo& g) { return (L + 2 * g.pad - g.k) / g.stride + 1; }
 inline int span_of(const ConvGeo& g) { return (kNP - 1) * g.stride + g.k; }
@@ -105,6 +107,50 @@ inline long long dx_grid_y(const ConvGeo& g) {
 }
 inline bool dx_mfma_ok(const ConvGeo& g) {
     return conv_path(g) == PATH_MFMA && g.Cin >= 16 && dx_lds_bytes(g) <= (size_t)kMaxLds && dx_grid_y(g) <= kMaxGrid;
+}
+
+// One kernel launch as a launcher issues it: what launch_conv and launch_conv_bwd (losses.hip) launch
+// for one layer, in order.  The launchers take their grids and LDS bytes from these rows.
+struct LaunchRow {
+    const char* kernel;
+    unsigned gx, gy, gz;
+    int threads;
+    size_t lds;
+};
+
+// launch_conv over nb utterances of L (pooled) input samples.
+inline LaunchRow conv_row(const ConvGeo& g, int nb, int L) {
+    const int Lo = conv_out_len(L, g);
+    const Path path = conv_path(g);
+    if (path == PATH_MFMA)
+        return {"conv_mfma_kernel", (unsigned)cdiv(Lo, kNP), (unsigned)cdiv(g.Cout, kCoWg), (unsigned)nb, 256,
+                (size_t)kCch * spanp_of(g) * sizeof(float)};
+    if (path == PATH_WAVE) return {"conv_wave_kernel", (unsigned)cdiv(Lo, 4), (unsigned)g.Cout, (unsigned)nb, 256, 0};
+    return {"conv_direct_kernel", (unsigned)cdiv(Lo, 256), (unsigned)g.Cout, (unsigned)nb, 256, 0};
+}
+
+// launch_conv_bwd over nb utterances of L input samples: the data gradient, the weight gradient
+// (its partials, then dw_finish_kernel) and the bias gradient, each when asked for.
+inline void conv_bwd_rows(const ConvGeo& g, int nb, int L, bool dx, bool dw, bool db, std::vector<LaunchRow>& out) {
+    const size_t n = (size_t)g.Cout * (g.Cin / g.groups) * g.k;
+    if (dx) {
+        if (dx_mfma_ok(g))
+            out.push_back({"conv_dx_mfma_kernel", (unsigned)cdiv((L - 1 + g.pad) / g.stride + 1, kDxM),
+                           (unsigned)dx_grid_y(g), (unsigned)nb, 256, dx_lds_bytes(g)});
+        else
+            out.push_back({"conv_dx_direct_kernel", (unsigned)cdiv(L, 256), (unsigned)g.Cin, (unsigned)nb, 256, 0});
+    }
+    if (dw) {
+        const DwPlan p = dw_plan(g, nb, L);
+        if (p.mfma) {
+            out.push_back({"conv_dw_mfma_kernel", (unsigned)p.blocks, (unsigned)cdiv(g.Cout, 16), (unsigned)p.splits, 256,
+                           p.lds});
+            out.push_back({"dw_finish_kernel", (unsigned)((n + 255) / 256), 1, 1, 256, 0});
+        } else {
+            out.push_back({"conv_dw_direct_kernel", (unsigned)n, 1, 1, 256, 0});
+        }
+    }
+    if (db) out.push_back({"conv_db_kernel", (unsigned)g.Cout, 1, 1, kDbThreads, 0});
 }
 
 // conv_dx_audio_kernel's LDS: the weights and dy's window of 16 channels.

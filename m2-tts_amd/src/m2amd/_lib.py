@@ -125,6 +125,20 @@ _SIGNATURES = {
     "m2_loss_spectral_backward_workspace_bytes": (c_size, [c_vp, c_i32, c_i32]),
     "m2_loss_spectral_backward": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_f64, c_f64, c_f64, c_i32, c_vp,
                                           c_vp, c_vp, c_size, c_vp]),
+    "m2_vocoder_tape_bytes": (c_size, [c_i32, c_i32, c_i32, c_i32]),
+    "m2_vocoder_tape_map": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "m2_vocoder_train_forward": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp, c_size, c_vp]),
+    "m2_vocoder_backward_workspace_bytes": (c_size, [c_i32, c_i32, c_i32, c_i32]),
+    "m2_vocoder_backward": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp,
+                                    c_size, c_vp]),
+    "m2_debug_vocoder_grad_plan": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_vp, c_size]),
+    "m2_vocoder_out_backward_workspace_bytes": (c_size, [c_i32, c_i32, c_i32]),
+    "m2_vocoder_out_backward": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_size,
+                                        c_vp]),
+    "m2_resblock_backward": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "m2_conv1d_narrow_dw_workspace_bytes": (c_size, [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32]),
+    "m2_conv1d_narrow_dw": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp,
+                                    c_size, c_vp]),
     "m2_front_bytes": (c_size, [c_vp, c_i32, c_i32]),
     "m2_inference_workspace_bytes": (c_size, [c_vp, c_i32, c_i32, c_i32]),
     "m2_inference_front": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_vp, c_size, c_vp, c_size, c_vp, c_vp]),

@@ -347,6 +347,139 @@ class Discriminators:
         return self._rows_call("gen_step", real, fake, (w_adv, w_fm), (_ptr(d_fake),)), d_fake
 
 
+VOCODER_PARAMS = 28
+VOCODER_TAPE_NAMES = ("h",) + tuple(f"{n}{k + (n == 'x')}" for k in range(4) for n in ("a", "lv", "x")) + ("y",)
+
+
+def _vocoder_params(params):
+    """The 28 SimpleVocoder parameters (state_dict order) as contiguous float32 device tensors, their
+    pointer array, and (M, C)."""
+    keep = [f32c(p.detach()) for p in params]
+    if len(keep) != VOCODER_PARAMS:
+        raise ValueError(f"vocoder: {VOCODER_PARAMS} parameters in state_dict order, got {len(keep)}")
+    require_device(*keep, what="vocoder parameter")
+    C, M, K = keep[0].shape
+    if K != 3:
+        raise NotImplementedError(f"vocoder backward: kernel size 3 only, got {K}")
+    return keep, (ctypes.c_void_p * VOCODER_PARAMS)(*[t.data_ptr() for t in keep]), int(M), int(C)
+
+
+def _vocoder_mel(mel: Tensor, M: int) -> Tensor:
+    require_device(mel, what="vocoder")
+    if mel.dim() != 3 or mel.shape[1] != M:
+        raise ValueError(f"vocoder: mel must be [B, {M}, T], got {tuple(mel.shape)}")
+    return f32c(mel.detach())
+
+
+def vocoder_train_forward(params, mel: Tensor):
+    """SimpleVocoder's forward from its 28 raw parameters, keeping a tape (m2_vocoder_train_forward):
+    (audio [B,1,64T], bit-equal to the stand-alone module's forward, and the tape, a uint8 tensor that
+    ``vocoder_tape_maps`` names and ``vocoder_backward`` reads)."""
+    keep, ptrs, M, C = _vocoder_params(params)
+    mel = _vocoder_mel(mel, M)
+    B, _, T = mel.shape
+    dev = mel.device
+    lib = _lib.load()
+    need = int(lib.m2_vocoder_tape_bytes(M, C, B, T))
+    if need == 0:
+        raise M2Error(f"vocoder_train_forward: unsupported shape M={M} C={C} B={B} T={T}")
+    tape = torch.empty(need, dtype=torch.uint8, device=dev)
+    audio = torch.empty(B, 1, 64 * T, device=dev, dtype=torch.float32)
+    _lib.call("m2_vocoder_train_forward", ptrs, M, C, _ptr(mel), B, T, _ptr(audio), _ptr(tape), tape.numel(),
+              stream_handle(dev))
+    return audio, tape
+
+
+def vocoder_tape_maps(tape: Tensor, M: int, C: int, B: int, T: int) -> dict:
+    """The maps of a tape as named float32 views [B, channels, length] (m2_vocoder_tape_map): h, then per
+    stage k a<k> = leaky(ConvT_k(x_k)), lv<k> = leaky(conv1_k(a_k)), x<k+1> = conv2_k(lv_k) + a_k, and y."""
+    lib = _lib.load()
+    flat = tape.view(torch.float32) if tape.numel() % 4 == 0 else tape[:tape.numel() // 4 * 4].view(torch.float32)
+    off, ch, n = ctypes.c_size_t(), ctypes.c_int32(), ctypes.c_int32()
+    out = {}
+    for i, name in enumerate(VOCODER_TAPE_NAMES):
+        _lib.check(lib.m2_vocoder_tape_map(M, C, B, T, i, ctypes.byref(off), ctypes.byref(ch), ctypes.byref(n)),
+                   "m2_vocoder_tape_map")
+        out[name] = flat[off.value:off.value + B * ch.value * n.value].view(B, ch.value, n.value)
+    return out
+
+
+def vocoder_backward(params, mel: Tensor, tape: Tensor, d_audio: Tensor, need_mel: bool = True, need=None,
+                     out=None):
+    """The gradients of SimpleVocoder given d_audio [B,1,64T] (m2_vocoder_backward): (d_mel [B,M,T] or None,
+    the 28 gradients in state_dict order, None where ``need[i]`` is false).  ``out`` (28 tensors or None
+    entries): gradients to add to instead of new tensors."""
+    keep, ptrs, M, C = _vocoder_params(params)
+    mel = _vocoder_mel(mel, M)
+    B, _, T = mel.shape
+    dev = mel.device
+    require_device(tape, d_audio, what="vocoder_backward")
+    d_audio = f32c(d_audio.detach().to(torch.float32))
+    if d_audio.numel() != B * 64 * T:
+        raise ValueError(f"vocoder_backward: d_audio must be {(B, 1, 64 * T)}, got {tuple(d_audio.shape)}")
+    lib = _lib.load()
+    if tape.numel() < int(lib.m2_vocoder_tape_bytes(M, C, B, T)):
+        raise ValueError("vocoder_backward: the tape is not that of this shape")
+    want = [True] * VOCODER_PARAMS if need is None else [bool(n) for n in need]
+    grads = []
+    for i, (p, w) in enumerate(zip(keep, want)):
+        if not w:
+            grads.append(None)
+        elif out is not None and out[i] is not None:
+            grads.append(out[i])
+        else:
+            grads.append(torch.empty_like(p) if out is None else torch.zeros_like(p))
+    gp =(ctypes.c_void_p * VOCODER_PARAMS)(*[_ptr(g) for g in grads])
+    d_mel = torch.empty_like(mel) if need_mel else None
+    nbytes = int(lib.m2_vocoder_backward_workspace_bytes(M, C, B, T))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    _lib.call("m2_vocoder_backward", ptrs, M, C, _ptr(mel), B, T, _ptr(tape), _ptr(d_audio), _ptr(d_mel), gp,
+              0 if out is None else 1, _ptr(ws), ws.numel(), stream_handle(dev))
+    return d_mel, grads
+
+
+def vocoder_out_backward(gy: Tensor, y: Tensor, x: Tensor, w: Tensor):
+    """(gx, dw, db) of y = tanh(conv1d(x [B,c,L], w [1,c,3], b, padding=1)) given gy (m2_vocoder_out_backward)."""
+    require_device(gy, y, x, w, what="vocoder_out_backward")
+    gy, y, x, w = f32c(gy), f32c(y), f32c(x), f32c(w)
+    B, c, L = x.shape
+    gx, dw, db = torch.empty_like(x), torch.empty_like(w), torch.empty(1, device=x.device, dtype=torch.float32)
+    ws = torch.empty(max(int(_lib.load().m2_vocoder_out_backward_workspace_bytes(B, c, L)), 1), dtype=torch.uint8,
+                     device=x.device)
+    _lib.call("m2_vocoder_out_backward", _ptr(gy), _ptr(y), _ptr(x), _ptr(w), B, c, L, _ptr(gx), _ptr(dw), _ptr(db),
+              _ptr(ws), ws.numel(), stream_handle(x.device))
+    return gx, dw, db
+
+
+def resblock_backward(g_r: Tensor, lv: Tensor, a: Tensor, w1: Tensor, w2: Tensor):
+    """(g_v, g_u) of x_out = conv2(lv) + a, lv = leaky(conv1(a), 0.1), a = leaky(u, 0.1) given g_r, the
+    cotangent of x_out (m2_resblock_backward): the cotangents of conv1's output and of u."""
+    require_device(g_r, lv, a, w1, w2, what="resblock_backward")
+    g_r, lv, a, w1, w2 = f32c(g_r), f32c(lv), f32c(a), f32c(w1), f32c(w2)
+    B, c, L = g_r.shape
+    g_v, g_u = torch.empty_like(g_r), torch.empty_like(g_r)
+    _lib.call("m2_resblock_backward", _ptr(g_r), _ptr(lv), _ptr(a), _ptr(w1), _ptr(w2), B, c, L, _ptr(g_v), _ptr(g_u),
+              stream_handle(g_r.device))
+    return g_v, g_u
+
+
+def conv1d_narrow_dw(x: Tensor, dy: Tensor, ksize: int, *, stride: int = 1, padding: int = 0):
+    """(dw [Cout,Cin,k], db [Cout]) of y = conv1d(x, w, b, stride, padding) given dy, for Cout < 16
+    (m2_conv1d_narrow_dw)."""
+    require_device(x, dy, what="conv1d_narrow_dw")
+    x, dy = f32c(x), f32c(dy)
+    B, Cin, L = x.shape
+    Cout = dy.shape[1]
+    geo = (int(ksize), int(stride), int(padding))
+    dw = torch.empty(Cout, Cin, ksize, device=x.device, dtype=torch.float32)
+    db = torch.empty(Cout, device=x.device, dtype=torch.float32)
+    ws = torch.empty(max(int(_lib.load().m2_conv1d_narrow_dw_workspace_bytes(*geo, B, Cin, Cout, L)), 1),
+                     dtype=torch.uint8, device=x.device)
+    _lib.call("m2_conv1d_narrow_dw", _ptr(x), _ptr(dy), *geo, B, Cin, Cout, L, _ptr(dw), _ptr(db), _ptr(ws),
+              ws.numel(), stream_handle(x.device))
+    return dw, db
+
+
 def embed_positional(ids: Tensor, emb: Tensor, pe: Tensor, scale: float) -> Tensor:
     require_device(ids, emb, what="embedding")
     ids = ids.to(torch.int64).contiguous()

@@ -146,11 +146,43 @@ class MelDecoder(nn.Module):
                           ln=(self.norm.weight, self.norm.bias))
 
 
+class _VocoderGrad(torch.autograd.Function):
+    """SimpleVocoder.forward with a graph: ops.vocoder_train_forward on the
+    module's own parameters, and ops.vocoder_backward on grad_output (once
+    differentiable).  Arguments: mel, then the 28 parameters in state_dict
+    order."""
+
+    @staticmethod
+    def forward(ctx, mel, *params):
+        audio, tape = ops.vocoder_train_forward(params, mel)
+        ctx.save_for_backward(mel, *params)
+        ctx.tape = tape
+        return audio
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        mel, *params = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        d_mel, grads = ops.vocoder_backward(params, mel, ctx.tape, grad_output, need_mel=need[0], need=need[1:])
+        return (d_mel, *grads)
+
+
 class SimpleVocoder(nn.Module):
     """input_conv -> 4 x [ConvT(k=2r, s=r, p=r/2) -> leaky(0.1) -> resblock]
     -> output_conv -> tanh; 64 samples per mel frame (reference
     tts_model.py:231-297).  ``kernel_size``/``n_layers`` are accepted and, as
-    in the reference, do not change the upsampling schedule."""
+    in the reference, do not change the upsampling schedule.
+
+    ``enable_backward()`` gives ``forward`` a graph: when gradients are enabled
+    and mel or a parameter requires grad, the audio comes from the exact-fp32
+    per-op path on the module's own parameters (inside an M2TTSModel too: no
+    handle, the stand-alone module's bits) and carries a ``grad_fn`` whose
+    backward fills the 28 ``.grad`` and ``mel.grad`` on the GPU.  Off by
+    default; with it off, under ``no_grad`` or with nothing requiring grad,
+    ``forward`` is unchanged."""
+
+    backward_enabled = False
 
     def __init__(self, mel_channels: int = 64, hidden_channels: int = 128, kernel_size: int = 3, n_layers: int = 4):
         super().__init__()
@@ -165,7 +197,21 @@ class SimpleVocoder(nn.Module):
         self.output_conv = nn.Conv1d(ch, 1, kernel_size, padding=kernel_size // 2)
         self.apply(initialize_weights)
 
+    def enable_backward(self, enabled: bool = True) -> "SimpleVocoder":
+        """Switch the graph of ``forward`` on or off (a plain attribute, no
+        state_dict entry); kernel size 3 only."""
+        if enabled and self.input_conv.kernel_size[0] != 3:
+            raise NotImplementedError(f"SimpleVocoder.enable_backward: kernel_size 3 only, got "
+                                      f"{self.input_conv.kernel_size[0]}")
+        self.backward_enabled = bool(enabled)
+        return self
+
     def forward(self, mel: Tensor) -> Tensor:
+        if self.backward_enabled and torch.is_grad_enabled():
+            params = list(self.parameters())
+            if mel.requires_grad or any(p.requires_grad for p in params):
+                ops.require_device(mel, *params, what="SimpleVocoder")
+                return _VocoderGrad.apply(mel, *params)
         hm = _owner_handle(self, "vocoder", mel.device)
         if hm is not None:
             return hm.vocoder(mel, layout_btm=False)

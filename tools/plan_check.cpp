@@ -17,6 +17,9 @@
 // calls' sizes and workspace layout against the formulas they replaced, and the
 // backward kernels' launch plans against their limits, and the spectral backward's
 // workspace carve against its frame count.
+// The vocoder's gradient plan (csrc/vocoder_grad_plan.h) runs here too: the tape and the backward's
+// workspace against a plain restatement of their formulas, the carved regions against each other,
+// and every launch row against the LDS and grid limits.
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -27,6 +30,7 @@
 
 #include "losses_plan.h"
 #include "m2_model.h"
+#include "vocoder_grad_plan.h"
 #include "vocoder_launch.h"
 #include "vocoder_pipe.h"
 
@@ -702,12 +706,131 @@ static void check_spectral_bwd() {
     std::printf(" (%d carved)\n", carved);
 }
 
+// The vocoder's gradient plan over C x T x B.  Restated plainly: the tape is h [C, T], three maps
+// [C / 2^(k+1), T x 4, 16, 32, 64] per stage and the audio [1, 64 T], B of each, every map on a 256-byte
+// boundary; the workspace is three buffers of B x the widest map, the partials of the widest
+// reduction, and one weight and one bias of the largest size.  A Carve over exactly the Sizer's bytes succeeds and one byte fewer is refused; the
+// carved regions are in order and disjoint; every row fits 48 KiB of LDS and the grid limits.
+static void check_vocoder_grad() {
+    int bad = 0, plans = 0, rows_seen = 0, narrow = 0;
+    const int rates[4] = {4, 4, 2, 2};
+    for (const int C : {16, 32, 128, 256})
+        for (const int T : {1, 17, 70, 500})
+            for (const int B : {1, 3, 32}) {
+                const vgrad::Dims d{C == 256 ? 80 : C == 32 ? 5 : 64, C, B, T};
+                bad += !vgrad::dims_ok(d);
+                ++plans;
+                // the tape
+                size_t off = 0, widest = (size_t)C * T;
+                std::vector<size_t> at, len;
+                auto put = [&](size_t floats) {
+                    off = (off + 255) / 256 * 256;
+                    at.push_back(off);
+                    len.push_back(floats * 4);
+                    off += floats * 4;
+                };
+                put((size_t)B * C * T);
+                int L = T;
+                for (int k = 0; k < 4; ++k) {
+                    L *= rates[k];
+                    const size_t n = (size_t)(C >> (k + 1)) * L;
+                    widest = std::max(widest, n);
+                    for (int j = 0; j < 3; ++j) put((size_t)B * n);
+                }
+                put((size_t)B * 64 * T);
+                Sizer ts;
+                vgrad::carve_tape(ts, d, nullptr);
+                bad += ts.off != off || at.size() != (size_t)vgrad::kMaps;
+                std::vector<char> mem(off);
+                Carve tc(mem.data(), mem.size()), less(mem.data(), mem.size() - 1);
+                float *maps[vgrad::kMaps], *none[vgrad::kMaps];
+                vgrad::carve_tape(tc, d, maps);
+                vgrad::carve_tape(less, d, none);
+                bad += !tc.ok || less.ok;
+                for (int i = 0; i < vgrad::kMaps && tc.ok; ++i) {
+                    bad += reinterpret_cast<char*>(maps[i]) != mem.data() + at[i];
+                    if (i > 0) bad += at[i] < at[i - 1] + len[i - 1];  // no overlap
+                    int c, n;
+                    vgrad::map_shape(d, i, &c, &n);
+                    bad += (size_t)B * c * n * 4 != len[i];
+                }
+                // the workspace
+                size_t part = (size_t)B * ((64 * T + 1023) / 1024) * (3 * (size_t)(C >> 4) + 1);
+                for (const vgrad::Step& s : vgrad::plan_steps(d)) {
+                    if (s.kind != vgrad::STEP_WGRAD && s.kind != vgrad::STEP_IN) continue;
+                    const size_t n = (size_t)s.g.Cout * s.g.Cin * s.g.k;
+                    const int Lo = loss::conv_out_len(s.L, s.g);
+                    size_t want;
+                    if (s.g.Cout < 16) {
+                        const long long chunks = (long long)B * ((Lo + 255) / 256);
+                        const long long cps = (chunks + std::min<long long>(chunks, 512) - 1) / std::min<long long>(chunks, 512);
+                        want = (size_t)((chunks + cps - 1) / cps) * (n + s.g.Cout);
+                        bad += !s.narrow;
+                        ++narrow;
+                    } else {
+                        const long long chunks = (long long)B * ((Lo + 63) / 64);
+                        want = (size_t)std::max<long long>(1, std::min<long long>({chunks, 64, (long long)(1 + (8u << 20) / n)})) * n;
+                        bad += s.narrow || !loss::dw_plan(s.g, B, s.L).mfma;
+                    }
+                    bad += vgrad::step_part_floats(s, B) != want;
+                    part = std::max(part, want);
+                }
+                bad += vgrad::part_floats(d) != part || vgrad::widest_map(d) != widest;
+                size_t woff = 0;
+                const size_t weight = std::max((size_t)3 * C * d.M, (size_t)4 * C * C);  // the input conv, or ConvT_0
+                bad += vgrad::widest_weight(d) != weight || vgrad::widest_bias(d) != (size_t)C;
+                for (const size_t floats : {B * widest, B * widest, B * widest, part, weight, (size_t)C}) woff = (woff + 255) / 256 * 256 + floats * 4;
+                Sizer ws;
+                vgrad::carve_backward(ws, d, nullptr);
+                bad += ws.off != woff;
+                if (woff <= ((size_t)160 << 20)) {
+                    std::vector<char> wm(woff);
+                    Carve wc(wm.data(), wm.size()), wless(wm.data(), wm.size() - 1);
+                    vgrad::Bufs b{}, nb{};
+                    vgrad::carve_backward(wc, d, &b);
+                    vgrad::carve_backward(wless, d, &nb);
+                    bad += !wc.ok || wless.ok;
+                    const char* p[7] = {reinterpret_cast<char*>(b.cot[0]), reinterpret_cast<char*>(b.cot[1]),
+                                        reinterpret_cast<char*>(b.gv), reinterpret_cast<char*>(b.part),
+                                        reinterpret_cast<char*>(b.wtmp), reinterpret_cast<char*>(b.btmp),
+                                        wm.data() + wm.size()};
+                    const size_t bytes[6] = {B * widest * 4, B * widest * 4, B * widest * 4, part * 4, weight * 4,
+                                             (size_t)C * 4};
+                    bad += p[0] != wm.data();
+                    for (int i = 0; i < 5; ++i) bad += p[i + 1] < p[i] + bytes[i];  // no overlap
+                    bad += p[6] != p[5] + bytes[5];
+                }
+                // the rows
+                for (const vgrad::Step& s : vgrad::plan_steps(d)) {
+                    std::vector<loss::LaunchRow> rows;
+                    vgrad::step_rows(s, B, true, s.dw >= 0, s.db >= 0, rows);
+                    bad += rows.empty();
+                    for (const loss::LaunchRow& r : rows) {
+                        ++rows_seen;
+                        bad += r.lds > (size_t)loss::kMaxLds || r.gx < 1 || r.gy < 1 || r.gz < 1 || r.gy > 65535 ||
+                               r.gz > 65535 || (r.threads != 256 && r.threads != loss::kDbThreads);
+                        if (C >= 128 && B * T >= 500)
+                            bad += !std::strcmp(r.kernel, "conv_dw_direct_kernel") ||
+                                   !std::strcmp(r.kernel, "conv_dx_direct_kernel");
+                    }
+                }
+                bad += vgrad::print_plan(d).find("out:voc_out_bwd_kernel[grid=") == std::string::npos;
+            }
+    for (const int c : {1, 2, 8, 16, 64, 128}) bad += vgrad::res_width(c) < 32 || vgrad::res_lds_bytes(c) > (size_t)loss::kMaxLds;
+    bad += vgrad::dims_ok(vgrad::Dims{64, 120, 1, 4}) || vgrad::dims_ok(vgrad::Dims{64, 512, 1, 4}) ||
+           vgrad::dims_ok(vgrad::Dims{0, 128, 1, 4});
+    std::printf("vocoder_grad:");
+    expect("plans_match", bad == 0 && plans == 48 && narrow > 0, true);
+    std::printf(" (%d plans, %d rows)\n", plans, rows_seen);
+}
+
 int main() {
     check_strips();
     check_launch_plans();
     check_disc_plans();
     check_geometries();
     check_spectral_bwd();
+    check_vocoder_grad();
     const m2_config stage1{256, 64, 64, 2, 2, 2, 128, 1000}, stage2{256, 96, 80, 3, 3, 2, 256, 1000};
     for (const bool huge : {false, true}) {
         check(2 * huge, "stage1", stage1, huge);

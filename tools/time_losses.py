@@ -23,7 +23,13 @@ audio gradient kernel summed over the three scales.  The spectral switch
 (generator_spectral_step_ms, against generator_step_ms), and the three
 m2_loss_spectral_backward calls of the default weights on their own
 (spectral_backward_ms, against spectral_and_perceptual_ms:
-spectral_backward_over_forward).  Each
+spectral_backward_over_forward).  The vocoder's training side (DESIGN 4.6d,
+stage1 vocoder, --frames frames): m2_vocoder_train_forward
+(vocoder_train_forward_ms), m2_vocoder_backward with every parameter gradient
+(vocoder_backward_ms, against the forward: vocoder_backward_over_forward), and
+the generator-mode call on audio_pred = vocoder(mel) with total_loss.backward()
+reaching the vocoder's parameters (gen_step_vocoder_ms; only when --length is
+64 x --frames).  Each
 figure is the median of --iters timed calls after --warmup untimed ones.
 """
 import argparse
@@ -161,6 +167,31 @@ def main():
         both_ms = timed(lambda: ops.conv1d_strided_backward(x, w, dy, need_dx=True, **geo), args.warmup, args.iters)
         for key, t in (("weight_gradient", dw_ms), ("data_gradient", both_ms - dw_ms)):
             out[name][key] = {"ms": t, "fraction_of_f32_mfma_peak": flop / (t * 1e-3) / PEAK_F32_MFMA}
+    # the vocoder's training forward and backward on the stage1 vocoder, and the generator-mode
+    # call with total_loss.backward() reaching the vocoder's parameters through audio_pred = vocoder(mel)
+    from models.tts_model import SimpleVocoder
+    voc = SimpleVocoder(mel_channels=M).to(dev).enable_backward()
+    vparams = [p.detach() for p in voc.parameters()]
+    vmel = torch.randn(B, M, T, device=dev)
+    _, tape = ops.vocoder_train_forward(vparams, vmel)
+    d_audio = torch.randn(B, 1, 64 * T, device=dev)
+    out["vocoder_train_forward_ms"] = timed(lambda: ops.vocoder_train_forward(vparams, vmel), args.warmup, args.iters)
+    out["vocoder_backward_ms"] = timed(lambda: ops.vocoder_backward(vparams, vmel, tape, d_audio, need_mel=False),
+                                       args.warmup, args.iters)
+    out["vocoder_backward_over_forward"] = out["vocoder_backward_ms"] / out["vocoder_train_forward_ms"]
+    if L == 64 * T:
+        loss.enable_backward(spectral=True)
+        kv = {k: v for k, v in kg.items() if k != "audio_pred"}  # mel and duration predictions require grad
+
+        def vocoder_step():
+            for p in voc.parameters():
+                p.grad = None
+            for k in ("mel_pred", "duration_pred"):
+                kg[k].grad = None
+            loss(audio_pred=voc(vmel), **kv, optimize_discriminator=False)["total_loss"].backward()
+
+        out["gen_step_vocoder_ms"] = timed(vocoder_step, args.warmup, args.iters)
+        loss.enable_backward(False)
     print(json.dumps(out))
 
 
