@@ -760,6 +760,85 @@ int32_t m2_conv1d_narrow_dw(const float* x, const float* dy, int32_t ksize, int3
                             int32_t Cin, int32_t Cout, int32_t L, float* dw, float* db, void* workspace,
                             size_t workspace_bytes, void* stream);
 
+/* ---- the mel decoder's training forward and backward ----------------------
+ * MelDecoder from its raw parameters (no model handle: an optimizer step
+ * changes every one of them).  params: 11 layers + 4 device pointers in
+ * state_dict order, PyTorch layout, read where they are: per layer
+ * self_attn.qkv.weight [3H,H], self_attn.out_proj.weight [H,H] and .bias,
+ * ffn.linear1.weight [2H,H] and .bias, ffn.linear2.weight [H,2H] and .bias,
+ * norm1.weight, norm1.bias, norm2.weight, norm2.bias; then norm.weight,
+ * norm.bias, mel_projection.weight [M,H] and .bias.  The dimension arguments
+ * are (H, M, layers, heads, B, T); x is [B,T,H], read as R = B T rows.
+ * Supported: H a multiple of 8 with 2 H <= 256, head_dim H / heads in
+ * {16, 32, 48, 64}, M >= 1, layers >= 1 (else M2_E_SHAPE; the _bytes queries
+ * return 0).  B = 0 or T = 0: nothing to do, M2_OK.
+ *
+ * m2_decoder_train_forward: mel [B,T,M], bit-equal to the stand-alone
+ * module's forward (m2_linear with its fused LayerNorm / ReLU / residual and
+ * m2_attention under the process's switches, in that order), each op writing
+ * into the tape: per layer qkv [R,3H], att [R,H], x_mid [R,H], h [R,2H] (stored
+ * post-ReLU) and x_out [R,H], each map on a 256-byte boundary.
+ * m2_decoder_tape_map(index = 5 layer + map) names a map's offset (in floats)
+ * and width.  A tape shorter than m2_decoder_tape_bytes: M2_E_ARG.
+ *
+ * m2_decoder_backward: given d_mel [B,T,M], d_x [B,T,H] (NULL: skipped) and
+ * grads, 11 layers + 4 device pointers shaped like the parameters (a NULL entry
+ * skips that tensor and its launches).  Each is overwritten, or with
+ * accumulate != 0 added to: the gradient's partials are summed exactly as
+ * without it and that sum is added with one fp32 addition per element.  Exact
+ * f32 on v_mfma_f32_16x16x4_f32, no floating-point atomics: equal inputs give
+ * equal bits, and a row of d_x depends on its own utterance only.  LayerNorm
+ * statistics and attention probabilities are recomputed, not taped.  A
+ * workspace shorter than m2_decoder_backward_workspace_bytes: M2_E_ARG.
+ *
+ * m2_debug_decoder_grad_plan: the tape and workspace sizes and every launch of
+ * m2_decoder_backward with all gradients asked for, as one line of text (the
+ * format is fixed and documented in csrc/decoder_grad_plan.h).  Host
+ * arithmetic only.  Writes at most cap bytes (NUL-terminated) and returns the
+ * line's length, or a negative M2_E_* code.
+ *
+ * The kernels alone:
+ * m2_attention_backward: d_qkv [B,N,3H] (overwritten) of att = softmax(Q K^T /
+ *   sqrt(hd), key_mask) V given qkv, att and d_att [B,N,H]; key_mask [B,N]
+ *   (0 = masked; NULL: none).  A masked key's score is replaced, so its dS is 0
+ *   by definition: in a fully masked row dQ and dK are exactly 0 and dV still
+ *   receives P^T dO with P = 1 / N.  The workspace holds the row statistics.
+ * m2_linear_backward_input: g_x [R,K] = g_y [R,N] w [N,K], K a multiple of 8,
+ *   at most 256.  relu_of [R,K] (or NULL): g_x is multiplied by relu_of > 0.
+ *   ln_x [R,K] with gamma [K] (or both NULL; K <= 128; not with relu_of): the
+ *   product is the cotangent of LayerNorm(ln_x) and g_x is the LayerNorm's
+ *   input cotangent plus g_res [R,K] (or NULL); dgamma and dbeta [K] (each may
+ *   be NULL) are overwritten, through the workspace
+ *   (m2_linear_backward_input_workspace_bytes); g_x may then be NULL.
+ * m2_linear_backward_weight: dw [N,K] = g_y^T X and db [N] = sum_r g_y (either
+ *   may be NULL), overwritten; X = x [R,K], or LayerNorm(x; ln_gamma, ln_beta)
+ *   re-formed while loading when those are given. */
+size_t m2_decoder_tape_bytes(int32_t H, int32_t M, int32_t layers, int32_t heads, int32_t B, int32_t T);
+int32_t m2_decoder_tape_map(int32_t H, int32_t M, int32_t layers, int32_t heads, int32_t B, int32_t T, int32_t index,
+                            size_t* offset_floats, int32_t* width);
+int32_t m2_decoder_train_forward(const float* const* params, int32_t H, int32_t M, int32_t layers, int32_t heads,
+                                 const float* x, int32_t B, int32_t T, float* mel, void* tape, size_t tape_bytes,
+                                 void* stream);
+size_t m2_decoder_backward_workspace_bytes(int32_t H, int32_t M, int32_t layers, int32_t heads, int32_t B, int32_t T);
+int32_t m2_decoder_backward(const float* const* params, int32_t H, int32_t M, int32_t layers, int32_t heads,
+                            const float* x, int32_t B, int32_t T, const void* tape, const float* d_mel, float* d_x,
+                            float* const* grads, int32_t accumulate, void* workspace, size_t workspace_bytes,
+                            void* stream);
+int32_t m2_debug_decoder_grad_plan(int32_t H, int32_t M, int32_t layers, int32_t heads, int32_t B, int32_t T, char* out,
+                                   size_t cap);
+size_t m2_attention_backward_workspace_bytes(int32_t B, int32_t N, int32_t heads);
+int32_t m2_attention_backward(const float* qkv, const uint8_t* key_mask, const float* att, const float* d_att,
+                              int32_t B, int32_t N, int32_t H, int32_t heads, float* d_qkv, void* workspace,
+                              size_t workspace_bytes, void* stream);
+size_t m2_linear_backward_input_workspace_bytes(int32_t R, int32_t K);
+int32_t m2_linear_backward_input(const float* g_y, const float* w, const float* relu_of, const float* ln_x,
+                                 const float* gamma, const float* g_res, int32_t R, int32_t K, int32_t N, float* g_x,
+                                 float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, void* stream);
+size_t m2_linear_backward_weight_workspace_bytes(int32_t R, int32_t K, int32_t N);
+int32_t m2_linear_backward_weight(const float* g_y, const float* x, const float* ln_gamma, const float* ln_beta,
+                                  int32_t R, int32_t K, int32_t N, float* dw, float* db, void* workspace,
+                                  size_t workspace_bytes, void* stream);
+
 /* ---- measurement ----------------------------------------------------------
  * Kernel timing with HIP events recorded on the launch stream around each of
  * the fused vocoder's kernels (bench.py's roofline).  enable: allocate event

@@ -139,6 +139,19 @@ _SIGNATURES = {
     "m2_conv1d_narrow_dw_workspace_bytes": (c_size, [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32]),
     "m2_conv1d_narrow_dw": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp,
                                     c_size, c_vp]),
+    "m2_decoder_tape_bytes": (c_size, [c_i32] * 6),
+    "m2_decoder_tape_map": (c_i32, [c_i32] * 7 + [c_vp, c_vp]),
+    "m2_decoder_train_forward": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp, c_size, c_vp]),
+    "m2_decoder_backward_workspace_bytes": (c_size, [c_i32] * 6),
+    "m2_decoder_backward": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32,
+                                    c_vp, c_size, c_vp]),
+    "m2_debug_decoder_grad_plan": (c_i32, [c_i32] * 6 + [c_vp, c_size]),
+    "m2_attention_backward_workspace_bytes": (c_size, [c_i32, c_i32, c_i32]),
+    "m2_attention_backward": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_size, c_vp]),
+    "m2_linear_backward_input_workspace_bytes": (c_size, [c_i32, c_i32]),
+    "m2_linear_backward_input": (c_i32, [c_vp] * 6 + [c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_size, c_vp]),
+    "m2_linear_backward_weight_workspace_bytes": (c_size, [c_i32, c_i32, c_i32]),
+    "m2_linear_backward_weight": (c_i32, [c_vp] * 4 + [c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_size, c_vp]),
     "m2_front_bytes": (c_size, [c_vp, c_i32, c_i32]),
     "m2_inference_workspace_bytes": (c_size, [c_vp, c_i32, c_i32, c_i32]),
     "m2_inference_front": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_vp, c_size, c_vp, c_size, c_vp, c_vp]),

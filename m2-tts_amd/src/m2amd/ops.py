@@ -480,6 +480,168 @@ def conv1d_narrow_dw(x: Tensor, dy: Tensor, ksize: int, *, stride: int = 1, padd
     return dw, db
 
 
+DECODER_LAYER_PARAMS = 11
+DECODER_TAIL_PARAMS = 4
+DECODER_TAPE_NAMES = ("qkv", "att", "x_mid", "h", "x_out")
+
+
+def _decoder_params(params, heads: int):
+    """MelDecoder's 11 layers + 4 parameters (state_dict order) as contiguous float32 device tensors, their
+    pointer array, and the dimensions (H, M, layers, heads)."""
+    keep = [f32c(p.detach()) for p in params]
+    layers, tail = divmod(len(keep) - DECODER_TAIL_PARAMS, DECODER_LAYER_PARAMS)
+    if layers < 1 or tail != 0:
+        raise ValueError(f"decoder: 11 layers + 4 parameters in state_dict order, got {len(keep)}")
+    require_device(*keep, what="decoder parameter")
+    M, H = keep[-2].shape
+    return keep, (ctypes.c_void_p * len(keep))(*[t.data_ptr() for t in keep]), (int(H), int(M), layers, int(heads))
+
+
+def _decoder_x(x: Tensor, H: int) -> Tensor:
+    require_device(x, what="decoder")
+    if x.dim() != 3 or x.shape[2] != H:
+        raise ValueError(f"decoder: x must be [B, T, {H}], got {tuple(x.shape)}")
+    return f32c(x.detach())
+
+
+def decoder_supported(H: int, M: int, layers: int, heads: int) -> bool:
+    """Whether m2_decoder_backward takes a MelDecoder of these dimensions (host arithmetic only)."""
+    return int(_lib.load().m2_decoder_tape_bytes(H, M, layers, heads, 1, 1)) != 0
+
+
+def decoder_train_forward(params, x: Tensor, heads: int):
+    """MelDecoder's forward from its raw parameters, keeping a tape (m2_decoder_train_forward): (mel [B,T,M],
+    bit-equal to the stand-alone module's forward, and the tape, a uint8 tensor that ``decoder_tape_maps``
+    names and ``decoder_backward`` reads)."""
+    keep, ptrs, dims = _decoder_params(params, heads)
+    x = _decoder_x(x, dims[0])
+    B, T, _ = x.shape
+    dev = x.device
+    need = int(_lib.load().m2_decoder_tape_bytes(*dims, B, T))
+    if need == 0:
+        raise M2Error(f"decoder_train_forward: unsupported shape (H, M, layers, heads) = {dims}, B={B} T={T}")
+    tape = torch.empty(need, dtype=torch.uint8, device=dev)
+    mel = torch.empty(B, T, dims[1], device=dev, dtype=torch.float32)
+    _lib.call("m2_decoder_train_forward", ptrs, *dims, _ptr(x), B, T, _ptr(mel), _ptr(tape), tape.numel(),
+              stream_handle(dev))
+    return mel, tape
+
+
+def decoder_tape_maps(tape: Tensor, H: int, M: int, layers: int, heads: int, B: int, T: int) -> list:
+    """The maps of a tape as float32 views (m2_decoder_tape_map): one dict per layer with qkv [B,T,3H],
+    att [B,T,H], x_mid [B,T,H], h [B,T,2H] (post-ReLU) and x_out [B,T,H]."""
+    lib = _lib.load()
+    flat = tape[:tape.numel() // 4 * 4].view(torch.float32)
+    off, width = ctypes.c_size_t(), ctypes.c_int32()
+    out = []
+    for layer in range(layers):
+        maps = {}
+        for i, name in enumerate(DECODER_TAPE_NAMES):
+            _lib.check(lib.m2_decoder_tape_map(H, M, layers, heads, B, T, len(DECODER_TAPE_NAMES) * layer + i,
+                                               ctypes.byref(off), ctypes.byref(width)), "m2_decoder_tape_map")
+            maps[name] = flat[off.value:off.value + B * T * width.value].view(B, T, width.value)
+        out.append(maps)
+    return out
+
+
+def decoder_backward(params, x: Tensor, tape: Tensor, d_mel: Tensor, heads: int, need_x: bool = True, need=None,
+                     accumulate=False):
+    """The gradients of MelDecoder given d_mel [B,T,M] (m2_decoder_backward): (d_x [B,T,H] or None, the
+    11 layers + 4 gradients in state_dict order, None where ``need[i]`` is false).  ``accumulate``: a list of
+    that many tensors (or None entries) to add the gradients to instead of new tensors."""
+    keep, ptrs, dims = _decoder_params(params, heads)
+    x = _decoder_x(x, dims[0])
+    B, T, _ = x.shape
+    dev = x.device
+    require_device(tape, d_mel, what="decoder_backward")
+    d_mel = f32c(d_mel.detach().to(torch.float32))
+    if tuple(d_mel.shape) != (B, T, dims[1]):
+        raise ValueError(f"decoder_backward: d_mel must be {(B, T, dims[1])}, got {tuple(d_mel.shape)}")
+    lib = _lib.load()
+    tape_bytes = int(lib.m2_decoder_tape_bytes(*dims, B, T))
+    if tape_bytes == 0:
+        raise M2Error(f"decoder_backward: unsupported shape (H, M, layers, heads) = {dims}, B={B} T={T}")
+    if tape.numel() < tape_bytes:
+        raise ValueError("decoder_backward: the tape is not that of this shape")
+    onto = accumulate if accumulate else None
+    want = [True] * len(keep) if need is None else [bool(n) for n in need]
+    grads = []
+    for i, (p, w) in enumerate(zip(keep, want)):
+        if not w:
+            grads.append(None)
+        elif onto is not None and onto[i] is not None:
+            grads.append(onto[i])
+        else:
+            grads.append(torch.empty_like(p) if onto is None else torch.zeros_like(p))
+    gp = (ctypes.c_void_p * len(keep))(*[_ptr(g) for g in grads])
+    d_x = torch.empty_like(x) if need_x else None
+    ws = torch.empty(max(int(lib.m2_decoder_backward_workspace_bytes(*dims, B, T)), 1), dtype=torch.uint8, device=dev)
+    _lib.call("m2_decoder_backward", ptrs, *dims, _ptr(x), B, T, _ptr(tape), _ptr(d_mel), _ptr(d_x), gp,
+              0 if onto is None else 1, _ptr(ws), ws.numel(), stream_handle(dev))
+    return d_x, grads
+
+
+def _key_mask(key_mask: Optional[Tensor]) -> Optional[Tensor]:
+    if key_mask is None:
+        return None
+    return key_mask.contiguous() if key_mask.dtype == torch.bool else key_mask.to(torch.uint8).contiguous()
+
+
+def attention_backward(qkv: Tensor, key_mask: Optional[Tensor], att: Tensor, d_att: Tensor, heads: int) -> Tensor:
+    """d_qkv [B,N,3H] of att = attention_core(qkv, heads, key_mask) given d_att [B,N,H]
+    (m2_attention_backward).  A masked key's dS is 0 by definition."""
+    require_device(qkv, att, d_att, key_mask, what="attention_backward")
+    qkv, att, d_att = f32c(qkv), f32c(att), f32c(d_att)
+    B, N, H3 = qkv.shape
+    m = _key_mask(key_mask)
+    d_qkv = torch.empty_like(qkv)
+    ws = torch.empty(max(int(_lib.load().m2_attention_backward_workspace_bytes(B, N, heads)), 1), dtype=torch.uint8,
+                     device=qkv.device)
+    _lib.call("m2_attention_backward", _ptr(qkv), _ptr(m), _ptr(att), _ptr(d_att), B, N, H3 // 3, heads, _ptr(d_qkv),
+              _ptr(ws), ws.numel(), stream_handle(qkv.device))
+    return d_qkv
+
+
+def linear_backward_input(g_y: Tensor, weight: Tensor, *, relu_of: Optional[Tensor] = None, ln_x: Optional[Tensor] = None,
+                          gamma: Optional[Tensor] = None, g_res: Optional[Tensor] = None):
+    """g_x = g_y @ W of y = x @ W^T (m2_linear_backward_input), W [N,K] as stored.  ``relu_of``: times
+    (relu_of > 0).  ``ln_x`` with ``gamma``: the linear consumed LayerNorm(ln_x) and the result is
+    (g_x, dgamma, dbeta), g_x the LayerNorm's input cotangent plus ``g_res``."""
+    require_device(g_y, weight, relu_of, ln_x, gamma, g_res, what="linear_backward_input")
+    g_y, weight = f32c(g_y), f32c(weight)
+    N, K = weight.shape
+    R = g_y.numel() // N
+    dev = g_y.device
+    relu_of, ln_x, gamma, g_res = (None if t is None else f32c(t) for t in (relu_of, ln_x, gamma, g_res))
+    g_x = torch.empty(*g_y.shape[:-1], K, device=dev, dtype=torch.float32)
+    dg = db = None
+    if ln_x is not None:
+        dg, db = torch.empty(K, device=dev, dtype=torch.float32), torch.empty(K, device=dev, dtype=torch.float32)
+    ws = torch.empty(max(int(_lib.load().m2_linear_backward_input_workspace_bytes(R, K)), 1), dtype=torch.uint8,
+                     device=dev)
+    _lib.call("m2_linear_backward_input", _ptr(g_y), _ptr(weight), _ptr(relu_of), _ptr(ln_x), _ptr(gamma), _ptr(g_res),
+              R, K, N, _ptr(g_x), _ptr(dg), _ptr(db), _ptr(ws), ws.numel(), stream_handle(dev))
+    return g_x if ln_x is None else (g_x, dg, db)
+
+
+def linear_backward_weight(g_y: Tensor, x: Tensor, *, ln: Optional[tuple] = None):
+    """(dw [N,K], db [N]) of y = X @ W^T + b given g_y [.., N] (m2_linear_backward_weight); X = x [.., K], or
+    LayerNorm(x; *ln) re-formed on the fly."""
+    require_device(g_y, x, what="linear_backward_weight")
+    g_y, x = f32c(g_y), f32c(x)
+    N, K = g_y.shape[-1], x.shape[-1]
+    R = x.numel() // K
+    dev = x.device
+    g, b_ = (None, None) if ln is None else (f32c(ln[0]), f32c(ln[1]))
+    dw = torch.empty(N, K, device=dev, dtype=torch.float32)
+    db = torch.empty(N, device=dev, dtype=torch.float32)
+    ws = torch.empty(max(int(_lib.load().m2_linear_backward_weight_workspace_bytes(R, K, N)), 1), dtype=torch.uint8,
+                     device=dev)
+    _lib.call("m2_linear_backward_weight", _ptr(g_y), _ptr(x), _ptr(g), _ptr(b_), R, K, N, _ptr(dw), _ptr(db), _ptr(ws),
+              ws.numel(), stream_handle(dev))
+    return dw, db
+
+
 def embed_positional(ids: Tensor, emb: Tensor, pe: Tensor, scale: float) -> Tensor:
     require_device(ids, emb, what="embedding")
     ids = ids.to(torch.int64).contiguous()

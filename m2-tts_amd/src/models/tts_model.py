@@ -122,9 +122,42 @@ class LengthRegulator(nn.Module):
         return ops.regulate(encoder_output, durations, max_length)
 
 
+class _DecoderGrad(torch.autograd.Function):
+    """MelDecoder.forward with a graph: ops.decoder_train_forward on the
+    module's own parameters, and ops.decoder_backward on grad_output (once
+    differentiable).  Arguments: x, the head count, then the 11 layers + 4
+    parameters in state_dict order."""
+
+    @staticmethod
+    def forward(ctx, x, heads, *params):
+        mel, tape = ops.decoder_train_forward(params, x, heads)
+        ctx.save_for_backward(x, *params)
+        ctx.tape, ctx.heads = tape, heads
+        return mel
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        x, *params = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        d_x, grads = ops.decoder_backward(params, x, ctx.tape, grad_output, ctx.heads, need_x=need[0], need=need[2:])
+        return (d_x, None, *grads)
+
+
 class MelDecoder(nn.Module):
     """Unmasked pre-LN transformer over frames -> LayerNorm -> Linear(H, M)
-    (reference tts_model.py:181-228)."""
+    (reference tts_model.py:181-228).
+
+    ``enable_backward()`` gives ``forward`` a graph: when gradients are enabled
+    and x or a parameter requires grad, the mel comes from the per-op path on
+    the module's own parameters (inside an M2TTSModel too: no handle, the
+    stand-alone module's bits) and carries a ``grad_fn`` whose backward fills
+    the 11 layers + 4 ``.grad`` and ``x.grad`` on the GPU.  The gradient is that
+    of the function this module computes: no dropout (models/components.py).
+    Off by default; with it off, under ``no_grad`` or with nothing requiring
+    grad, ``forward`` is unchanged."""
+
+    backward_enabled = False
 
     def __init__(self, hidden_dim: int = 64, mel_channels: int = 64, num_layers: int = 2, num_heads: int = 2,
                  dropout: float = 0.1):
@@ -136,7 +169,34 @@ class MelDecoder(nn.Module):
         self.mel_projection = nn.Linear(hidden_dim, mel_channels)
         self.apply(initialize_weights)
 
+    def _dims(self) -> Tuple[int, int, int, int]:
+        """(H, M, layers, heads)."""
+        m, h = self.mel_projection.weight.shape
+        heads = self.layers[0].self_attn.num_heads if len(self.layers) else 0
+        return int(h), int(m), len(self.layers), int(heads)
+
+    def enable_backward(self, enabled: bool = True) -> "MelDecoder":
+        """Switch the graph of ``forward`` on or off (a plain attribute, no
+        state_dict entry).  Supported: H a multiple of 8 with 2 H <= 256,
+        head_dim in {16, 32, 48, 64}, at least one layer."""
+        if enabled:
+            h, m, layers, heads = self._dims()
+            ok = (layers >= 1 and h % 8 == 0 and 2 * h <= 256 and heads >= 1 and h % heads == 0
+                  and h // heads in (16, 32, 48, 64) and m >= 1
+                  and all(la.ffn.linear1.out_features == 2 * h for la in self.layers))
+            if not ok:
+                raise NotImplementedError(f"MelDecoder.enable_backward: hidden_dim a multiple of 8 up to 128, head_dim "
+                                          f"16, 32, 48 or 64 and at least one layer; got hidden_dim {h}, "
+                                          f"{heads} heads, {layers} layers")
+        self.backward_enabled = bool(enabled)
+        return self
+
     def forward(self, x: Tensor) -> Tensor:
+        if self.backward_enabled and torch.is_grad_enabled():
+            params = list(self.parameters())
+            if x.requires_grad or any(p.requires_grad for p in params):
+                ops.require_device(x, *params, what="MelDecoder")
+                return _DecoderGrad.apply(x, self._dims()[3], *params)
         hm = _owner_handle(self, "decoder", x.device)
         if hm is not None:
             return hm.decoder(x)

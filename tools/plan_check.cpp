@@ -17,6 +17,7 @@
 // calls' sizes and workspace layout against the formulas they replaced, and the
 // backward kernels' launch plans against their limits, and the spectral backward's
 // workspace carve against its frame count.
+// The decoder's gradient plan (csrc/decoder_grad_plan.h) is checked the same way (check_decoder_grad).
 // The vocoder's gradient plan (csrc/vocoder_grad_plan.h) runs here too: the tape and the backward's
 // workspace against a plain restatement of their formulas, the carved regions against each other,
 // and every launch row against the LDS and grid limits.
@@ -30,6 +31,7 @@
 
 #include "losses_plan.h"
 #include "m2_model.h"
+#include "decoder_grad_plan.h"
 #include "vocoder_grad_plan.h"
 #include "vocoder_launch.h"
 #include "vocoder_pipe.h"
@@ -824,6 +826,106 @@ static void check_vocoder_grad() {
     std::printf(" (%d plans, %d rows)\n", plans, rows_seen);
 }
 
+// The decoder's gradient plan (csrc/decoder_grad_plan.h) over the stage1 and stage2 training shapes and a
+// few small ones.  Restated plainly: the tape is five maps [R, 3H | H | H | 2H | H] per layer, each on a
+// 256-byte boundary; the workspace is two maps [R, H], one [R, 3H], the statistics [B, heads, T, 3] and
+// the partials of the widest reduction.  A Carve over exactly the Sizer's bytes succeeds and one byte
+// fewer is refused; the carved regions are in order and disjoint; every row fits 48 KiB of LDS and the
+// grid limits; every weight gradient's partials fit `part`.
+static void check_decoder_grad() {
+    int bad = 0, plans = 0, rows_seen = 0;
+    const int shapes[][6] = {{64, 64, 2, 2, 32, 500}, {96, 80, 3, 2, 8, 500}, {32, 5, 1, 2, 3, 1},
+                             {128, 80, 1, 2, 1, 65},  {64, 64, 1, 4, 2, 33},  {64, 64, 2, 2, 1, 1}};
+    for (const auto& sh : shapes) {
+        const dgrad::Dims d{sh[0], sh[1], sh[2], sh[3], sh[4], sh[5]};
+        bad += !dgrad::dims_ok(d);
+        ++plans;
+        const size_t R = (size_t)d.B * d.T, H = (size_t)d.H;
+        // the tape
+        size_t off = 0;
+        std::vector<size_t> at, len;
+        auto put = [&](size_t floats) {
+            off = (off + 255) / 256 * 256;
+            at.push_back(off);
+            len.push_back(floats * 4);
+            off += floats * 4;
+        };
+        for (int l = 0; l < d.layers; ++l)
+            for (const size_t w : {3 * H, H, H, 2 * H, H}) put(R * w);
+        Sizer ts;
+        dgrad::carve_tape(ts, d, nullptr);
+        bad += ts.off != off || at.size() != (size_t)dgrad::n_maps(d);
+        std::vector<char> mem(off);
+        Carve tc(mem.data(), mem.size()), less(mem.data(), mem.size() - 1);
+        std::vector<float*> maps(at.size()), none(at.size());
+        dgrad::carve_tape(tc, d, maps.data());
+        dgrad::carve_tape(less, d, none.data());
+        bad += !tc.ok || less.ok;
+        for (size_t i = 0; i < at.size() && tc.ok; ++i) {
+            bad += reinterpret_cast<char*>(maps[i]) != mem.data() + at[i];
+            if (i > 0) bad += at[i] < at[i - 1] + len[i - 1];  // no overlap
+            bad += R * dgrad::map_width(d, (int)i) * 4 != len[i];
+        }
+        // the workspace
+        size_t part = (R + 63) / 64 * 2 * H;
+        for (const dgrad::Step& s : dgrad::plan_steps(d)) {
+            if (s.kind != dgrad::STEP_DW) continue;
+            const long long tiles = (s.N + 63) / 64, chunks = (long long)((R + 31) / 32);
+            const long long want = std::max<long long>(1, std::min<long long>(chunks, (256 + tiles - 1) / tiles));
+            const long long rps = (chunks + want - 1) / want * 32, splits = ((long long)R + rps - 1) / rps;
+            const size_t need = (size_t)splits * ((size_t)s.N * s.K + s.N);
+            bad += dgrad::step_part_floats(s, d) != need || splits < 1 || splits > 256 || rps * splits < (long long)R;
+            part = std::max(part, need);
+        }
+        bad += dgrad::part_floats(d) != part;
+        size_t woff = 0;
+        const size_t floats[5] = {R * H, R * H, R * 3 * H, (size_t)d.B * d.heads * d.T * 3, part};
+        for (const size_t f : floats) woff = (woff + 255) / 256 * 256 + f * 4;
+        Sizer ws;
+        dgrad::carve_backward(ws, d, nullptr);
+        bad += ws.off != woff;
+        {
+            std::vector<char> wm(woff);
+            Carve wc(wm.data(), wm.size()), wless(wm.data(), wm.size() - 1);
+            dgrad::Bufs b{}, nb{};
+            dgrad::carve_backward(wc, d, &b);
+            dgrad::carve_backward(wless, d, &nb);
+            bad += !wc.ok || wless.ok;
+            const char* p[6] = {reinterpret_cast<char*>(b.cot[0]), reinterpret_cast<char*>(b.cot[1]),
+                                reinterpret_cast<char*>(b.wide),   reinterpret_cast<char*>(b.stats),
+                                reinterpret_cast<char*>(b.part),   wm.data() + wm.size()};
+            bad += p[0] != wm.data();
+            for (int i = 0; i < 4; ++i) bad += p[i + 1] < p[i] + floats[i] * 4;  // no overlap
+            bad += p[5] != p[4] + floats[4] * 4;
+        }
+        // the rows
+        int steps = 0;
+        for (const dgrad::Step& s : dgrad::plan_steps(d)) {
+            ++steps;
+            std::vector<loss::LaunchRow> rows;
+            const bool ln = s.kind == dgrad::STEP_DX && s.mode == dgrad::DX_LN;
+            dgrad::step_rows(s, d, true, s.kind == dgrad::STEP_DW ? s.dw >= 0 : ln,
+                             s.kind == dgrad::STEP_DW ? s.db >= 0 : ln, rows);
+            bad += rows.empty();
+            if (s.kind == dgrad::STEP_DX) bad += !dgrad::dx_ok(s.K, s.N, s.mode);
+            if (s.kind == dgrad::STEP_DW) bad += !dgrad::dw_ok(s.K, s.N);
+            for (const loss::LaunchRow& r : rows) {
+                ++rows_seen;
+                bad += r.lds > (size_t)loss::kMaxLds || r.gx < 1 || r.gy < 1 || r.gz < 1 || r.gy > 65535 ||
+                       r.gz > 65535 || r.threads != 256;
+            }
+        }
+        bad += steps != 2 + 9 * d.layers;
+        bad += dgrad::print_plan(d).find(" mw:lin_dw_kernel[grid=") == std::string::npos;
+    }
+    bad += dgrad::dims_ok(dgrad::Dims{60, 64, 2, 2, 1, 4}) || dgrad::dims_ok(dgrad::Dims{160, 64, 2, 4, 1, 4}) ||
+           dgrad::dims_ok(dgrad::Dims{64, 64, 2, 8, 1, 4}) || dgrad::dims_ok(dgrad::Dims{64, 0, 2, 2, 1, 4}) ||
+           dgrad::dims_ok(dgrad::Dims{64, 64, 0, 2, 1, 4});
+    std::printf("decoder_grad:");
+    expect("plans_match", bad == 0 && plans == 6, true);
+    std::printf(" (%d plans, %d rows)\n", plans, rows_seen);
+}
+
 int main() {
     check_strips();
     check_launch_plans();
@@ -831,6 +933,7 @@ int main() {
     check_geometries();
     check_spectral_bwd();
     check_vocoder_grad();
+    check_decoder_grad();
     const m2_config stage1{256, 64, 64, 2, 2, 2, 128, 1000}, stage2{256, 96, 80, 3, 3, 2, 256, 1000};
     for (const bool huge : {false, true}) {
         check(2 * huge, "stage1", stage1, huge);

@@ -29,7 +29,13 @@ stage1 vocoder, --frames frames): m2_vocoder_train_forward
 (vocoder_backward_ms, against the forward: vocoder_backward_over_forward), and
 the generator-mode call on audio_pred = vocoder(mel) with total_loss.backward()
 reaching the vocoder's parameters (gen_step_vocoder_ms; only when --length is
-64 x --frames).  Each
+64 x --frames).  The mel decoder's training side (--hidden,
+--dec-layers, --heads, default the stage1 decoder): m2_decoder_train_forward
+(decoder_train_forward_ms), m2_decoder_backward with every gradient and d_x
+(decoder_backward_ms, decoder_backward_over_forward), and the same generator
+step with mel = decoder(x) feeding both the mel loss and the vocoder
+(gen_step_decoder_ms, under gen_step_vocoder_ms's condition).  --decoder-only
+prints the two decoder lines alone (for a kernel trace).  Each
 figure is the median of --iters timed calls after --warmup untimed ones.
 """
 import argparse
@@ -61,6 +67,24 @@ def timed(fn, warmup, iters):
     return statistics.median(ms)
 
 
+def decoder_lines(out, args, dev):
+    """The mel decoder's training forward and backward; returns the module, its input and its
+    parameters."""
+    from m2amd import ops
+    from models.tts_model import MelDecoder
+    dec = MelDecoder(args.hidden, args.mels, args.dec_layers, args.heads).to(dev).enable_backward()
+    params = [p.detach() for p in dec.parameters()]
+    x = torch.randn(args.batch, args.frames, args.hidden, device=dev)
+    _, tape = ops.decoder_train_forward(params, x, args.heads)
+    d_mel = torch.randn(args.batch, args.frames, args.mels, device=dev)
+    out["decoder_train_forward_ms"] = timed(lambda: ops.decoder_train_forward(params, x, args.heads), args.warmup,
+                                            args.iters)
+    out["decoder_backward_ms"] = timed(lambda: ops.decoder_backward(params, x, tape, d_mel, args.heads), args.warmup,
+                                       args.iters)
+    out["decoder_backward_over_forward"] = out["decoder_backward_ms"] / out["decoder_train_forward_ms"]
+    return dec, x
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
@@ -68,6 +92,10 @@ def main():
     ap.add_argument("--frames", type=int, default=500)
     ap.add_argument("--mels", type=int, default=64)
     ap.add_argument("--phonemes", type=int, default=100)
+    ap.add_argument("--hidden", type=int, default=64)
+    ap.add_argument("--dec-layers", type=int, default=2)
+    ap.add_argument("--heads", type=int, default=2)
+    ap.add_argument("--decoder-only", action="store_true")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--iters", type=int, default=10)
     args = ap.parse_args()
@@ -75,6 +103,12 @@ def main():
     from training.losses import CombinedTTSLoss
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
+    if args.decoder_only:
+        out = {"batch": args.batch, "frames": args.frames, "mels": args.mels, "hidden": args.hidden,
+               "dec_layers": args.dec_layers, "heads": args.heads, "iters": args.iters}
+        decoder_lines(out, args, dev)
+        print(json.dumps(out))
+        return
     loss = CombinedTTSLoss().eval().to(dev)
     B, L, T, M, S = args.batch, args.length, args.frames, args.mels, args.phonemes
     kw = dict(mel_pred=torch.randn(B, T, M, device=dev), mel_target=torch.randn(B, M, T, device=dev),
@@ -191,6 +225,21 @@ def main():
             loss(audio_pred=voc(vmel), **kv, optimize_discriminator=False)["total_loss"].backward()
 
         out["gen_step_vocoder_ms"] = timed(vocoder_step, args.warmup, args.iters)
+        loss.enable_backward(False)
+    dec, dx = decoder_lines(out, args, dev)
+    if L == 64 * T:
+        loss.enable_backward(spectral=True)
+        kd = {k: v for k, v in kg.items() if k not in ("audio_pred", "mel_pred")}
+        dx.requires_grad_()
+
+        def decoder_step():
+            for p in list(voc.parameters()) + list(dec.parameters()) + [dx, kg["duration_pred"]]:
+                p.grad = None
+            mel = dec(dx)
+            loss(mel_pred=mel, audio_pred=voc(mel.transpose(1, 2)), **kd,
+                 optimize_discriminator=False)["total_loss"].backward()
+
+        out["gen_step_decoder_ms"] = timed(decoder_step, args.warmup, args.iters)
         loss.enable_backward(False)
     print(json.dumps(out))
 
