@@ -54,6 +54,8 @@ struct Switches {
     bool tailp2_seven = false;  // M2_TAILP2_SEVEN
     bool head_inconv = false;   // M2_HEAD_INCONV
     bool headmid = true;        // M2_HEADMID=0|1: the stage1 head and mid in one launch (headmid_kernel, vocoder_x3.hip)
+    bool head_items = true;     // M2_HEAD_ITEMS=0|1: ResBlock1's items of the 16-wave planar head m-block-major (1: the
+                                // four waves of an m-block on four SIMDs) or plane-major (0), head_rb1_planar
     int s2_mid_alt = -1;        // M2_S2_MID_ALT=0|1: the 30- / 33-position stage2 mid (-1: by grid)
     int s2_head_tf = 0;         // M2_S2_HEAD_TF=16|19|24|27 (M2_S2_HEAD_TF16: 16)
     int redo_grid = -1;         // M2_REDO_GRID: workgroups of the guarded redo launch (-1: one per CU)
@@ -113,6 +115,25 @@ __device__ __forceinline__ float act_t(float v) {
 __device__ __forceinline__ int dev_frames(const int32_t* p, int cap) {
     const int t = max(1, *p);
     return t <= cap ? t : 0;
+}
+
+// A 16-byte vector store to base + off (base wave-uniform, off this lane's
+// byte offset, below 4 GB) under a cache policy: 0 plain, 1 write-through
+// (sc1: the line does not stay dirty in the XCD's L2), 2 non-temporal (nt).
+// The users pick the policy with a build define (an A/B, profiles/r15/).
+// 1 and 2 go through a raw buffer store, whose cache bits the compiler knows
+// (aux 16 = sc1, 2 = nt).
+template <int POLICY, class V>
+__device__ __forceinline__ void gstore16(void* base, size_t off, const V& v) {
+    static_assert(sizeof(V) == 16 && POLICY >= 0 && POLICY <= 2, "16-B vectors; policy 0, 1 or 2");
+    if constexpr (POLICY == 0) {
+        *reinterpret_cast<V*>(static_cast<unsigned char*>(base) + off) = v;
+    } else {
+        typedef unsigned gs_u32x4 __attribute__((ext_vector_type(4)));
+        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(base, 0, -1, 0x00020000);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(gs_u32x4, v), rsrc, (int)off, 0,
+                                               POLICY == 1 ? 16 : 2);
+    }
 }
 
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }

@@ -91,6 +91,7 @@ void reload_switches() {
     s.head_inconv = env_set("M2_HEAD_INCONV");
     // "0" or "1"; anything else keeps the default (m2amd.runtime.headmid_switch rejects it at handle creation)
     if (const char* e = std::getenv("M2_HEADMID"); e && (e[0] == '0' || e[0] == '1') && !e[1]) s.headmid = e[0] == '1';
+    s.head_items = env_int("M2_HEAD_ITEMS", 1) != 0;
     const int malt = env_int("M2_S2_MID_ALT", -1);
     s.s2_mid_alt = (malt == 0 || malt == 1) ? malt : -1;
     const int htf = env_int("M2_S2_HEAD_TF", env_set("M2_S2_HEAD_TF16") ? 16 : 0);

@@ -14,6 +14,16 @@ namespace mp {
 
 using namespace pipe;  // vector types, mfma_h, step_barrier
 
+// Cache policy of conv2's U2 stores (gstore16, m2_common.h; a build define
+// for the A/B): write-through.  U2 (32.8 MB at B=32, T=500) is read by the
+// next launch, mostly from another XCD; plain stores left it dirty in the
+// writing XCD's L2 for the launch boundary to write back.  Write-through
+// measured 3.4 us per call faster than plain at that shape (non-temporal
+// 2.9), in every alternation pair (profiles/r15/r15_store_ab.txt).
+#ifndef M2_U2_STORE
+#define M2_U2_STORE 1
+#endif
+
 constexpr int RROWS = 64;               // 4 chunks of 16 columns
 constexpr int RS0 = 288;                // R0 row: 256 B (hi[64] lo[64]) + pad, RS/16 = 2 mod 4
 constexpr int RS1 = 544;                // R1/R2 row: 512 B (hi[128] lo[128]) + pad
@@ -56,12 +66,24 @@ __device__ __forceinline__ unsigned r12_at(int row, int u) { return row * RS1 + 
 // the chunk's parity, which is the ring phase's (j = k mod 4 at layer 0).
 // xown: conv2 stores the columns below it (the strip's owned columns end
 // there, or the utterance does).
-template <int L, int S, class Lay = RingLay, int HB = 0, int NH = 2>
+// PRE, pre (headmid_kernel): the role's first kPre k-blocks of weight fragments
+// in the order the role holds them (its units are consecutive), whose loads
+// the caller issued earlier from role_wp; the role fetches the rest.
+// Else (midp_kernel): the role fetches all of them when it starts.
+constexpr int kPre = 4;
+// this lane's slot of the first unit of the role of wave wv (wv < 12: layer wv / 4, phase wv % 4)
+__device__ __forceinline__ const u32x4* role_wp(const u32x4* __restrict__ W, int wv) {
+    const int l = wv >> 2, s = wv & 3;
+    return W + (size_t)(munit0(l) + 2 * s * mkb(l)) * 128 + (threadIdx.x & 63);
+}
+template <int L, int S, class Lay = RingLay, int HB = 0, int NH = 2, bool PRE = false>
 __device__ __forceinline__ void layer_role(unsigned char* lds, int qa, int L1, int nch, bool edge,
                                            const u32x4* __restrict__ W, const float* __restrict__ bias,
-                                           unsigned char* __restrict__ u2row, int xown) {
+                                           unsigned char* __restrict__ u2row, int xown,
+                                           const u32x4 (*pre)[1][2] = nullptr) {
     constexpr int NKB = mkb(L);
     constexpr bool PL = L == 0 && Lay::PLANES;
+    static_assert(NH * NKB >= kPre, "a role holds at least the handed-over k-blocks");
     constexpr int IN_OFF = L == 0 ? Lay::R0_OFF : (L == 1 ? Lay::R1_OFF : Lay::R2_OFF);
     constexpr int LO_IN = L == 0 ? 128 : 256;           // lo half offset in an input row
     const int lane = threadIdx.x & 63, li = lane & 15, g = lane >> 4;
@@ -73,8 +95,13 @@ __device__ __forceinline__ void layer_role(unsigned char* lds, int qa, int L1, i
 #pragma unroll
         for (int kb = 0; kb < NKB; ++kb) {
             const int u = munit0(L) + (2 * S + h) * NKB + kb;
-            a[hh][kb][0] = W[u * 128 + lane];
-            a[hh][kb][1] = W[u * 128 + 64 + lane];
+            if (PRE && hh * NKB + kb < kPre) {
+                a[hh][kb][0] = pre[hh * NKB + kb][0][0];
+                a[hh][kb][1] = pre[hh * NKB + kb][0][1];
+            } else {
+                a[hh][kb][0] = W[u * 128 + lane];
+                a[hh][kb][1] = W[u * 128 + 64 + lane];
+            }
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) bv[hh][r] = bias[L * 128 + 32 * S + 16 * h + 4 * g + r];
@@ -167,8 +194,8 @@ __device__ __forceinline__ void layer_role(unsigned char* lds, int qa, int L1, i
             } else {
                 const int x = x0 + li;
                 if (k >= 0 && x >= 0 && x < xown)  // U2 row of position 4x + S
-                    *reinterpret_cast<u32x4*>(u2row + ((size_t)4 * x + S) * 128 + 32 * h + 64 * (g & 1) +
-                                              16 * (g >> 1)) = val;
+                    gstore16<M2_U2_STORE>(u2row, ((size_t)4 * x + S) * 128 + 32 * h + 64 * (g & 1) + 16 * (g >> 1),
+                                          val);
             }
         }
     };

@@ -678,15 +678,27 @@ __device__ __forceinline__ void head_convT1c_planar(const u32x4* __restrict__ Wp
 // of its four channels before the permlane16 swap and writes, after it, 16 B
 // of the same row and m-block, which only this wave touches.  rot: plane p
 // holds positions 4 q + p + rot (head_convT1c_planar).
+// Item map (wave-uniform; M2_HEAD_ITEMS, default 1 = mbmajor): the weights do
+// not depend on the plane, so the four waves of an m-block load the same
+// fragments.  mbmajor: they are waves 4 mb .. 4 mb + 3, one on every SIMD and
+// of one age, so their loads meet in L1; else (the ConvT1 map, whose
+// fragments are all distinct) waves mb, mb + 4, .. of one SIMD, which run by
+// age, far apart in time, and each fetch their own copy from L2.  The sums of
+// an item and their order are the same under both maps.
+template <int MB>
+__device__ __forceinline__ int rb1_mb(int wv, bool mbmajor) {
+    return mbmajor ? wv / 4 : wv % MB;
+}
 template <int C, int RS, bool CONV2, bool INPL = false>
 __device__ __forceinline__ void head_rb1_planar(const u32x4* __restrict__ Wp, const float* __restrict__ bias,
                                                 const unsigned char* in, unsigned char* out,
                                                 const unsigned char* x, int f0, int tf, int L, APipe* ap,
-                                                const u32x4* wp_next, unsigned char* gout, int rot = 0) {
+                                                const u32x4* wp_next, unsigned char* gout, int rot = 0,
+                                                bool mbmajor = false) {
     constexpr int MB = C / 16, NKB = nkb_of<C, 3>(), NT = 4;
     static_assert(CONV2 || !INPL, "in place: conv2 only");
     const int item = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int p = item / MB, mb = item - p * MB;
+    const int p = mbmajor ? item % 4 : item / MB, mb = rb1_mb<MB>(item, mbmajor);
     const int lane = threadIdx.x & 63, li = lane & 15, g = lane >> 4, co0 = mb * 16 + 4 * g;
     const int qo = CONV2 ? f0 : qs_h(p, f0);
     const unsigned char* tb[3];
@@ -864,7 +876,8 @@ __device__ unsigned long long g_x3_stamps[3][4096][16][16];
 // (head_convT1c_planar; w.hc / w.hcb / w.hce).
 template <class Cfg, bool TRANS, bool COMP = false>
 __global__ __launch_bounds__(Cfg::HW * 64, Cfg::HMIN) void x3_head_kernel(const float* __restrict__ mel, int T,
-                                                                            VocX w, unsigned char* __restrict__ U1) {
+                                                                            VocX w, unsigned char* __restrict__ U1,
+                                                                            int items) {
     if (w.rclear && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < 5) {
         if (threadIdx.x == 0) *reinterpret_cast<volatile int*>(w.rclear) = 0;
         else if (w.rqueue) reinterpret_cast<volatile unsigned*>(w.rqueue)[threadIdx.x - 1] = 0u;
@@ -972,19 +985,19 @@ __global__ __launch_bounds__(Cfg::HW * 64, Cfg::HMIN) void x3_head_kernel(const 
         unsigned char* hp = lds;
         head_convT1c_planar<MP, C1, Pl::RS_M, Pl::RS_1>(
             w.hc, w.hcb, (left || right) ? corr : nullptr, melA, up, f0, T, &ap,
-            w.w1[0] + (size_t)(wv % MB1) * nkb_of<C1, 3>() * 128 + (threadIdx.x & 63));
+            w.w1[0] + (size_t)rb1_mb<MB1>(wv, items) * nkb_of<C1, 3>() * 128 + (threadIdx.x & 63));
         XSTAMP(0, 5);
         __syncthreads();
         XSTAMP(0, 6);
         head_rb1_planar<C1, Pl::RS_1, false>(w.w1[0], w.b1[0], up, hp, nullptr, f0, TF, 4 * T, &ap,
-                                             w.w2[0] + (size_t)(wv % MB1) * nkb_of<C1, 3>() * 128 +
+                                             w.w2[0] + (size_t)rb1_mb<MB1>(wv, items) * nkb_of<C1, 3>() * 128 +
                                                  (threadIdx.x & 63),
-                                             nullptr);
+                                             nullptr, 0, items);
         XSTAMP(0, 7);
         __syncthreads();
         XSTAMP(0, 8);
         head_rb1_planar<C1, Pl::RS_1, true>(w.w2[0], w.b2[0], hp, nullptr, up, f0, TF, 4 * T, &ap, nullptr,
-                                            U1 + (size_t)b * 4 * T * 4 * C1);
+                                            U1 + (size_t)b * 4 * T * 4 * C1, 0, items);
         XSTAMP(0, 9);
         XSTAMP_RT(0, 15);
         return;
@@ -1012,20 +1025,20 @@ __global__ __launch_bounds__(Cfg::HW * 64, Cfg::HMIN) void x3_head_kernel(const 
         XSTAMP(0, 4);
         constexpr int MB1 = C1 / 16;
         head_convT1_planar<C, C1, Pl::RS_C, Pl::RS_1>(w.wt[0], w.bt[0], a0w, up, f0, 4 * T, &ap,
-                                                    w.w1[0] + (size_t)(wv % MB1) * nkb_of<C1, 3>() * 128 +
+                                                    w.w1[0] + (size_t)rb1_mb<MB1>(wv, items) * nkb_of<C1, 3>() * 128 +
                                                         (threadIdx.x & 63));
         XSTAMP(0, 5);
         __syncthreads();
         XSTAMP(0, 6);
         head_rb1_planar<C1, Pl::RS_1, false>(w.w1[0], w.b1[0], up, hp, nullptr, f0, TF, 4 * T, &ap,
-                                             w.w2[0] + (size_t)(wv % MB1) * nkb_of<C1, 3>() * 128 +
+                                             w.w2[0] + (size_t)rb1_mb<MB1>(wv, items) * nkb_of<C1, 3>() * 128 +
                                                  (threadIdx.x & 63),
-                                             nullptr);
+                                             nullptr, 0, items);
         XSTAMP(0, 7);
         __syncthreads();
         XSTAMP(0, 8);
         head_rb1_planar<C1, Pl::RS_1, true>(w.w2[0], w.b2[0], hp, nullptr, up, f0, TF, 4 * T, &ap, nullptr,
-                                            U1 + (size_t)b * 4 * T * 4 * C1);
+                                            U1 + (size_t)b * 4 * T * 4 * C1, 0, items);
         XSTAMP(0, 9);
         XSTAMP_RT(0, 15);
         return;
@@ -1073,8 +1086,14 @@ __global__ __launch_bounds__(Cfg::HW * 64, Cfg::HMIN) void x3_head_kernel(const 
 // memory, one launch boundary less.  Every output keeps its operation
 // sequence: U2 is bit-identical to the two launches'.
 // The mid's roles take 12 of the 16 waves; the others only keep the step
-// barriers.  Each role fetches its weight fragments when it starts, as in
-// midp_kernel.
+// barriers.  A role's first four k-blocks of weight fragments (8 of its 12 -
+// 16 KB) are handed over like the head's from layer to layer: ResBlock1's
+// conv2 issues their loads after its last MFMA, so they fly across its
+// epilogue and the barrier; the role fetches the rest when it starts
+// (-DM2_ROLE_PREFETCH=0, an A/B build: all of them then, as in midp_kernel).
+#ifndef M2_ROLE_PREFETCH
+#define M2_ROLE_PREFETCH 1
+#endif
 struct HmPlan {
     using Pl = HeadPlan<CfgS1::MP, CfgS1::C, CfgS1::TF, true>;
     static constexpr int S_MAX = kHeadmidSMax;  // owned columns + one on either side = the valid positions
@@ -1097,7 +1116,7 @@ struct HmPlan {
 template <bool TRANS, int NCHC>
 __global__ __launch_bounds__(CfgS1::HW * 64, CfgS1::HMIN) void headmid_kernel(const float* __restrict__ mel, int T,
                                                                                VocX w, unsigned char* __restrict__ U2,
-                                                                               int S, int nch_arg) {
+                                                                               int S, int nch_arg, int items) {
     if (w.rclear && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < 5) {
         if (threadIdx.x == 0) *reinterpret_cast<volatile int*>(w.rclear) = 0;
         else if (w.rqueue) reinterpret_cast<volatile unsigned*>(w.rqueue)[threadIdx.x - 1] = 0u;
@@ -1143,15 +1162,18 @@ __global__ __launch_bounds__(CfgS1::HW * 64, CfgS1::HMIN) void headmid_kernel(co
     }
     unsigned char* up = lds + Pl::RA;
     unsigned char* hp = lds;
-    const u32x4* wr1 = w.w1[0] + (size_t)(wv % MB1) * nkb_of<C1, 3>() * 128 + (threadIdx.x & 63);
-    const u32x4* wr2 = w.w2[0] + (size_t)(wv % MB1) * nkb_of<C1, 3>() * 128 + (threadIdx.x & 63);
+    const u32x4* wr1 = w.w1[0] + (size_t)rb1_mb<MB1>(wv, items) * nkb_of<C1, 3>() * 128 + (threadIdx.x & 63);
+    const u32x4* wr2 = w.w2[0] + (size_t)rb1_mb<MB1>(wv, items) * nkb_of<C1, 3>() * 128 + (threadIdx.x & 63);
     head_convT1c_planar<MP, C1, Pl::RS_M, Pl::RS_1>(w.hc, w.hcb, (left || right) ? corr : nullptr, melA, up, f0, T,
                                                     &ap, wr1, rot);
     __syncthreads();
-    head_rb1_planar<C1, Pl::RS_1, false>(w.w1[0], w.b1[0], up, hp, nullptr, f0, TF, L1, &ap, wr2, nullptr, rot);
+    head_rb1_planar<C1, Pl::RS_1, false>(w.w1[0], w.b1[0], up, hp, nullptr, f0, TF, L1, &ap, wr2, nullptr, rot,
+                                         items);
     __syncthreads();
-    head_rb1_planar<C1, Pl::RS_1, true, true>(w.w2[0], w.b2[0], hp, nullptr, up, f0, TF, L1, &ap, nullptr, nullptr,
-                                              rot);
+    constexpr bool PREF = M2_ROLE_PREFETCH != 0;
+    static_assert(sizeof(APipe) == mp::kPre * 2 * sizeof(u32x4), "the hand-over holds the roles' first k-blocks");
+    head_rb1_planar<C1, Pl::RS_1, true, true>(w.w2[0], w.b2[0], hp, nullptr, up, f0, TF, L1, &ap,
+                                              PREF && wv < 12 ? mp::role_wp(w.mp, wv) : nullptr, nullptr, rot, items);
     __syncthreads();  // U1 of the window is in the u planes; region A is dead
     // the mid's pipeline over the strip (midp_kernel's roles and step protocol)
     const bool edge = qa < 16 || qa + 16 * nch + 16 > L1;
@@ -1164,18 +1186,18 @@ __global__ __launch_bounds__(CfgS1::HW * 64, CfgS1::HMIN) void headmid_kernel(co
     else if (layer == 1) __builtin_amdgcn_s_setprio(1);
     else __builtin_amdgcn_s_setprio(0);
     switch (wv) {
-        case 0: mp::layer_role<0, 0, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
-        case 1: mp::layer_role<0, 1, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
-        case 2: mp::layer_role<0, 2, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
-        case 3: mp::layer_role<0, 3, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
-        case 4: mp::layer_role<1, 0, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
-        case 5: mp::layer_role<1, 1, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
-        case 6: mp::layer_role<1, 2, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
-        case 7: mp::layer_role<1, 3, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
-        case 8: mp::layer_role<2, 0, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
-        case 9: mp::layer_role<2, 1, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
-        case 10: mp::layer_role<2, 2, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
-        case 11: mp::layer_role<2, 3, Lay>(lds, qa, L1, nch, edge, W, bias, u2row, xown); break;
+        case 0: mp::layer_role<0, 0, Lay, 0, 2, PREF>(lds, qa, L1, nch, edge, W, bias, u2row, xown, ap); break;
+        case 1: mp::layer_role<0, 1, Lay, 0, 2, PREF>(lds, qa, L1, nch, edge, W, bias, u2row, xown, ap); break;
+        case 2: mp::layer_role<0, 2, Lay, 0, 2, PREF>(lds, qa, L1, nch, edge, W, bias, u2row, xown, ap); break;
+        case 3: mp::layer_role<0, 3, Lay, 0, 2, PREF>(lds, qa, L1, nch, edge, W, bias, u2row, xown, ap); break;
+        case 4: mp::layer_role<1, 0, Lay, 0, 2, PREF>(lds, qa, L1, nch, edge, W, bias, u2row, xown, ap); break;
+        case 5: mp::layer_role<1, 1, Lay, 0, 2, PREF>(lds, qa, L1, nch, edge, W, bias, u2row, xown, ap); break;
+        case 6: mp::layer_role<1, 2, Lay, 0, 2, PREF>(lds, qa, L1, nch, edge, W, bias, u2row, xown, ap); break;
+        case 7: mp::layer_role<1, 3, Lay, 0, 2, PREF>(lds, qa, L1, nch, edge, W, bias, u2row, xown, ap); break;
+        case 8: mp::layer_role<2, 0, Lay, 0, 2, PREF>(lds, qa, L1, nch, edge, W, bias, u2row, xown, ap); break;
+        case 9: mp::layer_role<2, 1, Lay, 0, 2, PREF>(lds, qa, L1, nch, edge, W, bias, u2row, xown, ap); break;
+        case 10: mp::layer_role<2, 2, Lay, 0, 2, PREF>(lds, qa, L1, nch, edge, W, bias, u2row, xown, ap); break;
+        case 11: mp::layer_role<2, 3, Lay, 0, 2, PREF>(lds, qa, L1, nch, edge, W, bias, u2row, xown, ap); break;
         default:  // no role: the step barriers only
 #pragma unroll 1
             for (int s = -1; s <= nch + 2; ++s) pipe::step_barrier();
@@ -1372,13 +1394,14 @@ int32_t run(const float* mel, int T, const VocLaunchPlan& p, const VocX& w, void
     int32_t rc;
     int L1 = 4 * T, L2 = 16 * T;
     VocX wv = w;
+    int items = sw().head_items;  // ResBlock1's item map of the 16-wave planar head (head_rb1_planar)
     if (p.headmid) {
-        void* args[] = {&mel, &T, &wv, &U2, const_cast<int*>(&p.hm_S), const_cast<int*>(&p.hm_nch)};
+        void* args[] = {&mel, &T, &wv, &U2, const_cast<int*>(&p.hm_S), const_cast<int*>(&p.hm_nch), &items};
         if ((rc = launch_row(kRows.headmid[p.hm_nch == 16][p.trans], p.head_g, st, args, "headmid_kernel"))) return rc;
         g_headmid_launches.fetch_add(1, std::memory_order_relaxed);
     } else {
         mark(0, true);
-        void* hargs[] = {&mel, &T, &wv, &U1};
+        void* hargs[] = {&mel, &T, &wv, &U1, &items};
         rc = launch_row(kRows.head[(int)p.head][p.comp][p.trans], p.head_g, st, hargs, "x3_head_kernel");
         mark(0, false);
         if (rc) return rc;
