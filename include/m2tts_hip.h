@@ -884,7 +884,9 @@ int32_t m2_vocoder_path(const m2_model* model);
  * attention, 2 = the same with at least one layer whose attention-score bound
  * reaches the f16 maximum (that layer keeps its softmax base in fp32 in every
  * attention form), 0 = fp32 linears and the exact-f32 attention (weights
- * whose activation bound leaves the f16 range, or M2_TF_UNFUSED / M2_ATT_F32). */
+ * whose activation bound leaves the f16 range, or M2_TF_UNFUSED / M2_ATT_F32
+ * set when the handle is created: M2_ATT_F32 selects exactly what the range
+ * bound selects, M2_TF_UNFUSED the fp32 linears with the default attention). */
 int32_t m2_transformer_path(const m2_model* model);
 
 #ifdef __cplusplus

@@ -245,7 +245,9 @@ TransformerPlan plan_transformer(const HostWeights& w, const m2_config& c, const
         worst = std::max(worst, std::max(std::max(b1, b2), std::max(qkv, hid)));
     }
     if (c.decoder_layers > 0) worst = std::max(worst, ln_bound("decoder.norm"));
-    t.att_f32 = !(worst < 32768.0);
+    // M2_ATT_F32=1 asks for the same path at handle creation, as M2_TF_UNFUSED
+    // does for the linears: fp32 linears and attention_kernel<HD>
+    t.att_f32 = !(worst < 32768.0) || s.att_f32;
     if (t.att_f32) t.tfused = false;
     return t;
 }

@@ -42,42 +42,84 @@ def f32c(t: Tensor) -> Tensor:
     return t.contiguous()
 
 
+def _shape(t: Tensor) -> tuple:
+    return tuple(t.shape)
+
+
+def _vec(t: Optional[Tensor], n: int, what: str) -> Optional[Tensor]:
+    """A per-channel vector as contiguous float32 [n] (None stays None)."""
+    if t is None:
+        return None
+    t = f32c(t)
+    if _shape(t) != (n,):
+        raise RuntimeError(f"{what} must be [{n}], got {_shape(t)}")
+    return t
+
+
+def _like(t: Optional[Tensor], shape: tuple, what: str) -> Optional[Tensor]:
+    """A tensor of the output's shape as contiguous float32 (None stays None)."""
+    if t is None:
+        return None
+    t = f32c(t)
+    if _shape(t) != tuple(shape):
+        raise RuntimeError(f"{what} must be {tuple(shape)}, got {_shape(t)}")
+    return t
+
+
 def linear(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None, *, ln: Optional[tuple] = None,
            act: int = ACT_NONE, residual: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
     """y = act(LN?(x) @ W^T + b) (+ residual) over the last dim (nn.Linear layout W [N, K])."""
-    require_device(x, weight, what="linear")
-    x = f32c(x)
+    g, b_ = (ln if ln is not None else (None, None))
+    require_device(x, weight, bias, g, b_, residual, out, what="linear")
+    x, weight = f32c(x), f32c(weight)
     K = x.shape[-1]
+    if weight.dim() != 2 or weight.shape[1] != K:
+        raise RuntimeError(f"linear: weight {_shape(weight)} does not fit x {_shape(x)}: it must be [N, {K}]")
     N = weight.shape[0]
     R = x.numel() // K if K else 0
-    y = out if out is not None else torch.empty(*x.shape[:-1], N, device=x.device, dtype=torch.float32)
-    g, b_ = (ln if ln is not None else (None, None))
-    res = f32c(residual) if residual is not None else None
-    _lib.call("m2_linear", _ptr(x), _ptr(g), _ptr(b_), _ptr(f32c(weight)), _ptr(bias), _ptr(res), act,
+    shape = (*x.shape[:-1], N)
+    bias = _vec(bias, N, "linear: bias")
+    g, b_ = _vec(g, K, "linear: the LayerNorm weight"), _vec(b_, K, "linear: the LayerNorm bias")
+    res = _like(residual, shape, "linear: residual")
+    if out is not None and (_like(out, shape, "linear: out") is not out):
+        raise RuntimeError(f"linear: out {_shape(out)} must be contiguous, got strides {out.stride()}")
+    y = out if out is not None else torch.empty(shape, device=x.device, dtype=torch.float32)
+    if y.numel() == 0:
+        return y
+    _lib.call("m2_linear", _ptr(x), _ptr(g), _ptr(b_), _ptr(weight), _ptr(bias), _ptr(res), act,
               R, K, N, _ptr(y), stream_handle(x.device))
     return y
 
 
 def layer_norm(x: Tensor, weight: Tensor, bias: Tensor) -> Tensor:
-    require_device(x, what="layer_norm")
+    require_device(x, weight, bias, what="layer_norm")
     x = f32c(x)
     K = x.shape[-1]
+    weight, bias = _vec(weight, K, "layer_norm: weight"), _vec(bias, K, "layer_norm: bias")
     y = torch.empty_like(x)
-    _lib.call("m2_layer_norm", _ptr(x), _ptr(weight), _ptr(bias), x.numel() // K, K, _ptr(y),
+    if y.numel() == 0:
+        return y
+    _lib.call("m2_layer_norm", _ptr(x), _ptr(weight), _ptr(bias), x.numel() // K if K else 0, K, _ptr(y),
               stream_handle(x.device))
     return y
 
 
 def attention_core(qkv: Tensor, heads: int, key_mask: Optional[Tensor]) -> Tensor:
     """softmax(QK^T/sqrt(hd) with -1e9 key mask) V for qkv [B,N,3H] -> [B,N,H]."""
-    require_device(qkv, what="attention")
+    require_device(qkv, key_mask, what="attention")
     qkv = f32c(qkv)
+    if qkv.dim() != 3 or qkv.shape[-1] % 3 != 0:
+        raise RuntimeError(f"attention: qkv must be [B, N, 3H], got {_shape(qkv)}")
     B, N, H3 = qkv.shape
     H = H3 // 3
-    out = torch.empty(B, N, H, device=qkv.device, dtype=torch.float32)
     m = None
     if key_mask is not None:
+        if _shape(key_mask) != (B, N):
+            raise RuntimeError(f"attention: the key mask must be {(B, N)}, got {_shape(key_mask)}")
         m = key_mask.to(torch.uint8).contiguous() if key_mask.dtype != torch.bool else key_mask.contiguous()
+    out = torch.empty(B, N, H, device=qkv.device, dtype=torch.float32)
+    if out.numel() == 0:
+        return out
     _lib.call("m2_attention", _ptr(qkv), _ptr(m), B, N, H, heads, _ptr(out), stream_handle(qkv.device))
     return out
 
@@ -87,36 +129,54 @@ def conv1d(x: Tensor, weight: Tensor, bias: Tensor, *, act: int = ACT_NONE,
            padding: Optional[int] = None) -> Tensor:
     """Conv1d(k, dilation, zero padding (default k//2)) [+ per-channel affine]
     [+ act] [+ residual], x [B,Cin,L] -> [B,Cout,L + 2 pad - dil (k - 1)].
+    Order: affine, then act, then the residual add.
     k = 1 | 3 with dilation 1 and padding k//2 run the tiled kernel
     (m2_conv1d); every other geometry the general one (m2_conv1d_ex)."""
-    require_device(x, weight, what="conv1d")
-    x = f32c(x)
+    al, be = affine if affine is not None else (None, None)
+    require_device(x, weight, bias, al, be, residual, what="conv1d")
+    x, weight = f32c(x), f32c(weight)
+    if x.dim() != 3 or weight.dim() != 3 or weight.shape[1] != x.shape[1]:
+        raise RuntimeError(f"conv1d: weight {_shape(weight)} does not fit x {_shape(x)}: x must be [B, Cin, L] "
+                           f"and weight [Cout, Cin, k]")
     B, Cin, L = x.shape
     Cout, _, K = weight.shape
     pad = K // 2 if padding is None else int(padding)
     Lo = L + 2 * pad - dilation * (K - 1)
     if residual is not None and Lo != L:
         raise RuntimeError(f"conv1d: output length {Lo} != input length {L}: the residual add has mismatched shapes")
-    y = torch.empty(B, Cout, max(Lo, 0), device=x.device, dtype=torch.float32)
-    al, be = affine if affine is not None else (None, None)
-    res = f32c(residual) if residual is not None else None
+    if Lo < 0:
+        raise RuntimeError(f"conv1d: x {_shape(x)} is shorter than the kernel (k {K}, dilation {dilation}, "
+                           f"padding {pad}): output length {Lo}")
+    bias = _vec(bias, Cout, "conv1d: bias")
+    al, be = _vec(al, Cout, "conv1d: the affine scale"), _vec(be, Cout, "conv1d: the affine shift")
+    res = _like(residual, (B, Cout, Lo), "conv1d: residual")
+    y = torch.empty(B, Cout, Lo, device=x.device, dtype=torch.float32)
+    if y.numel() == 0:
+        return y
     if K in (1, 3) and dilation == 1 and pad == K // 2:
-        _lib.call("m2_conv1d", _ptr(x), _ptr(f32c(weight)), _ptr(f32c(bias)), _ptr(al), _ptr(be), _ptr(res), K, act,
+        _lib.call("m2_conv1d", _ptr(x), _ptr(weight), _ptr(bias), _ptr(al), _ptr(be), _ptr(res), K, act,
                   B, Cin, Cout, L, _ptr(y), stream_handle(x.device))
     else:
-        _lib.call("m2_conv1d_ex", _ptr(x), _ptr(f32c(weight)), _ptr(f32c(bias)), _ptr(al), _ptr(be), _ptr(res), K,
+        _lib.call("m2_conv1d_ex", _ptr(x), _ptr(weight), _ptr(bias), _ptr(al), _ptr(be), _ptr(res), K,
                   int(dilation), pad, act, B, Cin, Cout, L, _ptr(y), stream_handle(x.device))
     return y
 
 
 def conv_transpose1d(x: Tensor, weight: Tensor, bias: Tensor, rate: int, *, act: int = ACT_NONE) -> Tensor:
     """ConvTranspose1d(k=2r, stride=r, padding=r/2) [+ act]; weight [Cin, Cout, 2r]."""
-    require_device(x, weight, what="conv_transpose1d")
-    x = f32c(x)
+    require_device(x, weight, bias, what="conv_transpose1d")
+    x, weight = f32c(x), f32c(weight)
+    rate = int(rate)
+    if x.dim() != 3 or weight.dim() != 3 or weight.shape[0] != x.shape[1] or weight.shape[2] != 2 * rate:
+        raise RuntimeError(f"conv_transpose1d: weight {_shape(weight)} does not fit x {_shape(x)} at rate {rate}: "
+                           f"x must be [B, Cin, L] and weight [Cin, Cout, {2 * rate}]")
     B, Cin, L = x.shape
     Cout = weight.shape[1]
+    bias = _vec(bias, Cout, "conv_transpose1d: bias")
     y = torch.empty(B, Cout, L * rate, device=x.device, dtype=torch.float32)
-    _lib.call("m2_conv_transpose1d", _ptr(x), _ptr(f32c(weight)), _ptr(f32c(bias)), rate, act, B, Cin, Cout, L,
+    if y.numel() == 0:
+        return y
+    _lib.call("m2_conv_transpose1d", _ptr(x), _ptr(weight), _ptr(bias), rate, act, B, Cin, Cout, L,
               _ptr(y), stream_handle(x.device))
     return y
 
@@ -643,24 +703,39 @@ def linear_backward_weight(g_y: Tensor, x: Tensor, *, ln: Optional[tuple] = None
 
 
 def embed_positional(ids: Tensor, emb: Tensor, pe: Tensor, scale: float) -> Tensor:
-    require_device(ids, emb, what="embedding")
+    """y[b,s,:] = emb[ids[b,s],:] * scale + pe[s,:]; ids outside [0, vocab) read a zero row."""
+    require_device(ids, emb, pe, what="embedding")
     ids = ids.to(torch.int64).contiguous()
+    emb, pe = f32c(emb), f32c(pe)
+    if ids.dim() != 2 or emb.dim() != 2:
+        raise RuntimeError(f"embedding: ids must be [B, S] and emb [vocab, H], got {_shape(ids)} and {_shape(emb)}")
     B, S = ids.shape
     H = emb.shape[1]
+    if pe.dim() != 2 or pe.shape[0] < S or pe.shape[1] != H:
+        raise RuntimeError(f"embedding: the positional table must be [>= {S}, {H}], got {_shape(pe)}")
     y = torch.empty(B, S, H, device=emb.device, dtype=torch.float32)
-    _lib.call("m2_embed_positional", _ptr(ids), _ptr(f32c(emb)), _ptr(f32c(pe)), B, S, H, emb.shape[0],
+    if y.numel() == 0:
+        return y
+    _lib.call("m2_embed_positional", _ptr(ids), _ptr(emb), _ptr(pe), B, S, H, emb.shape[0],
               float(scale), _ptr(y), stream_handle(emb.device))
     return y
 
 
 def add_positional(x: Tensor, pe: Tensor) -> Tensor:
+    """y = x + pe[:S] for x [B,S,H]; pe [rows >= S, H] (leading dimensions of size 1 allowed)."""
     require_device(x, pe, what="positional encoding")
-    x = f32c(x)
+    x, pe = f32c(x), f32c(pe)
+    if x.dim() != 3:
+        raise RuntimeError(f"positional encoding: x must be [B, S, H], got {_shape(x)}")
     B, S, H = x.shape
+    if pe.dim() < 2 or pe.shape[-1] != H or pe.numel() != pe.shape[-2] * H:
+        raise RuntimeError(f"positional encoding: the table must be [rows, {H}], got {_shape(pe)}")
     if S > pe.shape[-2]:
         raise RuntimeError(f"sequence length {S} exceeds the positional table ({pe.shape[-2]})")
     y = torch.empty_like(x)
-    _lib.call("m2_add_positional", _ptr(x), _ptr(f32c(pe)), B, S, H, _ptr(y), stream_handle(x.device))
+    if y.numel() == 0:
+        return y
+    _lib.call("m2_add_positional", _ptr(x), _ptr(pe), B, S, H, _ptr(y), stream_handle(x.device))
     return y
 
 

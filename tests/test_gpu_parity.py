@@ -377,10 +377,15 @@ def test_alternate_kernel_paths(gpu, stage, env, monkeypatch):
     """The unfused transformer layer (five linears), the per-layer vocoder
     kernels, the x3 tail / mid kernels (instead of the pipelined stage1 ones)
     and the exact-f32 attention stay parity-green: inference vs the
-    reference's fixture."""
+    reference's fixture.  The two transformer switches act at handle creation
+    and give the fp32 path (m2_transformer_path 0); the vocoder's leave the
+    split-f16 transformer alone."""
+    from m2amd import _lib
     monkeypatch.setenv(env, "1")
     g = golden(f"{stage}_small")
     m = build_model(stage, gpu)
+    path = _lib.load().m2_transformer_path(m._hip(gpu).handle)
+    assert path == 0 if env in ("M2_TF_UNFUSED", "M2_ATT_F32") else path in (1, 2)
     ids, lens = _ids(g, gpu)
     mel, audio = m.inference(ids, lens)
     assert maxabs(mel, g["mel"]) <= MEL_MAXABS_TOL
