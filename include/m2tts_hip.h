@@ -888,6 +888,16 @@ int32_t m2_vocoder_path(const m2_model* model);
  * set when the handle is created: M2_ATT_F32 selects exactly what the range
  * bound selects, M2_TF_UNFUSED the fp32 linears with the default attention). */
 int32_t m2_transformer_path(const m2_model* model);
+/* The driver a call made now would run the layers of a stack on (stack: 0 text
+ * encoder, 1 mel decoder), under the developer switches in force: 0 = five
+ * fp32 linears per layer, 1 = three launches per layer, each LN1 -> QKV its
+ * own launch (M2_TF_CHAIN=0), 2 = three launches per layer with the next
+ * layer's LN1 -> QKV (or the final LN -> mel projection) chained into
+ * post_attn_kernel, 3 = one launch per layer (transformer_layer.hip).  A stack
+ * without layers reports the form its layers would take.  Host arithmetic on
+ * the predicates the drivers branch on: nothing is launched.  Negative
+ * M2_E_ARG for a null model or another stack. */
+int32_t m2_debug_transformer_form(const m2_model* model, int32_t stack);
 
 #ifdef __cplusplus
 }

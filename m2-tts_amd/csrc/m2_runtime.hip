@@ -631,6 +631,17 @@ int32_t m2_length_regulator_expand(const float* enc, const int32_t* cum, int32_t
 }  // extern "C"
 
 namespace {
+// The decoder's final LayerNorm -> mel projection as a launch of its own (the
+// last layer did not run it): ln_gemm on the packed weights where (H, mel) has
+// an instance, else - any other mel width of a fused handle, and the fp32
+// path - the generic linear on the fp32 weights.  Neither needs scratch.
+int32_t final_projection(const m2_model* m, const float* x, int R, float* out_mel, hipStream_t st) {
+    const int H = m->cfg.hidden_dim, M = m->cfg.mel_channels;
+    if (m->tfused && tf_ln_gemm_supported(H, M))
+        return launch_ln_gemm(x, m->dec_nw, m->dec_nb, m->mel_p, m->mel_b, ACT_NONE, R, H, M, out_mel, st);
+    return launch_linear(x, m->dec_nw, m->dec_nb, m->mel_w, m->mel_b, nullptr, ACT_NONE, R, H, M, out_mel, st);
+}
+
 // The mel decoder on x [B, T, H]; with enc / cum given, x is first filled by
 // the length regulator's frame expansion of enc, fused into the first layer's
 // LN1 -> QKV launch when tf_first_fused (else a separate lr_expand launch).
@@ -678,8 +689,7 @@ int32_t mel_decoder(const m2_model* m, float* x, int32_t B, int32_t T, float* ou
                           m->cfg.mel_channels, out_mel, &projected, dT, rows)))
             return rc;
         if (projected) return M2_OK;
-        return launch_ln_gemm(wb.x, m->dec_nw, m->dec_nb, m->mel_p, m->mel_b, ACT_NONE, B * T, H, m->cfg.mel_channels,
-                              out_mel, st);
+        return final_projection(m, wb.x, B * T, out_mel, st);
     }
     bool qkv_ready = false;
     if (enc) {
@@ -697,12 +707,7 @@ int32_t mel_decoder(const m2_model* m, float* x, int32_t B, int32_t T, float* ou
                         m->cfg.mel_channels, out_mel, &projected, qkv_ready)))
         return rc;
     if (projected) return M2_OK;
-    const float* cur = m->dec.empty() ? x : wb.x;
-    if (m->tfused)
-        return launch_ln_gemm(cur, m->dec_nw, m->dec_nb, m->mel_p, m->mel_b, ACT_NONE, B * T, H, m->cfg.mel_channels,
-                              out_mel, st);
-    return launch_linear(cur, m->dec_nw, m->dec_nb, m->mel_w, m->mel_b, nullptr, ACT_NONE, B * T, H,
-                         m->cfg.mel_channels, out_mel, st);
+    return final_projection(m, m->dec.empty() ? x : wb.x, B * T, out_mel, st);
 }
 }  // namespace
 
@@ -1441,6 +1446,13 @@ int32_t m2_transformer_path(const m2_model* m) {
         for (const m2_layer_w& L : *st)
             if (L.wide_scores) return 2;
     return 1;
+}
+
+int32_t m2_debug_transformer_form(const m2_model* m, int32_t stack) {
+    M2_CHECK_ARG(m && (stack == 0 || stack == 1), "m2_debug_transformer_form: bad argument");
+    if (tfl_use(m, stack ? m->dec : m->enc)) return 3;  // text_encoder_layers / mel_decoder ask this first
+    if (!m->tfused) return 0;                           // run_layer's five linears
+    return tf_chain(m) ? 2 : 1;                         // run_stack
 }
 
 int32_t m2_profile_enable(m2_model* m, int32_t capacity) {

@@ -14,6 +14,9 @@ std::vector<float> pack_bfrag(const float* W, int N, int K);
 // W in fp32); false if a weight is outside the f16 range.
 bool pack_bfrag_split(const float* W, int N, int K, std::vector<float>* out);
 // y[R][N] = LN(x)[R][K] . W^T (+ bias); Wp from pack_bfrag_split.
+// (K, N) with an instance: (32, 96 | 32 | 64), (64, 192 | 64 | 80), (96, 288 | 80 | 96);
+// any other answers M2_E_SHAPE (tf_ln_gemm_supported asks beforehand).
+bool tf_ln_gemm_supported(int K, int N);
 int32_t launch_ln_gemm(const float* x, const float* g, const float* b, const float* Wp, const float* bias, int act,
                        int R, int K, int N, float* y, hipStream_t st);
 // y = o + FFN(LN2(o)), o = x + att . Wo^T + bo (Wo, W1, W2 from pack_bfrag_split); y may alias x.

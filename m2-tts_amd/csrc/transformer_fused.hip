@@ -435,6 +435,9 @@ static int tf_waves(int R) {
     return cdiv(R, tfx::TR) < 2 * 256 ? 8 : 4;
 }
 
+// The widths launch_ln_gemm instantiates are those post_attn_kernel chains (tf_post_next_supported).
+bool tf_ln_gemm_supported(int K, int N) { return tf_post_next_supported(K, N); }
+
 int32_t launch_ln_gemm(const float* x, const float* g, const float* b, const float* Wp, const float* bias, int act,
                        int R, int K, int N, float* y, hipStream_t st) {
     if (R == 0) return M2_OK;
