@@ -839,6 +839,68 @@ int32_t m2_linear_backward_weight(const float* g_y, const float* x, const float*
                                   int32_t R, int32_t K, int32_t N, float* dw, float* db, void* workspace,
                                   size_t workspace_bytes, void* stream);
 
+/* ---- the text encoder's training forward and backward, the length regulator's
+ * adjoint ------------------------------------------------------------------
+ * TextEncoder from its raw parameters, as the decoder above.  params: 1 + 11
+ * layers + 2 device pointers in parameters() order: embedding.weight [V,H],
+ * the layers' 11 each (the decoder's), norm.weight, norm.bias.  The dimension
+ * arguments are (V, H, layers, heads, B, S); ids is int64 [B,S], read as R = B S
+ * positions; pe is the positional table's first S rows [S,H] (a buffer: it gets
+ * no gradient); key_mask is [B,S] bytes (0 = masked) or NULL.  Supported: the
+ * decoder's shapes and 1 <= V <= 65536 (else M2_E_SHAPE; the _bytes queries
+ * return 0).  B = 0 or S = 0: nothing to do, M2_OK.
+ *
+ * m2_encoder_train_forward: out [B,S,H], bit-equal to the stand-alone module's
+ * forward (m2_embed_positional at scale sqrt(H), the layers with the key mask,
+ * m2_layer_norm), each op writing into the tape: x0 [R,H], the embedding's
+ * output, then the decoder's five maps per layer.  m2_encoder_tape_map(index =
+ * 0, or 1 + 5 layer + map) names a map's offset (in floats) and width.
+ *
+ * m2_encoder_backward: given d_out [B,S,H], grads as the decoder's (1 + 11
+ * layers + 2 pointers, NULL skips, accumulate adds with one fp32 addition per
+ * element).  An id outside [0, V) read a zero row and contributes nothing; a
+ * vocabulary row that never occurs gets exactly 0.  No floating-point atomics:
+ * equal inputs give equal bits.
+ *
+ * m2_debug_encoder_grad_plan: as m2_debug_decoder_grad_plan (the format is in
+ * csrc/encoder_grad_plan.h).
+ *
+ * The kernels alone:
+ * m2_embedding_backward: d_emb [V,H] = scale * the sum of d_x [R,H] over the
+ *   positions with ids[r] == v, in ascending position; overwritten, or added
+ *   to with accumulate != 0.  1 <= V <= 65536, H <= 256.
+ * m2_layer_norm_backward: the backward of y = LayerNorm(x; gamma, beta), x and
+ *   g_y [R,K], K a multiple of 8, at most 128: g_x [R,K] (or NULL) = the
+ *   input's cotangent plus g_res [R,K] (or NULL); dgamma and dbeta [K] (each
+ *   may be NULL) are overwritten, through the workspace.
+ * m2_length_regulator_backward: the adjoint of m2_length_regulator_expand:
+ *   d_enc [B,S,H] at (b, s) = the sum of d_reg [B,T_out,H] at (b, t) over
+ *   cum[b,s] <= t < min(cum[b,s+1], T_out), t ascending, so the order depends on
+ *   the phoneme's frame count alone; a phoneme without frames gets exactly 0,
+ *   padding and truncated frames reach nothing, durations get no gradient. */
+size_t m2_encoder_tape_bytes(int32_t V, int32_t H, int32_t layers, int32_t heads, int32_t B, int32_t S);
+int32_t m2_encoder_tape_map(int32_t V, int32_t H, int32_t layers, int32_t heads, int32_t B, int32_t S, int32_t index,
+                            size_t* offset_floats, int32_t* width);
+int32_t m2_encoder_train_forward(const float* const* params, int32_t V, int32_t H, int32_t layers, int32_t heads,
+                                 const int64_t* ids, const float* pe, const uint8_t* key_mask, int32_t B, int32_t S,
+                                 float* out, void* tape, size_t tape_bytes, void* stream);
+size_t m2_encoder_backward_workspace_bytes(int32_t V, int32_t H, int32_t layers, int32_t heads, int32_t B, int32_t S);
+int32_t m2_encoder_backward(const float* const* params, int32_t V, int32_t H, int32_t layers, int32_t heads,
+                            const int64_t* ids, const uint8_t* key_mask, int32_t B, int32_t S, const void* tape,
+                            const float* d_out, float* const* grads, int32_t accumulate, void* workspace,
+                            size_t workspace_bytes, void* stream);
+int32_t m2_debug_encoder_grad_plan(int32_t V, int32_t H, int32_t layers, int32_t heads, int32_t B, int32_t S, char* out,
+                                   size_t cap);
+size_t m2_embedding_backward_workspace_bytes(int32_t R, int32_t V, int32_t H);
+int32_t m2_embedding_backward(const int64_t* ids, const float* d_x, int32_t R, int32_t V, int32_t H, float scale,
+                              float* d_emb, int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream);
+size_t m2_layer_norm_backward_workspace_bytes(int32_t R, int32_t K);
+int32_t m2_layer_norm_backward(const float* g_y, const float* x, const float* gamma, const float* g_res, int32_t R,
+                               int32_t K, float* g_x, float* dgamma, float* dbeta, void* workspace,
+                               size_t workspace_bytes, void* stream);
+int32_t m2_length_regulator_backward(const float* d_reg, const int32_t* cum, int32_t B, int32_t S, int32_t H,
+                                     int32_t T_out, float* d_enc, void* stream);
+
 /* ---- measurement ----------------------------------------------------------
  * Kernel timing with HIP events recorded on the launch stream around each of
  * the fused vocoder's kernels (bench.py's roofline).  enable: allocate event

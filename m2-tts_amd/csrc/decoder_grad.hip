@@ -27,6 +27,7 @@
 #include <cstring>
 
 #include "decoder_grad_plan.h"
+#include "layer_grad.h"
 
 namespace m2 {
 
@@ -35,8 +36,6 @@ int32_t launch_linear(const float*, const float*, const float*, const float*, co
 int32_t launch_attention(const float*, const uint8_t*, int, int, int, int, float*, hipStream_t, bool force_f32 = false);
 
 namespace dgrad {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
@@ -116,94 +115,8 @@ __global__ __launch_bounds__(256) void lin_dx_kernel(const float* __restrict__ g
         return;
     }
     // the LayerNorm's backward over the workgroup's whole rows
-    const int xs = K + 1;
-    float* Xs = sm;                    // [64][K + 1]
-    float* stats = Xs + kRows * xs;    // [64][2]: mean, rstd
-    float* colp = stats + 2 * kRows;   // [4][2 K]: the waves' column sums
-    __syncthreads();
-    for (int i = tid; i < kRows * K; i += 256) {
-        const int row = i / K, k = i - row * K;
-        Xs[row * xs + k] = r0 + row < R ? ln_x[(size_t)(r0 + row) * K + k] : 0.f;
-    }
-    __syncthreads();
-    {
-        const int row = tid >> 2, part = tid & 3;
-        const float* xr = Xs + row * xs;
-        float s = 0.f;
-        for (int k = part; k < K; k += 4) s += xr[k];
-        s += __shfl_xor(s, 1);
-        s += __shfl_xor(s, 2);
-        const float mean = s / (float)K;
-        float v = 0.f;
-        for (int k = part; k < K; k += 4) {
-            const float dlt = xr[k] - mean;
-            v = fmaf(dlt, dlt, v);
-        }
-        v += __shfl_xor(v, 1);
-        v += __shfl_xor(v, 2);
-        if (part == 0) {
-            stats[2 * row] = mean;
-            stats[2 * row + 1] = 1.0f / sqrtf(v / (float)K + kLnEps);
-        }
-    }
-    __syncthreads();
-    float gam[KTM], cg[KTM], cb[KTM];
-#pragma unroll
-    for (int t = 0; t < KTM; ++t) {
-        const int col = 16 * t + li;
-        gam[t] = (t < kt && col < K) ? gamma[col] : 0.f;
-        cg[t] = cb[t] = 0.f;
-    }
-    const float invK = 1.0f / (float)K;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int row = lrow + r;
-        const float mean = stats[2 * row], rstd = stats[2 * row + 1];
-        float xh[KTM], m1 = 0.f, m2 = 0.f;
-#pragma unroll
-        for (int t = 0; t < KTM; ++t) {
-            const int col = 16 * t + li;
-            xh[t] = (t < kt && col < K) ? (Xs[row * xs + col] - mean) * rstd : 0.f;
-            const float a = acc[t][r] * gam[t];
-            m1 += a;
-            m2 = fmaf(a, xh[t], m2);
-            cg[t] = fmaf(acc[t][r], xh[t], cg[t]);
-            cb[t] += acc[t][r];
-        }
-        for (int o = 1; o < 16; o <<= 1) {
-            m1 += __shfl_xor(m1, o);
-            m2 += __shfl_xor(m2, o);
-        }
-        m1 *= invK;
-        m2 *= invK;
-        if (gx != nullptr && r0 + row < R) {
-#pragma unroll
-            for (int t = 0; t < KTM; ++t) {
-                const int col = 16 * t + li;
-                if (t < kt && col < K) {
-                    const size_t o = (size_t)(r0 + row) * K + col;
-                    const float v = rstd * (acc[t][r] * gam[t] - m1 - xh[t] * m2);
-                    gx[o] = g_res ? g_res[o] + v : v;
-                }
-            }
-        }
-    }
-    if (slots == nullptr) return;  // the same for every thread of the workgroup
-#pragma unroll
-    for (int t = 0; t < KTM; ++t) {
-        cg[t] += __shfl_xor(cg[t], 16);
-        cg[t] += __shfl_xor(cg[t], 32);
-        cb[t] += __shfl_xor(cb[t], 16);
-        cb[t] += __shfl_xor(cb[t], 32);
-        const int col = 16 * t + li;
-        if (g == 0 && t < kt && col < K) {
-            colp[wave * 2 * K + col] = cg[t];
-            colp[wave * 2 * K + K + col] = cb[t];
-        }
-    }
-    __syncthreads();
-    for (int i = tid; i < 2 * K; i += 256)
-        slots[(size_t)blockIdx.x * 2 * K + i] = ((colp[i] + colp[2 * K + i]) + colp[4 * K + i]) + colp[6 * K + i];
+    ln_bwd_rows<KTM>(acc, sm, ln_x, gamma, g_res, R, K, r0, gx,
+                     slots ? slots + (size_t)blockIdx.x * 2 * K : nullptr);
 }
 
 // grid (cdiv(N, 64), splits), 256 threads, DwPlan's lds.  Workgroup (bx, by) takes the rows
@@ -533,47 +446,16 @@ __global__ __launch_bounds__(256) void att_bwd_kv_kernel(const float* __restrict
         }
 }
 
-}  // namespace dgrad
-}  // namespace m2
+// ---- the launchers (layer_grad.h) -----------------------------------------------------
 
-namespace {
-using namespace m2;
-using dgrad::Dims;
-using dgrad::DxMode;
-using dgrad::LaunchRow;
-using dgrad::Step;
-
-dim3 grid_of(const LaunchRow& r) { return dim3(r.gx, r.gy, r.gz); }
-
-const char* kDimsMsg = "H a multiple of 8 with 2 H <= 256, head_dim 16, 32, 48 or 64, M >= 1, layers >= 1";
-
-// dst = (add ? dst : 0) + the sum over `slots` partials of n floats, `stride` floats apart.
 int32_t launch_finish(const float* part, size_t n, int slots, size_t stride, bool add, float* dst, hipStream_t st) {
-    const LaunchRow r = dgrad::finish_row(n);
-    hipLaunchKernelGGL(dgrad::dec_finish_kernel, grid_of(r), dim3(r.threads), 0, st, part, n, slots, stride, add ? 1 : 0,
-                       dst);
+    const LaunchRow r = finish_row(n);
+    hipLaunchKernelGGL(dec_finish_kernel, grid_of(r), dim3(r.threads), 0, st, part, n, slots, stride, add ? 1 : 0, dst);
     M2_LAUNCHED(r.kernel);
     return M2_OK;
 }
 
-// lin_dx_kernel and, in DX_LN mode, the finishes of its slots; part holds dx_part_floats.
-int32_t launch_dx(const float* gy, const float* w, DxMode mode, const float* aux, const float* gamma, const float* g_res,
-                  size_t R, int K, int N, float* gx, float* dgamma, float* dbeta, bool add, float* part,
-                  hipStream_t st) {
-    const LaunchRow r = dgrad::dx_row(R, K, mode);
-    const float* relu_of = mode == dgrad::DX_RELU ? aux : nullptr;
-    const float* ln_x = mode == dgrad::DX_LN ? aux : nullptr;
-    float* slots = (dgamma || dbeta) ? part : nullptr;
-    const int kt = dgrad::col_tiles(K);
-#define M2_DX(KTM)                                                                                                    \
-    hipLaunchKernelGGL(dgrad::lin_dx_kernel<KTM>, grid_of(r), dim3(r.threads), r.lds, st, gy, w, relu_of, ln_x, gamma, \
-                       g_res, (int)R, K, N, gx, slots)
-    if (kt <= 4) M2_DX(4);
-    else if (kt <= 8) M2_DX(8);
-    else M2_DX(16);
-#undef M2_DX
-    M2_LAUNCHED(r.kernel);
-    const int blocks = dgrad::dx_blocks(R);
+int32_t launch_ln_finish(const float* part, int K, int blocks, bool add, float* dgamma, float* dbeta, hipStream_t st) {
     if (dgamma) {
         const int32_t rc = launch_finish(part, (size_t)K, blocks, (size_t)2 * K, add, dgamma, st);
         if (rc != M2_OK) return rc;
@@ -582,18 +464,36 @@ int32_t launch_dx(const float* gy, const float* w, DxMode mode, const float* aux
     return M2_OK;
 }
 
-// lin_dw_kernel and the finishes; part holds dw_split's part_floats.
+int32_t launch_dx(const float* gy, const float* w, DxMode mode, const float* aux, const float* gamma, const float* g_res,
+                  size_t R, int K, int N, float* gx, float* dgamma, float* dbeta, bool add, float* part,
+                  hipStream_t st) {
+    const LaunchRow r = dx_row(R, K, mode);
+    const float* relu_of = mode == DX_RELU ? aux : nullptr;
+    const float* ln_x = mode == DX_LN ? aux : nullptr;
+    float* slots = (dgamma || dbeta) ? part : nullptr;
+    const int kt = col_tiles(K);
+#define M2_DX(KTM)                                                                                             \
+    hipLaunchKernelGGL(lin_dx_kernel<KTM>, grid_of(r), dim3(r.threads), r.lds, st, gy, w, relu_of, ln_x, gamma, \
+                       g_res, (int)R, K, N, gx, slots)
+    if (kt <= 4) M2_DX(4);
+    else if (kt <= 8) M2_DX(8);
+    else M2_DX(16);
+#undef M2_DX
+    M2_LAUNCHED(r.kernel);
+    return launch_ln_finish(part, K, dx_blocks(R), add, dgamma, dbeta, st);
+}
+
 int32_t launch_dw(const float* gy, const float* x, const float* ln_g, const float* ln_b, size_t R, int K, int N,
                   float* dw, float* db, bool add, float* part, hipStream_t st) {
-    const dgrad::DwPlan p = dgrad::dw_split(R, K, N);
+    const DwPlan p = dw_split(R, K, N);
     const size_t n = (size_t)N * K;
     float* partW = dw ? part : nullptr;
     float* partB = db ? part + (size_t)p.splits * n : nullptr;
     const dim3 grid(p.tiles, p.splits);
-    const int kt = dgrad::col_tiles(K);
+    const int kt = col_tiles(K);
 #define M2_DW(KTM)                                                                                              \
-    hipLaunchKernelGGL(dgrad::lin_dw_kernel<KTM>, grid, dim3(256), p.lds, st, gy, x, ln_g, ln_b, (int)R, K, N, \
-                       p.rps, partW, partB)
+    hipLaunchKernelGGL(lin_dw_kernel<KTM>, grid, dim3(256), p.lds, st, gy, x, ln_g, ln_b, (int)R, K, N, p.rps, \
+                       partW, partB)
     if (kt <= 4) M2_DW(4);
     else if (kt <= 8) M2_DW(8);
     else M2_DW(16);
@@ -608,15 +508,13 @@ int32_t launch_dw(const float* gy, const float* x, const float* ln_g, const floa
 }
 
 template <int HD>
-int32_t launch_att_bwd_hd(const float* qkv, const uint8_t* mask, const float* att, const float* d_att, int B, int N,
-                          int H, int heads, float scale, float* d_qkv, float* stats, hipStream_t st) {
-    const dim3 grid(cdiv(N, dgrad::kRows), heads, B);
-    const size_t lds = dgrad::att_lds_bytes(HD);
-    hipLaunchKernelGGL(dgrad::att_bwd_q_kernel<HD>, grid, dim3(256), lds, st, qkv, mask, att, d_att, N, H, scale, d_qkv,
-                       stats);
+static int32_t launch_att_bwd_hd(const float* qkv, const uint8_t* mask, const float* att, const float* d_att, int B,
+                                 int N, int H, int heads, float scale, float* d_qkv, float* stats, hipStream_t st) {
+    const dim3 grid(cdiv(N, kRows), heads, B);
+    const size_t lds = att_lds_bytes(HD);
+    hipLaunchKernelGGL(att_bwd_q_kernel<HD>, grid, dim3(256), lds, st, qkv, mask, att, d_att, N, H, scale, d_qkv, stats);
     M2_LAUNCHED("att_bwd_q_kernel");
-    hipLaunchKernelGGL(dgrad::att_bwd_kv_kernel<HD>, grid, dim3(256), lds, st, qkv, mask, d_att, stats, N, H, scale,
-                       d_qkv);
+    hipLaunchKernelGGL(att_bwd_kv_kernel<HD>, grid, dim3(256), lds, st, qkv, mask, d_att, stats, N, H, scale, d_qkv);
     M2_LAUNCHED("att_bwd_kv_kernel");
     return M2_OK;
 }
@@ -633,6 +531,57 @@ int32_t launch_att_bwd(const float* qkv, const uint8_t* mask, const float* att, 
         default: return fail(M2_E_SHAPE, "attention backward: head_dim must be 16, 32, 48 or 64");
     }
 }
+
+int32_t layer_forward(const float* x, const float* const* p, float* const* m, const uint8_t* mask, int B, int N, int H,
+                      int heads, hipStream_t st) {
+    const int R = B * N;
+    int32_t rc = launch_linear(x, p[P_N1_W], p[P_N1_B], p[P_QKV_W], nullptr, nullptr, ACT_NONE, R, H, 3 * H, m[MAP_QKV],
+                               st);
+    if (rc == M2_OK) rc = launch_attention(m[MAP_QKV], mask, B, N, H, heads, m[MAP_ATT], st);
+    if (rc == M2_OK)
+        rc = launch_linear(m[MAP_ATT], nullptr, nullptr, p[P_OUT_W], p[P_OUT_B], x, ACT_NONE, R, H, H, m[MAP_XMID], st);
+    if (rc == M2_OK)
+        rc = launch_linear(m[MAP_XMID], p[P_N2_W], p[P_N2_B], p[P_L1_W], p[P_L1_B], nullptr, ACT_RELU, R, H, 2 * H,
+                           m[MAP_H], st);
+    if (rc == M2_OK)
+        rc = launch_linear(m[MAP_H], nullptr, nullptr, p[P_L2_W], p[P_L2_B], m[MAP_XMID], ACT_NONE, R, 2 * H, H,
+                           m[MAP_XOUT], st);
+    return rc;
+}
+
+int32_t run_step(const Step& s, const Walk& w) {
+    const Geo& g = w.geo;
+    switch (s.kind) {
+        case STEP_DW:
+            if (!w.grad(s.dw) && !w.grad(s.db)) return M2_OK;
+            return launch_dw(w.buf(s.gy), w.buf(s.x), w.param(s.ln), s.ln >= 0 ? w.params[s.ln + 1] : nullptr, g.R, s.K,
+                             s.N, w.grad(s.dw), w.grad(s.db), w.add, w.bufs.part, w.st);
+        case STEP_DX: {
+            float* out = w.buf(s.out);  // null only for layer 0's input when nothing asks for it
+            if (!out && !w.grad(s.dgamma) && !w.grad(s.dbeta)) return M2_OK;
+            return launch_dx(w.buf(s.gy), w.params[s.w], s.mode, w.buf(s.aux), w.param(s.dgamma), w.buf(s.res), g.R, s.K,
+                             s.N, out, w.grad(s.dgamma), w.grad(s.dbeta), w.add, w.bufs.part, w.st);
+        }
+        case STEP_ATT:
+            return launch_att_bwd(w.buf(s.x), w.mask, w.buf(s.aux), w.buf(s.gy), g.B, g.N, g.H, g.heads, w.bufs.wide,
+                                  w.bufs.stats, w.st);
+        default: return fail(M2_E_ARG, "run_step: not a step of the layer walk");
+    }
+}
+
+}  // namespace dgrad
+}  // namespace m2
+
+namespace {
+using namespace m2;
+using dgrad::Dims;
+using dgrad::DxMode;
+using dgrad::launch_att_bwd;
+using dgrad::launch_dw;
+using dgrad::launch_dx;
+using dgrad::Step;
+
+const char* kDimsMsg = "H a multiple of 8 with 2 H <= 256, head_dim 16, 32, 48 or 64, M >= 1, layers >= 1";
 
 size_t tape_bytes(const Dims& d) {
     Sizer s;
@@ -689,20 +638,8 @@ int32_t m2_decoder_train_forward(const float* const* params, int32_t H, int32_t 
     const float* cur = x;
     int32_t rc = M2_OK;
     for (int l = 0; l < layers && rc == M2_OK; ++l) {
-        const float* const* p = params + dgrad::p_layer(l, 0);
         float** m = map + dgrad::map_of(l, 0);
-        rc = launch_linear(cur, p[dgrad::P_N1_W], p[dgrad::P_N1_B], p[dgrad::P_QKV_W], nullptr, nullptr, ACT_NONE, R, H,
-                           3 * H, m[dgrad::MAP_QKV], st);
-        if (rc == M2_OK) rc = launch_attention(m[dgrad::MAP_QKV], nullptr, B, T, H, heads, m[dgrad::MAP_ATT], st);
-        if (rc == M2_OK)
-            rc = launch_linear(m[dgrad::MAP_ATT], nullptr, nullptr, p[dgrad::P_OUT_W], p[dgrad::P_OUT_B], cur, ACT_NONE,
-                               R, H, H, m[dgrad::MAP_XMID], st);
-        if (rc == M2_OK)
-            rc = launch_linear(m[dgrad::MAP_XMID], p[dgrad::P_N2_W], p[dgrad::P_N2_B], p[dgrad::P_L1_W],
-                               p[dgrad::P_L1_B], nullptr, ACT_RELU, R, H, 2 * H, m[dgrad::MAP_H], st);
-        if (rc == M2_OK)
-            rc = launch_linear(m[dgrad::MAP_H], nullptr, nullptr, p[dgrad::P_L2_W], p[dgrad::P_L2_B], m[dgrad::MAP_XMID],
-                               ACT_NONE, R, 2 * H, H, m[dgrad::MAP_XOUT], st);
+        rc = dgrad::layer_forward(cur, params + dgrad::p_layer(l, 0), m, nullptr, B, T, H, heads, st);
         cur = m[dgrad::MAP_XOUT];
     }
     if (rc != M2_OK) return rc;
@@ -734,44 +671,22 @@ int32_t m2_decoder_backward(const float* const* params, int32_t H, int32_t M, in
     dgrad::Bufs bufs;
     dgrad::carve_backward(c, d, &bufs);
     if (!c.ok) return fail(M2_E_ARG, "m2_decoder_backward: workspace too small");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const bool acc = accumulate != 0;
-    const size_t R = dgrad::rows(d);
-    auto buf = [&](int id) -> float* {
-        switch (id) {
-            case dgrad::BUF_NONE: return nullptr;
-            case dgrad::BUF_X: return const_cast<float*>(x);
-            case dgrad::BUF_DMEL: return const_cast<float*>(d_mel);
-            case dgrad::BUF_DX: return d_x;
-            case dgrad::BUF_COT0: return bufs.cot[0];
-            case dgrad::BUF_COT1: return bufs.cot[1];
-            case dgrad::BUF_WIDE: return bufs.wide;
-            default: return map[id];
-        }
-    };
-    auto grad = [&](int i) -> float* { return i >= 0 ? grads[i] : nullptr; };
-    auto param = [&](int i) -> const float* { return i >= 0 ? params[i] : nullptr; };
+    dgrad::Walk w{};
+    w.params = params;
+    w.grads = grads;
+    w.maps = map;
+    w.named[-dgrad::BUF_X] = const_cast<float*>(x);
+    w.named[-dgrad::BUF_DMEL] = const_cast<float*>(d_mel);
+    w.named[-dgrad::BUF_DX] = d_x;
+    w.named[-dgrad::BUF_COT0] = bufs.cot[0];
+    w.named[-dgrad::BUF_COT1] = bufs.cot[1];
+    w.named[-dgrad::BUF_WIDE] = bufs.wide;
+    w.geo = dgrad::geo(d);
+    w.add = accumulate != 0;
+    w.bufs = bufs;
+    w.st = static_cast<hipStream_t>(stream);
     for (const Step& s : dgrad::plan_steps(d)) {
-        int32_t rc = M2_OK;
-        switch (s.kind) {
-            case dgrad::STEP_DW:
-                if (grad(s.dw) || grad(s.db))
-                    rc = launch_dw(buf(s.gy), buf(s.x), param(s.ln), s.ln >= 0 ? params[s.ln + 1] : nullptr, R, s.K, s.N,
-                                   grad(s.dw), grad(s.db), acc, bufs.part, st);
-                break;
-            case dgrad::STEP_DX: {
-                float* out = buf(s.out);  // null only for layer 0's input when the caller passes no d_x
-                if (out || grad(s.dgamma) || grad(s.dbeta))
-                    rc = launch_dx(buf(s.gy), params[s.w], s.mode, buf(s.aux), param(s.dgamma), buf(s.res), R, s.K, s.N,
-                                   out, grad(s.dgamma), grad(s.dbeta), acc, bufs.part, st);
-                break;
-            }
-            case dgrad::STEP_ATT:
-                rc = launch_att_bwd(map[dgrad::map_of(s.layer, dgrad::MAP_QKV)], nullptr,
-                                    map[dgrad::map_of(s.layer, dgrad::MAP_ATT)], buf(s.gy), B, T, H, heads, bufs.wide,
-                                    bufs.stats, st);
-                break;
-        }
+        const int32_t rc = dgrad::run_step(s, w);
         if (rc != M2_OK) return rc;
     }
     return M2_OK;

@@ -153,6 +153,19 @@ _SIGNATURES = {
     "m2_linear_backward_input": (c_i32, [c_vp] * 6 + [c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_size, c_vp]),
     "m2_linear_backward_weight_workspace_bytes": (c_size, [c_i32, c_i32, c_i32]),
     "m2_linear_backward_weight": (c_i32, [c_vp] * 4 + [c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_size, c_vp]),
+    "m2_encoder_tape_bytes": (c_size, [c_i32] * 6),
+    "m2_encoder_tape_map": (c_i32, [c_i32] * 7 + [c_vp, c_vp]),
+    "m2_encoder_train_forward": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp,
+                                         c_size, c_vp]),
+    "m2_encoder_backward_workspace_bytes": (c_size, [c_i32] * 6),
+    "m2_encoder_backward": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32,
+                                    c_vp, c_size, c_vp]),
+    "m2_debug_encoder_grad_plan": (c_i32, [c_i32] * 6 + [c_vp, c_size]),
+    "m2_embedding_backward_workspace_bytes": (c_size, [c_i32, c_i32, c_i32]),
+    "m2_embedding_backward": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_f32, c_vp, c_i32, c_vp, c_size, c_vp]),
+    "m2_layer_norm_backward_workspace_bytes": (c_size, [c_i32, c_i32]),
+    "m2_layer_norm_backward": (c_i32, [c_vp] * 4 + [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_size, c_vp]),
+    "m2_length_regulator_backward": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "m2_front_bytes": (c_size, [c_vp, c_i32, c_i32]),
     "m2_inference_workspace_bytes": (c_size, [c_vp, c_i32, c_i32, c_i32]),
     "m2_inference_front": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_vp, c_size, c_vp, c_size, c_vp, c_vp]),

@@ -702,6 +702,172 @@ def linear_backward_weight(g_y: Tensor, x: Tensor, *, ln: Optional[tuple] = None
     return dw, db
 
 
+ENCODER_LAYER_PARAMS = DECODER_LAYER_PARAMS
+ENCODER_TAIL_PARAMS = 2
+ENCODER_TAPE_NAMES = DECODER_TAPE_NAMES
+
+
+def _encoder_params(params, heads: int):
+    """TextEncoder's 1 + 11 layers + 2 parameters (parameters() order) as contiguous float32 device tensors,
+    their pointer array, and the dimensions (V, H, layers, heads)."""
+    keep = [f32c(p.detach()) for p in params]
+    layers, tail = divmod(len(keep) - 1 - ENCODER_TAIL_PARAMS, ENCODER_LAYER_PARAMS)
+    if layers < 1 or tail != 0:
+        raise ValueError(f"encoder: 1 + 11 layers + 2 parameters in parameters() order, got {len(keep)}")
+    require_device(*keep, what="encoder parameter")
+    V, H = keep[0].shape
+    return keep, (ctypes.c_void_p * len(keep))(*[t.data_ptr() for t in keep]), (int(V), int(H), layers, int(heads))
+
+
+def _encoder_inputs(ids: Tensor, key_mask: Optional[Tensor]):
+    require_device(ids, key_mask, what="encoder")
+    if ids.dim() != 2:
+        raise ValueError(f"encoder: ids must be [B, S], got {tuple(ids.shape)}")
+    if key_mask is not None and tuple(key_mask.shape) != tuple(ids.shape):
+        raise ValueError(f"encoder: the key mask must be {tuple(ids.shape)}, got {tuple(key_mask.shape)}")
+    return ids.to(torch.int64).contiguous(), _key_mask(key_mask)
+
+
+def encoder_supported(V: int, H: int, layers: int, heads: int) -> bool:
+    """Whether m2_encoder_backward takes a TextEncoder of these dimensions (host arithmetic only)."""
+    return int(_lib.load().m2_encoder_tape_bytes(V, H, layers, heads, 1, 1)) != 0
+
+
+def encoder_train_forward(params, ids: Tensor, pe: Tensor, key_mask: Optional[Tensor], heads: int):
+    """TextEncoder's forward from its raw parameters, keeping a tape (m2_encoder_train_forward): (out [B,S,H],
+    bit-equal to the stand-alone module's forward, and the tape, a uint8 tensor that ``encoder_tape_maps``
+    names and ``encoder_backward`` reads).  ``pe``: the positional table's rows [>= S, H]; ``key_mask``
+    [B,S] (True / non-zero = attend) or None."""
+    keep, ptrs, dims = _encoder_params(params, heads)
+    ids, mask = _encoder_inputs(ids, key_mask)
+    B, S = ids.shape
+    dev = ids.device
+    require_device(pe, what="encoder")
+    pe = f32c(pe)
+    if pe.dim() != 2 or pe.shape[0] < S or pe.shape[1] != dims[1]:
+        raise ValueError(f"encoder: the positional table must be [>= {S}, {dims[1]}], got {tuple(pe.shape)}")
+    need = int(_lib.load().m2_encoder_tape_bytes(*dims, B, S))
+    if need == 0:
+        raise M2Error(f"encoder_train_forward: unsupported shape (V, H, layers, heads) = {dims}, B={B} S={S}")
+    tape = torch.empty(need, dtype=torch.uint8, device=dev)
+    out = torch.empty(B, S, dims[1], device=dev, dtype=torch.float32)
+    _lib.call("m2_encoder_train_forward", ptrs, *dims, _ptr(ids), _ptr(pe), _ptr(mask), B, S, _ptr(out), _ptr(tape),
+              tape.numel(), stream_handle(dev))
+    return out, tape
+
+
+def encoder_tape_maps(tape: Tensor, V: int, H: int, layers: int, heads: int, B: int, S: int):
+    """The maps of a tape as float32 views (m2_encoder_tape_map): (x0 [B,S,H], the embedding's output, and
+    one dict per layer as ``decoder_tape_maps``)."""
+    lib = _lib.load()
+    flat = tape[:tape.numel() // 4 * 4].view(torch.float32)
+    off, width = ctypes.c_size_t(), ctypes.c_int32()
+
+    def view(index):
+        _lib.check(lib.m2_encoder_tape_map(V, H, layers, heads, B, S, index, ctypes.byref(off), ctypes.byref(width)),
+                   "m2_encoder_tape_map")
+        return flat[off.value:off.value + B * S * width.value].view(B, S, width.value)
+
+    n = len(ENCODER_TAPE_NAMES)
+    return view(0), [{name: view(1 + n * layer + i) for i, name in enumerate(ENCODER_TAPE_NAMES)}
+                     for layer in range(layers)]
+
+
+def encoder_backward(params, ids: Tensor, key_mask: Optional[Tensor], tape: Tensor, d_out: Tensor, heads: int,
+                     need=None, accumulate=False):
+    """The gradients of TextEncoder given d_out [B,S,H] (m2_encoder_backward): the 1 + 11 layers + 2
+    gradients in parameters() order, None where ``need[i]`` is false.  ``accumulate``: a list of that many
+    tensors (or None entries) to add the gradients to instead of new tensors."""
+    keep, ptrs, dims = _encoder_params(params, heads)
+    ids, mask = _encoder_inputs(ids, key_mask)
+    B, S = ids.shape
+    dev = ids.device
+    require_device(tape, d_out, what="encoder_backward")
+    d_out = f32c(d_out.detach().to(torch.float32))
+    if tuple(d_out.shape) != (B, S, dims[1]):
+        raise ValueError(f"encoder_backward: d_out must be {(B, S, dims[1])}, got {tuple(d_out.shape)}")
+    lib = _lib.load()
+    tape_bytes = int(lib.m2_encoder_tape_bytes(*dims, B, S))
+    if tape_bytes == 0:
+        raise M2Error(f"encoder_backward: unsupported shape (V, H, layers, heads) = {dims}, B={B} S={S}")
+    if tape.numel() < tape_bytes:
+        raise ValueError("encoder_backward: the tape is not that of this shape")
+    onto = accumulate if accumulate else None
+    want = [True] * len(keep) if need is None else [bool(n) for n in need]
+    grads = []
+    for i, (p, w) in enumerate(zip(keep, want)):
+        if not w:
+            grads.append(None)
+        elif onto is not None and onto[i] is not None:
+            grads.append(onto[i])
+        else:
+            grads.append(torch.empty_like(p) if onto is None else torch.zeros_like(p))
+    gp = (ctypes.c_void_p * len(keep))(*[_ptr(g) for g in grads])
+    ws = torch.empty(max(int(lib.m2_encoder_backward_workspace_bytes(*dims, B, S)), 1), dtype=torch.uint8, device=dev)
+    _lib.call("m2_encoder_backward", ptrs, *dims, _ptr(ids), _ptr(mask), B, S, _ptr(tape), _ptr(d_out), gp,
+              0 if onto is None else 1, _ptr(ws), ws.numel(), stream_handle(dev))
+    return grads
+
+
+def embedding_backward(ids: Tensor, d_x: Tensor, vocab: int, scale: float = 1.0, accumulate: Optional[Tensor] = None):
+    """d_emb [vocab, H] = scale * the sum of d_x [.., H] over the positions whose id is the row
+    (m2_embedding_backward); ids outside [0, vocab) contribute nothing.  ``accumulate``: a [vocab, H] tensor
+    to add to instead of a new one."""
+    require_device(ids, d_x, accumulate, what="embedding_backward")
+    ids, d_x = ids.to(torch.int64).contiguous(), f32c(d_x)
+    H = d_x.shape[-1]
+    R = ids.numel()
+    if d_x.numel() != R * H:
+        raise ValueError(f"embedding_backward: d_x {tuple(d_x.shape)} does not fit ids {tuple(ids.shape)}")
+    dev = d_x.device
+    vocab = int(vocab)
+    if accumulate is not None and _like(accumulate, (vocab, H), "embedding_backward: accumulate") is not accumulate:
+        raise ValueError("embedding_backward: accumulate must be contiguous float32")
+    d_emb = accumulate if accumulate is not None else torch.empty(vocab, H, device=dev, dtype=torch.float32)
+    ws = torch.empty(max(int(_lib.load().m2_embedding_backward_workspace_bytes(R, vocab, H)), 1), dtype=torch.uint8,
+                     device=dev)
+    _lib.call("m2_embedding_backward", _ptr(ids), _ptr(d_x), R, vocab, H, float(scale), _ptr(d_emb),
+              0 if accumulate is None else 1, _ptr(ws), ws.numel(), stream_handle(dev))
+    return d_emb
+
+
+def layer_norm_backward(g_y: Tensor, x: Tensor, gamma: Tensor, g_res: Optional[Tensor] = None):
+    """(g_x, dgamma, dbeta) of y = LayerNorm(x; gamma, beta) over the last dim given g_y
+    (m2_layer_norm_backward); g_x is the input's cotangent plus ``g_res``."""
+    require_device(g_y, x, gamma, g_res, what="layer_norm_backward")
+    g_y, x = f32c(g_y), f32c(x)
+    K = x.shape[-1]
+    R = x.numel() // K if K else 0
+    gamma = _vec(gamma, K, "layer_norm_backward: gamma")
+    g_y = _like(g_y, x.shape, "layer_norm_backward: g_y")
+    g_res = _like(g_res, x.shape, "layer_norm_backward: g_res")
+    dev = x.device
+    g_x = torch.empty_like(x)
+    dg, db = torch.empty(K, device=dev, dtype=torch.float32), torch.empty(K, device=dev, dtype=torch.float32)
+    ws = torch.empty(max(int(_lib.load().m2_layer_norm_backward_workspace_bytes(R, K)), 1), dtype=torch.uint8,
+                     device=dev)
+    _lib.call("m2_layer_norm_backward", _ptr(g_y), _ptr(x), _ptr(gamma), _ptr(g_res), R, K, _ptr(g_x), _ptr(dg),
+              _ptr(db), _ptr(ws), ws.numel(), stream_handle(dev))
+    return g_x, dg, db
+
+
+def regulate_backward(d_reg: Tensor, cum: Tensor, S: int) -> Tensor:
+    """The adjoint of ``expand_frames`` (m2_length_regulator_backward): d_enc [B,S,H] given d_reg [B,T_out,H]
+    and the prefix sums cum [B,S+1] the forward expanded with.  Durations get no gradient."""
+    require_device(d_reg, cum, what="length_regulator")
+    d_reg = f32c(d_reg)
+    B, T_out, H = d_reg.shape
+    S = int(S)
+    if tuple(cum.shape) != (B, S + 1) or cum.dtype != torch.int32:
+        raise ValueError(f"regulate_backward: cum must be int32 {(B, S + 1)}, got {cum.dtype} {tuple(cum.shape)}")
+    d_enc = torch.empty(B, S, H, device=d_reg.device, dtype=torch.float32)
+    if d_enc.numel() == 0:
+        return d_enc
+    _lib.call("m2_length_regulator_backward", _ptr(d_reg), _ptr(cum.contiguous()), B, S, H, T_out, _ptr(d_enc),
+              stream_handle(d_reg.device))
+    return d_enc
+
+
 def embed_positional(ids: Tensor, emb: Tensor, pe: Tensor, scale: float) -> Tensor:
     """y[b,s,:] = emb[ids[b,s],:] * scale + pe[s,:]; ids outside [0, vocab) read a zero row."""
     require_device(ids, emb, pe, what="embedding")
@@ -798,13 +964,19 @@ def regulate(enc: Tensor, durations: Tensor, max_length: Optional[int] = None, s
 
     One device->host read of the batch maximum frame count, only when
     max_length is not given (it sizes the output)."""
+    return regulate_with_counts(enc, durations, max_length, scale)[0]
+
+
+def regulate_with_counts(enc: Tensor, durations: Tensor, max_length: Optional[int] = None, scale: float = 1.0):
+    """``regulate`` and the prefix sums it expanded with: (out [B,T_out,H], cum [B,S+1] int32), what
+    ``regulate_backward`` reads."""
     require_device(enc, durations, what="length_regulator")
     if max_length is not None:
         cum, _, _ = frame_counts(durations, scale)
-        return expand_frames(enc, cum, max_length)
+        return expand_frames(enc, cum, max_length), cum
     cum, _, _, t_max = frame_counts_sync(durations, scale)
     # an utterance with no frames becomes one zero frame (tts_model.py:158-160)
-    return expand_frames(enc, cum, max(1, t_max))
+    return expand_frames(enc, cum, max(1, t_max)), cum
 
 
 def batchnorm_eval_affine(weight: Tensor, bias: Tensor, mean: Tensor, var: Tensor, eps: float):

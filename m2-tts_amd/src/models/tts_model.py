@@ -66,9 +66,43 @@ def _owner_handle(stage: nn.Module, attr: str, device: torch.device):
     return owner._hip(device)
 
 
+class _EncoderGrad(torch.autograd.Function):
+    """TextEncoder.forward with a graph: ops.encoder_train_forward on the
+    module's own parameters, and ops.encoder_backward on grad_output (once
+    differentiable).  Arguments: ids, the positional rows, the key mask or
+    None, the head count, then the 1 + 11 layers + 2 parameters in
+    parameters() order."""
+
+    @staticmethod
+    def forward(ctx, ids, pe, mask, heads, *params):
+        out, tape = ops.encoder_train_forward(params, ids, pe, mask, heads)
+        ctx.save_for_backward(ids, *params)
+        ctx.tape, ctx.heads, ctx.mask = tape, heads, mask
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        ids, *params = ctx.saved_tensors
+        grads = ops.encoder_backward(params, ids, ctx.mask, ctx.tape, grad_output, ctx.heads,
+                                     need=ctx.needs_input_grad[4:])
+        return (None, None, None, None, *grads)
+
+
 class TextEncoder(nn.Module):
     """Embedding*sqrt(H) + positional table, pre-LN transformer layers with a
-    key-padding mask, final LayerNorm (reference tts_model.py:19-89)."""
+    key-padding mask, final LayerNorm (reference tts_model.py:19-89).
+
+    ``enable_backward()`` gives ``forward`` a graph: when gradients are enabled
+    and a parameter requires grad, the output comes from the per-op path on
+    the module's own parameters (inside an M2TTSModel too: no handle, the
+    stand-alone module's bits) and carries a ``grad_fn`` whose backward fills
+    the 1 + 11 layers + 2 ``.grad`` on the GPU; the mask is returned as without
+    it.  The gradient is that of the function this module computes: no dropout
+    (models/components.py).  Off by default; with it off, under ``no_grad`` or
+    with nothing requiring grad, ``forward`` is unchanged."""
+
+    backward_enabled = False
 
     def __init__(self, vocab_size: int = 256, hidden_dim: int = 64, num_layers: int = 2, num_heads: int = 2,
                  dropout: float = 0.1, max_seq_len: int = 1000):
@@ -83,7 +117,41 @@ class TextEncoder(nn.Module):
         self.dropout = nn.Dropout(dropout)
         self.apply(initialize_weights)
 
+    def _dims(self) -> Tuple[int, int, int, int]:
+        """(V, H, layers, heads)."""
+        v, h = self.embedding.weight.shape
+        heads = self.layers[0].self_attn.num_heads if len(self.layers) else 0
+        return int(v), int(h), len(self.layers), int(heads)
+
+    def enable_backward(self, enabled: bool = True) -> "TextEncoder":
+        """Switch the graph of ``forward`` on or off (a plain attribute, no
+        state_dict entry).  Supported: a vocabulary of 1 to 65536, H a multiple
+        of 8 with 2 H <= 256, head_dim in {16, 32, 48, 64}, at least one
+        layer."""
+        if enabled:
+            v, h, layers, heads = self._dims()
+            ok = (layers >= 1 and 1 <= v <= 65536 and h % 8 == 0 and 2 * h <= 256 and heads >= 1 and h % heads == 0
+                  and h // heads in (16, 32, 48, 64) and self.embedding.padding_idx is None
+                  and all(la.ffn.linear1.out_features == 2 * h for la in self.layers))
+            if not ok:
+                raise NotImplementedError(f"TextEncoder.enable_backward: a vocabulary of 1 to 65536, hidden_dim a "
+                                          f"multiple of 8 up to 128, head_dim 16, 32, 48 or 64 and at least one layer; "
+                                          f"got vocabulary {v}, hidden_dim {h}, {heads} heads, {layers} layers")
+        self.backward_enabled = bool(enabled)
+        return self
+
     def forward(self, phoneme_ids: Tensor, lengths: Optional[Tensor] = None) -> Tuple[Tensor, Optional[Tensor]]:
+        if self.backward_enabled and torch.is_grad_enabled():
+            params = list(self.parameters())
+            if any(p.requires_grad for p in params):
+                ops.require_device(phoneme_ids, lengths, *params, what="TextEncoder")
+                s = phoneme_ids.shape[1]
+                if s > self.pos_encoding.pe.shape[1]:
+                    raise RuntimeError(f"sequence length {s} exceeds the positional table "
+                                       f"({self.pos_encoding.pe.shape[1]})")
+                mask = create_padding_mask(lengths, s) if lengths is not None else None
+                out = _EncoderGrad.apply(phoneme_ids, self.pos_encoding.pe[0, :s], mask, self._dims()[3], *params)
+                return out, mask
         hm = _owner_handle(self, "text_encoder", phoneme_ids.device)
         if hm is not None:
             return hm.text_encoder(phoneme_ids, lengths)
@@ -112,13 +180,49 @@ class DurationPredictor(nn.Module):
         return self.predictor(x, _act=ops.ACT_SOFTPLUS).squeeze(1)
 
 
+class _RegulateGrad(torch.autograd.Function):
+    """LengthRegulator.forward with a graph: ops.regulate's own launches
+    (with its one host read when max_length is None), keeping the prefix sums;
+    the backward is the expansion's adjoint, ops.regulate_backward (once
+    differentiable).  Durations get no gradient: the reference takes
+    int(duration.item())."""
+
+    @staticmethod
+    def forward(ctx, encoder_output, durations, max_length):
+        out, cum = ops.regulate_with_counts(encoder_output, durations, max_length)
+        ctx.cum, ctx.phonemes = cum, encoder_output.shape[1]
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        return ops.regulate_backward(grad_output, ctx.cum, ctx.phonemes), None, None
+
+
 class LengthRegulator(nn.Module):
     """Repeat each phoneme row int(duration) times, pad/truncate to the batch
     maximum or ``max_length`` (reference tts_model.py:120-178).  GPU scan +
     gather; truncation toward zero and the all-zero-durations case (one zero
-    frame) follow the reference."""
+    frame) follow the reference.
+
+    ``enable_backward()`` gives ``forward`` a graph: when gradients are enabled
+    and ``encoder_output`` requires grad, the result carries a ``grad_fn``
+    whose backward sums each phoneme's frames back into ``encoder_output.grad``
+    on the GPU; durations get no gradient.  Off by default; with it off, under
+    ``no_grad`` or with ``encoder_output`` not requiring grad, ``forward`` is
+    unchanged."""
+
+    backward_enabled = False
+
+    def enable_backward(self, enabled: bool = True) -> "LengthRegulator":
+        """Switch the graph of ``forward`` on or off (a plain attribute, no
+        state_dict entry)."""
+        self.backward_enabled = bool(enabled)
+        return self
 
     def forward(self, encoder_output: Tensor, durations: Tensor, max_length: Optional[int] = None) -> Tensor:
+        if self.backward_enabled and torch.is_grad_enabled() and encoder_output.requires_grad:
+            return _RegulateGrad.apply(encoder_output, durations.detach(), max_length)
         return ops.regulate(encoder_output, durations, max_length)
 
 

@@ -18,6 +18,8 @@
 // backward kernels' launch plans against their limits, and the spectral backward's
 // workspace carve against its frame count.
 // The decoder's gradient plan (csrc/decoder_grad_plan.h) is checked the same way (check_decoder_grad).
+// The text encoder's gradient plan (csrc/encoder_grad_plan.h) likewise (check_encoder_grad), with the
+// embedding's split over the positions.
 // The vocoder's gradient plan (csrc/vocoder_grad_plan.h) runs here too: the tape and the backward's
 // workspace against a plain restatement of their formulas, the carved regions against each other,
 // and every launch row against the LDS and grid limits.
@@ -32,6 +34,7 @@
 #include "losses_plan.h"
 #include "m2_model.h"
 #include "decoder_grad_plan.h"
+#include "encoder_grad_plan.h"
 #include "vocoder_grad_plan.h"
 #include "vocoder_launch.h"
 #include "vocoder_pipe.h"
@@ -926,6 +929,121 @@ static void check_decoder_grad() {
     std::printf(" (%d plans, %d rows)\n", plans, rows_seen);
 }
 
+// The text encoder's gradient plan (csrc/encoder_grad_plan.h) over the stage1 and stage2 training shapes
+// and the test cases.  Restated plainly: the tape is x0 [R, H] and then the decoder's five maps per layer;
+// the workspace is the decoder's, its partials the widest of the final norm's slots, the layers' weight
+// gradients and the embedding's [splits][V][H]; a vocabulary row's positions are split into whole
+// 64-position chunks, about 256 workgroups in all.  Sizes, overlaps and launch limits as check_decoder_grad.
+static void check_encoder_grad() {
+    int bad = 0, plans = 0, rows_seen = 0;
+    const int shapes[][6] = {{256, 64, 2, 2, 32, 100}, {256, 96, 3, 2, 8, 100}, {256, 64, 2, 2, 2, 7},
+                             {256, 96, 3, 2, 1, 5},    {5, 32, 1, 2, 3, 1},     {40, 64, 2, 2, 2, 130},
+                             {300, 96, 1, 2, 1, 67},   {256, 128, 1, 2, 1, 65}, {256, 64, 1, 4, 3, 33}};
+    for (const auto& sh : shapes) {
+        const egrad::Dims d{sh[0], sh[1], sh[2], sh[3], sh[4], sh[5]};
+        bad += !egrad::dims_ok(d);
+        ++plans;
+        const size_t R = (size_t)d.B * d.S, H = (size_t)d.H, V = (size_t)d.V;
+        // the tape
+        size_t off = 0;
+        std::vector<size_t> at, len;
+        auto put = [&](size_t floats) {
+            off = (off + 255) / 256 * 256;
+            at.push_back(off);
+            len.push_back(floats * 4);
+            off += floats * 4;
+        };
+        put(R * H);
+        for (int l = 0; l < d.layers; ++l)
+            for (const size_t w : {3 * H, H, H, 2 * H, H}) put(R * w);
+        Sizer ts;
+        egrad::carve_tape(ts, d, nullptr);
+        bad += ts.off != off || at.size() != (size_t)egrad::n_maps(d);
+        std::vector<char> mem(off);
+        Carve tc(mem.data(), mem.size()), less(mem.data(), mem.size() - 1);
+        std::vector<float*> maps(at.size()), none(at.size());
+        egrad::carve_tape(tc, d, maps.data());
+        egrad::carve_tape(less, d, none.data());
+        bad += !tc.ok || less.ok;
+        for (size_t i = 0; i < at.size() && tc.ok; ++i) {
+            bad += reinterpret_cast<char*>(maps[i]) != mem.data() + at[i];
+            if (i > 0) bad += at[i] < at[i - 1] + len[i - 1];  // no overlap
+            bad += R * egrad::map_width(d, (int)i) * 4 != len[i];
+        }
+        // the embedding's split and the workspace
+        const long long chunks = (long long)((R + 63) / 64);
+        const long long want = std::max<long long>(1, std::min<long long>(chunks, (256 + (long long)V - 1) / (long long)V));
+        const long long rps = (chunks + want - 1) / want * 64, splits = ((long long)R + rps - 1) / rps;
+        const egrad::EmbPlan ep = egrad::emb_split(R, d.V, d.H);
+        bad += ep.rps != rps || ep.splits != splits || ep.part_floats != (size_t)splits * V * H || splits < 1 ||
+               rps * splits < (long long)R || (V >= 256 && splits != 1) || (long long)V * splits > 256 + (long long)V;
+        size_t part = std::max((R + 63) / 64 * 2 * H, ep.part_floats);
+        for (const dgrad::Step& s : egrad::plan_steps(d)) {
+            if (s.kind != dgrad::STEP_DW) continue;
+            const size_t need = dgrad::dw_split(R, s.K, s.N).part_floats;  // check_decoder_grad restates it
+            bad += egrad::step_part_floats(s, d) != need;
+            part = std::max(part, need);
+        }
+        bad += egrad::part_floats(d) != part;
+        size_t woff = 0;
+        const size_t floats[5] = {R * H, R * H, R * 3 * H, (size_t)d.B * d.heads * d.S * 3, part};
+        for (const size_t f : floats) woff = (woff + 255) / 256 * 256 + f * 4;
+        Sizer ws;
+        egrad::carve_backward(ws, d, nullptr);
+        bad += ws.off != woff;
+        {
+            std::vector<char> wm(woff);
+            Carve wc(wm.data(), wm.size()), wless(wm.data(), wm.size() - 1);
+            dgrad::Bufs b{}, nb{};
+            egrad::carve_backward(wc, d, &b);
+            egrad::carve_backward(wless, d, &nb);
+            bad += !wc.ok || wless.ok;
+            const char* p[6] = {reinterpret_cast<char*>(b.cot[0]), reinterpret_cast<char*>(b.cot[1]),
+                                reinterpret_cast<char*>(b.wide),   reinterpret_cast<char*>(b.stats),
+                                reinterpret_cast<char*>(b.part),   wm.data() + wm.size()};
+            bad += p[0] != wm.data();
+            for (int i = 0; i < 4; ++i) bad += p[i + 1] < p[i] + floats[i] * 4;  // no overlap
+            bad += p[5] != p[4] + floats[4] * 4;
+        }
+        // the rows
+        int steps = 0;
+        const std::vector<dgrad::Step> plan = egrad::plan_steps(d);
+        for (const dgrad::Step& s : plan) {
+            ++steps;
+            std::vector<loss::LaunchRow> rows;
+            const bool ln = s.kind == dgrad::STEP_LN || (s.kind == dgrad::STEP_DX && s.mode == dgrad::DX_LN);
+            const bool w = s.kind == dgrad::STEP_DW || s.kind == dgrad::STEP_EMB;
+            egrad::step_rows(s, d, true, w ? s.dw >= 0 : ln, w ? s.db >= 0 : ln, rows);
+            bad += rows.empty();
+            if (s.kind == dgrad::STEP_DX) bad += !dgrad::dx_ok(s.K, s.N, s.mode);
+            if (s.kind == dgrad::STEP_DW) bad += !dgrad::dw_ok(s.K, s.N);
+            if (s.kind == dgrad::STEP_LN) bad += !egrad::ln_ok(s.K);
+            if (s.kind == dgrad::STEP_EMB) bad += !egrad::emb_ok(d.V, d.H);
+            for (const loss::LaunchRow& r : rows) {
+                ++rows_seen;
+                bad += r.lds > (size_t)loss::kMaxLds || r.gx < 1 || r.gy < 1 || r.gz < 1 || r.gy > 65535 ||
+                       r.gz > 65535 || r.threads != 256;
+            }
+        }
+        bad += steps != 2 + 9 * d.layers || plan.front().kind != dgrad::STEP_LN || plan.back().kind != dgrad::STEP_EMB;
+        // layer 0's qx reads x0 and writes the cotangent the embedding reads
+        const dgrad::Step& qx0 = plan[plan.size() - 2];
+        bad += qx0.aux != 0 || qx0.out != dgrad::BUF_DX || plan.back().gy != dgrad::BUF_DX || plan.back().dw != 0;
+        const std::string line = egrad::print_plan(d);
+        bad += line.find(" nx:ln_bwd_kernel[grid=") == std::string::npos ||
+               line.find(" ew:emb_dw_kernel[grid=") == std::string::npos;
+        const loss::LaunchRow lr = egrad::lr_row(d.B, d.S);
+        bad += lr.gx != (unsigned)((d.S + 3) / 4) || lr.gy != (unsigned)d.B || lr.threads != 256 || lr.lds != 0;
+    }
+    bad += egrad::dims_ok(egrad::Dims{0, 64, 2, 2, 1, 4}) || egrad::dims_ok(egrad::Dims{65537, 64, 2, 2, 1, 4}) ||
+           egrad::dims_ok(egrad::Dims{256, 60, 2, 2, 1, 4}) || egrad::dims_ok(egrad::Dims{256, 160, 2, 4, 1, 4}) ||
+           egrad::dims_ok(egrad::Dims{256, 64, 2, 8, 1, 4}) || egrad::dims_ok(egrad::Dims{256, 64, 0, 2, 1, 4});
+    bad += !egrad::dims_ok(egrad::Dims{65536, 128, 1, 2, 1, 4}) || !egrad::dims_ok(egrad::Dims{1, 64, 1, 2, 1, 4});
+    std::printf("encoder_grad:");
+    expect("plans_match", bad == 0 && plans == 9, true);
+    std::printf(" (%d plans, %d rows)\n", plans, rows_seen);
+}
+
 int main() {
     check_strips();
     check_launch_plans();
@@ -934,6 +1052,7 @@ int main() {
     check_spectral_bwd();
     check_vocoder_grad();
     check_decoder_grad();
+    check_encoder_grad();
     const m2_config stage1{256, 64, 64, 2, 2, 2, 128, 1000}, stage2{256, 96, 80, 3, 3, 2, 256, 1000};
     for (const bool huge : {false, true}) {
         check(2 * huge, "stage1", stage1, huge);

@@ -35,7 +35,14 @@ reaching the vocoder's parameters (gen_step_vocoder_ms; only when --length is
 (decoder_backward_ms, decoder_backward_over_forward), and the same generator
 step with mel = decoder(x) feeding both the mel loss and the vocoder
 (gen_step_decoder_ms, under gen_step_vocoder_ms's condition).  --decoder-only
-prints the two decoder lines alone (for a kernel trace).  Each
+prints the two decoder lines alone (for a kernel trace).  The text
+encoder's training side and the length regulator's adjoint (DESIGN 4.6f;
+--vocab, --hidden, --enc-layers, --heads, --phonemes, default the stage1
+encoder at 100 phonemes): --encoder-only prints m2_encoder_train_forward
+(encoder_train_forward_ms), m2_encoder_backward with every gradient
+(encoder_backward_ms, encoder_backward_over_forward) and
+m2_length_regulator_backward at --frames frames per utterance
+(regulator_adjoint_ms), alone.  Each
 figure is the median of --iters timed calls after --warmup untimed ones.
 """
 import argparse
@@ -85,6 +92,31 @@ def decoder_lines(out, args, dev):
     return dec, x
 
 
+def encoder_lines(out, args, dev):
+    """The text encoder's training forward and backward and the length regulator's adjoint."""
+    from m2amd import ops
+    from models.tts_model import TextEncoder
+    B, S, T, H = args.batch, args.phonemes, args.frames, args.hidden
+    enc = TextEncoder(args.vocab, H, args.enc_layers, args.heads).to(dev)
+    params = [p.detach() for p in enc.parameters()]
+    pe = enc.pos_encoding.pe[0]
+    ids = torch.randint(0, args.vocab, (B, S), device=dev)
+    mask = torch.arange(S, device=dev)[None, :] < torch.randint(S // 2, S + 1, (B, 1), device=dev)
+    _, tape = ops.encoder_train_forward(params, ids, pe, mask, args.heads)
+    d_out = torch.randn(B, S, H, device=dev)
+    out["encoder_train_forward_ms"] = timed(lambda: ops.encoder_train_forward(params, ids, pe, mask, args.heads),
+                                            args.warmup, args.iters)
+    out["encoder_backward_ms"] = timed(lambda: ops.encoder_backward(params, ids, mask, tape, d_out, args.heads),
+                                       args.warmup, args.iters)
+    out["encoder_backward_over_forward"] = out["encoder_backward_ms"] / out["encoder_train_forward_ms"]
+    # every utterance fills its T frames: T // S per phoneme and the remainder on the first ones
+    durations = torch.full((B, S), T // S, dtype=torch.int64, device=dev)
+    durations[:, :T % S] += 1
+    cum, _, _ = ops.frame_counts(durations)
+    d_reg = torch.randn(B, T, H, device=dev)
+    out["regulator_adjoint_ms"] = timed(lambda: ops.regulate_backward(d_reg, cum, S), args.warmup, args.iters)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
@@ -96,6 +128,9 @@ def main():
     ap.add_argument("--dec-layers", type=int, default=2)
     ap.add_argument("--heads", type=int, default=2)
     ap.add_argument("--decoder-only", action="store_true")
+    ap.add_argument("--vocab", type=int, default=256)
+    ap.add_argument("--enc-layers", type=int, default=2)
+    ap.add_argument("--encoder-only", action="store_true")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--iters", type=int, default=10)
     args = ap.parse_args()
@@ -107,6 +142,12 @@ def main():
         out = {"batch": args.batch, "frames": args.frames, "mels": args.mels, "hidden": args.hidden,
                "dec_layers": args.dec_layers, "heads": args.heads, "iters": args.iters}
         decoder_lines(out, args, dev)
+        print(json.dumps(out))
+        return
+    if args.encoder_only:
+        out = {"batch": args.batch, "phonemes": args.phonemes, "frames": args.frames, "vocab": args.vocab,
+               "hidden": args.hidden, "enc_layers": args.enc_layers, "heads": args.heads, "iters": args.iters}
+        encoder_lines(out, args, dev)
         print(json.dumps(out))
         return
     loss = CombinedTTSLoss().eval().to(dev)
