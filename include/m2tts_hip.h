@@ -960,6 +960,23 @@ int32_t m2_transformer_path(const m2_model* model);
  * the predicates the drivers branch on: nothing is launched.  Negative
  * M2_E_ARG for a null model or another stack. */
 int32_t m2_debug_transformer_form(const m2_model* model, int32_t stack);
+/* The launch plan of one forward of a stack (0 text encoder, 1 mel decoder) on
+ * [B, N] rows as one line of text: the form above, then every launch in order
+ * with its tile geometry, e.g.
+ *   dec form=3 H=64 heads=2 layers=4 B=3 N=21 src=x masked=0 devT=0 ragged=0
+ *   projected=1 tfl_first0[rb=1 grid=12 thr=512] tfl_layer0[next=1 rb=1
+ *   qs2=12 grid=12 thr=512] ...
+ * or error="<text>" where the call would be refused (one line; the format is
+ * fixed and documented in csrc/transformer_plan.h).  masked: lengths are
+ * given; source: 0 rows as given, 1 the embedding, 2 the length regulator's
+ * frame expansion; device_T: N is the capacity of a speculative launch;
+ * ragged: per-utterance row counts.  Only the calls an entry point makes
+ * are planned (encoder: source 0 or 1, masked; decoder: source 0 or 2,
+ * device_T, ragged), any other is M2_E_ARG.  Host arithmetic only: nothing is
+ * launched.  Writes at most cap bytes (NUL-terminated) and returns the line's
+ * length, or a negative M2_E_* code. */
+int32_t m2_debug_transformer_plan(const m2_model* model, int32_t stack, int32_t B, int32_t N, int32_t masked,
+                                  int32_t source, int32_t device_T, int32_t ragged, char* out, size_t cap);
 
 #ifdef __cplusplus
 }

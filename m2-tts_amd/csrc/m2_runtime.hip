@@ -16,6 +16,7 @@
 #include "m2_model.h"
 #include "transformer_fused.h"
 #include "transformer_layer.h"
+#include "transformer_plan.h"
 #include "vocoder_fused.h"
 
 namespace m2 {
@@ -288,42 +289,6 @@ void carve_front(A& a, int B, int S, int H, FrontBufs* out) {
     if (out) *out = FrontBufs{enc, dur, cum, tot, tmax, mask};
 }
 
-// One pre-LN transformer layer (components.py:131-140), x updated in place;
-// for the first decoder layer the residual source is the caller's input.
-int32_t run_layer(const m2_model* m, const m2_layer_w& L, const float* x_in, float* x, TfBufs& wb,
-                  const uint8_t* mask, int B, int N, hipStream_t st) {
-    const int H = m->cfg.hidden_dim, R = B * N;
-    int32_t rc;
-    if (m->tfused) {
-        if ((rc = launch_ln_gemm(x_in, L.n1_w, L.n1_b, L.qkv_p, nullptr, ACT_NONE, R, H, 3 * H, wb.qkv, st))) return rc;
-        if ((rc = launch_attention(wb.qkv, mask, B, N, H, m->cfg.num_heads, wb.att, st, m->att_f32))) return rc;
-        return launch_post_attn(wb.att, x_in, L.out_p, L.out_b, L.n2_w, L.n2_b, L.ff1_p, L.ff1_b, L.ff2_p, L.ff2_b, R, H,
-                                x, st);
-    }
-    if ((rc = launch_linear(x_in, L.n1_w, L.n1_b, L.qkv_w, nullptr, nullptr, ACT_NONE, R, H, 3 * H, wb.qkv, st))) return rc;
-    if ((rc = launch_attention(wb.qkv, mask, B, N, H, m->cfg.num_heads, wb.att, st, m->att_f32))) return rc;
-    if ((rc = launch_linear(wb.att, nullptr, nullptr, L.out_w, L.out_b, x_in, ACT_NONE, R, H, H, x, st))) return rc;
-    if ((rc = launch_linear(x, L.n2_w, L.n2_b, L.ff1_w, L.ff1_b, nullptr, ACT_RELU, R, H, 2 * H, wb.hid, st))) return rc;
-    if ((rc = launch_linear(wb.hid, nullptr, nullptr, L.ff2_w, L.ff2_b, x, ACT_NONE, R, 2 * H, H, x, st))) return rc;
-    return M2_OK;
-}
-
-// A stack of layers; x_in -> x (x_in may be x).  On the fused path each
-// layer's post-attention kernel also runs the next layer's LN1 -> QKV on its
-// row tile (and, with fin_W, the final LN -> projection into fin_out: then
-// *fin_done), one launch per layer fewer; results are identical to the
-// separate launches (same fp32 y into the same LayerNorm / GEMM code).
-bool tf_chain(const m2_model* m) {
-    const int H = m->cfg.hidden_dim;  // M2_TF_CHAIN=0: separate ln_gemm launches (A/B)
-    return sw().tf_chain && m->tfused && tf_post_next_supported(H, 3 * H);
-}
-
-// The first layer's input rows built by its LN1 -> QKV launch (embedding /
-// frame expansion fused in; tf_chain stacks only).
-bool tf_first_fused(const m2_model* m, const std::vector<m2_layer_w>& layers) {
-    return tf_chain(m) && !layers.empty() && tf_src_fused_supported(m->cfg.hidden_dim, 3 * m->cfg.hidden_dim);
-}
-
 // The next launch's work queue (its parity alternates the counter sets).
 TflQueue tfl_queue(const m2_model* m) { return TflQueue{m->tflq, m->tfl_seq++}; }
 // A launch that failed may not have zeroed the next counter set: restart both.
@@ -333,93 +298,157 @@ int32_t tfl_reset(const m2_model* m, hipStream_t st, int32_t rc) {
     return rc;
 }
 
-// One-launch layers (transformer_layer.hip) for a stack of this model:
-// heads == 2, H in {32, 64, 96}, the split-f16 transformer path.
-// M2_TF_LAYER=0 keeps the three-launch layers (A/B comparisons, tests).
-bool tfl_use(const m2_model* m, const std::vector<m2_layer_w>& layers) {
-    return sw().tf_layer && m->tfused && !m->att_f32 && !layers.empty() &&
-           tfl_supported(m->cfg.hidden_dim, m->cfg.num_heads);
+// What plan_transformer (transformer_plan.h) reads of a call on one of this
+// model's stacks.
+TfCall tf_call(const m2_model* m, bool decoder, TfSrc src, bool masked, bool device_T, bool ragged, int B, int N) {
+    const std::vector<m2_layer_w>& layers = decoder ? m->dec : m->enc;
+    TfCall c;
+    c.decoder = decoder;
+    c.H = m->cfg.hidden_dim;
+    c.heads = m->cfg.num_heads;
+    c.layers = (int)layers.size();
+    c.proj = decoder ? m->cfg.mel_channels : 0;
+    c.tfused = m->tfused;
+    c.att_f32 = m->att_f32;
+    for (int l = 0; l < c.layers; ++l)
+        if (layers[l].wide_scores) c.set_wide(l);
+    c.src = src;
+    c.masked = masked;
+    c.device_T = device_T;
+    c.ragged = ragged;
+    c.B = B;
+    c.N = N;
+    return c;
 }
 
-// The layers of a stack whose first LN1 -> QKV (launch_tfl_first) already
-// wrote wb.tfl[0]; x0 = layer 0's input rows (residual), x = the output
-// stream.  The last layer also runs the final LN -> projection into fin_out
-// when its width has an instantiation (*fin_done).
-int32_t run_tfl(const m2_model* m, const std::vector<m2_layer_w>& layers, const float* x0, float* x, TfBufs& wb,
-                const int64_t* lengths, int B, int N, hipStream_t st, const float* fin_g = nullptr,
-                const float* fin_b = nullptr, const float* fin_W = nullptr, const float* fin_bias = nullptr,
-                int fin_N = 0, float* fin_out = nullptr, bool* fin_done = nullptr, const int32_t* dN = nullptr,
-                const int32_t* rows = nullptr) {
-    const int H = m->cfg.hidden_dim, heads = m->cfg.num_heads, n = (int)layers.size();
-    if (fin_done) *fin_done = false;
-    const float* cur = x0;
-    for (int l = 0; l < n; ++l) {
-        const m2_layer_w& L = layers[l];
-        TflLayer w{L.out_p, L.out_b, L.n2_w, L.n2_b, L.ff1_p, L.ff1_b, L.ff2_p, L.ff2_b};
-        w.wide_scores = L.wide_scores;
-        int next = 0, NN = 0;
-        float* z = nullptr;
-        if (l + 1 < n) {
-            next = 1;
-            w.gn = layers[l + 1].n1_w;
-            w.bn = layers[l + 1].n1_b;
-            w.Wn = layers[l + 1].qkv_p;
-        } else if (fin_W && tfl_proj_supported(H, fin_N)) {
-            next = 2;
-            w.gn = fin_g;
-            w.bn = fin_b;
-            w.Wn = fin_W;
-            w.bn2 = fin_bias;
-            NN = fin_N;
-            z = fin_out;
-        }
-        const int32_t rc = launch_tfl_layer(w, B, N, H, heads, lengths != nullptr, lengths, cur, x, wb.tfl[l & 1], next,
-                                            wb.tfl[(l + 1) & 1], NN, z, tfl_queue(m), st, dN, rows);
-        if (rc) return tfl_reset(m, st, rc);
-        if (next == 2 && fin_done) *fin_done = true;
-        cur = x;
-    }
-    return M2_OK;
-}
+// The pointers of one stack call.  x0: layer 0's input rows [B, N, H] - given
+// (src x), or built there by the first launch from ids (embed) or from
+// enc / cum / S (expand); x: the stream the layers write (may be x0); out: the
+// final projection's output (decoder).
+struct TfIo {
+    const int64_t* ids = nullptr;
+    const float* enc = nullptr;
+    const int32_t* cum = nullptr;
+    int S = 0;
+    float* x0 = nullptr;
+    const int64_t* lengths = nullptr;  // masked calls
+    uint8_t* mask = nullptr;           // the padding mask the embedding launch writes and the attention reads
+    uint8_t* mask_out = nullptr;       // one-launch layers: the caller's mask (may be null), written by tfl_first
+    const int32_t* dT = nullptr;       // device frame count: N is the capacity
+    const int32_t* rows = nullptr;     // per-utterance rows, N their stride
+    float* x = nullptr;
+    float* out = nullptr;
+};
 
-int32_t run_stack(const m2_model* m, const std::vector<m2_layer_w>& layers, const float* x_in, float* x, TfBufs& wb,
-                  const uint8_t* mask, int B, int N, hipStream_t st, const float* fin_g = nullptr,
-                  const float* fin_b = nullptr, const float* fin_W = nullptr, const float* fin_bias = nullptr,
-                  int fin_N = 0, float* fin_out = nullptr, bool* fin_done = nullptr, bool qkv_ready = false) {
-    const int H = m->cfg.hidden_dim, R = B * N, n = (int)layers.size();
-    if (fin_done) *fin_done = false;
-    int32_t rc;
-    const bool chain = tf_chain(m);
-    if (!chain) {
-        const float* cur = x_in;
-        for (const auto& L : layers) {
-            if ((rc = run_layer(m, L, cur, x, wb, mask, B, N, st))) return rc;
-            cur = x;
-        }
-        return M2_OK;
-    }
-    if (n == 0) return M2_OK;
-    const float* cur = x_in;
-    if (!qkv_ready && (rc = launch_ln_gemm(cur, layers[0].n1_w, layers[0].n1_b, layers[0].qkv_p, nullptr, ACT_NONE, R,
-                                           H, 3 * H, wb.qkv, st)))
-        return rc;
-    for (int l = 0; l < n; ++l) {
-        const m2_layer_w& L = layers[l];
-        if ((rc = launch_attention(wb.qkv, mask, B, N, H, m->cfg.num_heads, wb.att, st, m->att_f32))) return rc;
-        if (l + 1 < n) {
-            const m2_layer_w& Nx = layers[l + 1];
-            rc = launch_post_attn_next(wb.att, cur, L.out_p, L.out_b, L.n2_w, L.n2_b, L.ff1_p, L.ff1_b, L.ff2_p,
-                                       L.ff2_b, R, H, x, Nx.n1_w, Nx.n1_b, Nx.qkv_p, nullptr, 3 * H, wb.qkv, st);
-        } else if (fin_W && tf_post_next_supported(H, fin_N)) {
-            rc = launch_post_attn_next(wb.att, cur, L.out_p, L.out_b, L.n2_w, L.n2_b, L.ff1_p, L.ff1_b, L.ff2_p,
-                                       L.ff2_b, R, H, x, fin_g, fin_b, fin_W, fin_bias, fin_N, fin_out, st);
-            if (!rc && fin_done) *fin_done = true;
-        } else {
-            rc = launch_post_attn(wb.att, cur, L.out_p, L.out_b, L.n2_w, L.n2_b, L.ff1_p, L.ff1_b, L.ff2_p, L.ff2_b, R,
-                                  H, x, st);
+// Launches the rows of a plan, in order.  Pre-LN layers (components.py:131-140):
+// the first layer's residual source is x0, every later launch reads x.
+int32_t run_tf_plan(const m2_model* m, const TfPlan& p, const TfIo& io, TfBufs& wb, hipStream_t st) {
+    if (p.error.code) return fail(p.error.code, p.error.text);
+    const TfCall& c = p.call;
+    const std::vector<m2_layer_w>& layers = c.decoder ? m->dec : m->enc;
+    const int B = c.B, N = c.N, H = c.H, heads = c.heads, R = B * N, M = c.proj;
+    const float* cur = io.x0;
+    for (const TfRow& r : p.rows) {
+        const m2_layer_w* L = r.layer < c.layers ? &layers[r.layer] : nullptr;
+        // what a chained launch runs on its row tile after the layer: the next
+        // layer's LN1 -> QKV (next 1) or the final LN -> projection (next 2)
+        const m2_layer_w* Nx = r.next == 1 ? &layers[r.layer + 1] : nullptr;
+        const float* gn = Nx ? Nx->n1_w : r.next == 2 ? m->dec_nw : nullptr;
+        const float* bn = Nx ? Nx->n1_b : r.next == 2 ? m->dec_nb : nullptr;
+        const float* Wn = Nx ? Nx->qkv_p : r.next == 2 ? m->mel_p : nullptr;
+        const float* bn2 = r.next == 2 ? m->mel_b : nullptr;
+        int32_t rc = M2_OK;
+        switch (r.kind) {
+            case TfKind::EmbedPe:
+                rc = launch_embed_pe(io.ids, m->emb, m->pe, B, N, H, m->cfg.vocab_size, io.x0, io.lengths, io.mask, st);
+                break;
+            case TfKind::EmbedLnGemm:
+                rc = launch_embed_ln_gemm(io.ids, m->emb, m->pe, B, N, H, m->cfg.vocab_size, io.lengths, io.mask, io.x0,
+                                          L->n1_w, L->n1_b, L->qkv_p, 3 * H, r.waves, wb.qkv, st);
+                break;
+            case TfKind::LrExpand: rc = launch_lr_expand(io.enc, io.cum, B, io.S, H, N, io.x0, st); break;
+            case TfKind::ExpandLnGemm:
+                rc = launch_expand_ln_gemm(io.enc, io.cum, B, io.S, N, H, io.x0, L->n1_w, L->n1_b, L->qkv_p, 3 * H,
+                                           r.waves, wb.qkv, st);
+                break;
+            case TfKind::LnGemm:
+                rc = launch_ln_gemm(cur, L->n1_w, L->n1_b, L->qkv_p, nullptr, ACT_NONE, R, H, 3 * H, r.waves, wb.qkv, st);
+                break;
+            case TfKind::Linear:
+                if (r.op == 0)
+                    rc = launch_linear(cur, L->n1_w, L->n1_b, L->qkv_w, nullptr, nullptr, ACT_NONE, R, H, 3 * H, wb.qkv, st);
+                else if (r.op == 1)
+                    rc = launch_linear(wb.att, nullptr, nullptr, L->out_w, L->out_b, cur, ACT_NONE, R, H, H, io.x, st);
+                else if (r.op == 2)
+                    rc = launch_linear(io.x, L->n2_w, L->n2_b, L->ff1_w, L->ff1_b, nullptr, ACT_RELU, R, H, 2 * H, wb.hid, st);
+                else
+                    rc = launch_linear(wb.hid, nullptr, nullptr, L->ff2_w, L->ff2_b, io.x, ACT_NONE, R, 2 * H, H, io.x, st);
+                if (r.op > 0) cur = io.x;
+                break;
+            case TfKind::Attention:
+                rc = launch_attention(wb.qkv, io.mask, B, N, H, heads, wb.att, st, m->att_f32);
+                break;
+            case TfKind::PostAttn:
+                rc = launch_post_attn(wb.att, cur, L->out_p, L->out_b, L->n2_w, L->n2_b, L->ff1_p, L->ff1_b, L->ff2_p,
+                                      L->ff2_b, R, H, r.waves, io.x, st);
+                cur = io.x;
+                break;
+            case TfKind::PostAttnNext:
+                rc = launch_post_attn_next(wb.att, cur, L->out_p, L->out_b, L->n2_w, L->n2_b, L->ff1_p, L->ff1_b,
+                                           L->ff2_p, L->ff2_b, R, H, r.waves, io.x, gn, bn, Wn, bn2,
+                                           Nx ? 3 * H : M, Nx ? wb.qkv : io.out, st);
+                cur = io.x;
+                break;
+            case TfKind::TflFirst: {
+                TflFirst f;
+                f.src = (int)c.src;
+                if (c.src == TfSrc::Embed) {
+                    f.ids = io.ids;
+                    f.emb = m->emb;
+                    f.pe = m->pe;
+                    f.vocab = m->cfg.vocab_size;
+                    f.escale = (float)std::sqrt((double)H);  // as launch_embed_pe
+                    f.lengths = io.lengths;
+                    f.mask = io.mask_out;
+                } else if (c.src == TfSrc::Expand) {  // the length regulator's expansion, built into x0
+                    f.enc = io.enc;
+                    f.cum = io.cum;
+                    f.S = io.S;
+                } else {
+                    f.x_in = io.x0;
+                }
+                f.dN = io.dT;
+                if (io.dT) {  // the first launch posts T for the host (m2_frames_wait)
+                    m->fpost_seq = m->fpost_seq == INT_MAX ? 1 : m->fpost_seq + 1;
+                    f.post = m->fpost_dev;
+                    f.post_seq = m->fpost_seq;
+                }
+                rc = launch_tfl_first(f, B, N, H, heads, c.masked, r.rb, io.x0, L->n1_w, L->n1_b, L->qkv_p, wb.tfl[0],
+                                      tfl_queue(m), st, io.rows);
+                if (rc) return tfl_reset(m, st, rc);
+                break;
+            }
+            case TfKind::TflLayer: {
+                TflLayer w{L->out_p, L->out_b, L->n2_w, L->n2_b, L->ff1_p, L->ff1_b, L->ff2_p, L->ff2_b, gn, bn, Wn, bn2};
+                rc = launch_tfl_layer(w, B, N, H, heads, c.masked, r.rb, r.qs2, io.lengths, cur, io.x,
+                                      wb.tfl[r.layer & 1], r.next, wb.tfl[(r.layer + 1) & 1], r.next == 2 ? M : 0,
+                                      r.next == 2 ? io.out : nullptr, tfl_queue(m), st, io.dT, io.rows);
+                if (rc) return tfl_reset(m, st, rc);
+                cur = io.x;
+                break;
+            }
+            // The decoder's final LayerNorm -> mel projection as a launch of its
+            // own (no layer ran it): ln_gemm on the packed weights where (H, mel)
+            // has an instance, else - any other mel width of a fused handle, and
+            // the fp32 path - the generic linear on the fp32 weights.
+            case TfKind::FinalLnGemm:
+                rc = launch_ln_gemm(cur, m->dec_nw, m->dec_nb, m->mel_p, m->mel_b, ACT_NONE, R, H, M, r.waves, io.out, st);
+                break;
+            case TfKind::FinalLinear:
+                rc = launch_linear(cur, m->dec_nw, m->dec_nb, m->mel_w, m->mel_b, nullptr, ACT_NONE, R, H, M, io.out, st);
+                break;
         }
         if (rc) return rc;
-        cur = x;
     }
     return M2_OK;
 }
@@ -451,45 +480,19 @@ namespace {
 int32_t text_encoder_layers(const m2_model* m, const int64_t* ids, const int64_t* lengths, int32_t B, int32_t S,
                             uint8_t* out_mask, void* workspace, size_t workspace_bytes, hipStream_t st,
                             float** x_pre) {
-    const int H = m->cfg.hidden_dim;
     Carve a(workspace, workspace_bytes);
     TfBufs wb;
-    carve_tf(a, B, S, H, m->cfg.num_heads, &wb);
+    carve_tf(a, B, S, m->cfg.hidden_dim, m->cfg.num_heads, &wb);
     if (!a.ok) return fail(M2_E_WORKSPACE, "m2_text_encoder: workspace too small");
     *x_pre = wb.x;
-    if (B == 0 || S == 0) return M2_OK;
-    int32_t rc;
-    const uint8_t* mask = nullptr;
-    if (lengths) mask = out_mask ? out_mask : wb.mask;  // written by the embedding launch
-    if (tfl_use(m, m->enc)) {
-        const m2_layer_w& L0 = m->enc[0];
-        TflFirst f;
-        f.src = 1;
-        f.ids = ids;
-        f.emb = m->emb;
-        f.pe = m->pe;
-        f.vocab = m->cfg.vocab_size;
-        f.escale = (float)std::sqrt((double)H);  // as launch_embed_pe
-        f.lengths = lengths;
-        f.mask = out_mask;
-        if ((rc = launch_tfl_first(f, B, S, H, m->cfg.num_heads, lengths != nullptr, wb.x, L0.n1_w, L0.n1_b, L0.qkv_p,
-                                   wb.tfl[0], tfl_queue(m), st)))
-            return tfl_reset(m, st, rc);
-        return run_tfl(m, m->enc, wb.x, wb.x, wb, lengths, B, S, st);
-    }
-    if (tf_first_fused(m, m->enc)) {
-        const m2_layer_w& L0 = m->enc[0];
-        if ((rc = launch_embed_ln_gemm(ids, m->emb, m->pe, B, S, H, m->cfg.vocab_size, lengths,
-                                       const_cast<uint8_t*>(mask), wb.x, L0.n1_w, L0.n1_b, L0.qkv_p, 3 * H, wb.qkv,
-                                       st)))
-            return rc;
-        return run_stack(m, m->enc, wb.x, wb.x, wb, mask, B, S, st, nullptr, nullptr, nullptr, nullptr, 0, nullptr,
-                         nullptr, true);
-    }
-    if ((rc = launch_embed_pe(ids, m->emb, m->pe, B, S, H, m->cfg.vocab_size, wb.x, lengths,
-                              const_cast<uint8_t*>(mask), st)))
-        return rc;
-    return run_stack(m, m->enc, wb.x, wb.x, wb, mask, B, S, st);
+    TfIo io;
+    io.ids = ids;
+    io.lengths = lengths;
+    if (lengths) io.mask = out_mask ? out_mask : wb.mask;  // written by the embedding launch
+    io.mask_out = out_mask;
+    io.x0 = io.x = wb.x;
+    const TfPlan p = plan_transformer(tf_call(m, false, TfSrc::Embed, lengths != nullptr, false, false, B, S), sw());
+    return run_tf_plan(m, p, io, wb, st);
 }
 }  // namespace
 
@@ -631,83 +634,31 @@ int32_t m2_length_regulator_expand(const float* enc, const int32_t* cum, int32_t
 }  // extern "C"
 
 namespace {
-// The decoder's final LayerNorm -> mel projection as a launch of its own (the
-// last layer did not run it): ln_gemm on the packed weights where (H, mel) has
-// an instance, else - any other mel width of a fused handle, and the fp32
-// path - the generic linear on the fp32 weights.  Neither needs scratch.
-int32_t final_projection(const m2_model* m, const float* x, int R, float* out_mel, hipStream_t st) {
-    const int H = m->cfg.hidden_dim, M = m->cfg.mel_channels;
-    if (m->tfused && tf_ln_gemm_supported(H, M))
-        return launch_ln_gemm(x, m->dec_nw, m->dec_nb, m->mel_p, m->mel_b, ACT_NONE, R, H, M, out_mel, st);
-    return launch_linear(x, m->dec_nw, m->dec_nb, m->mel_w, m->mel_b, nullptr, ACT_NONE, R, H, M, out_mel, st);
-}
-
 // The mel decoder on x [B, T, H]; with enc / cum given, x is first filled by
-// the length regulator's frame expansion of enc, fused into the first layer's
-// LN1 -> QKV launch when tf_first_fused (else a separate lr_expand launch).
+// the length regulator's frame expansion of enc (by the first layer's launch
+// where the plan fuses it, else a separate lr_expand launch).
+// dT: T is the capacity of a speculative launch, the frame count a device word.
 // rows (one-launch layers only): utterance b has rows[b] frames, T is the
 // row stride; out_mel's rows past rows[b] are then not written.
 int32_t mel_decoder(const m2_model* m, float* x, int32_t B, int32_t T, float* out_mel, void* workspace,
                     size_t workspace_bytes, hipStream_t st, const float* enc = nullptr, const int32_t* cum = nullptr,
                     int32_t S = 0, const int32_t* dT = nullptr, const int32_t* rows = nullptr) {
-    const int H = m->cfg.hidden_dim;
     Carve a(workspace, workspace_bytes);
     TfBufs wb;
-    carve_tf(a, B, T, H, m->cfg.num_heads, &wb);
+    carve_tf(a, B, T, m->cfg.hidden_dim, m->cfg.num_heads, &wb);
     if (!a.ok) return fail(M2_E_WORKSPACE, "m2_mel_decoder: workspace too small");
-    if (B == 0 || T == 0) return M2_OK;
-    int32_t rc;
-    // dT: T is the capacity of a speculative launch (spec_ok: one-launch
-    // layers with the mel projection fused into the last one)
-    M2_CHECK_ARG(!dT || (tfl_use(m, m->dec) && tfl_proj_supported(H, m->cfg.mel_channels)),
-                 "mel decoder: a device frame count needs the one-launch layers");
-    M2_CHECK_SHAPE(!rows || tfl_use(m, m->dec), "mel decoder: per-utterance frame counts need the one-launch layers "
-                                                "(hidden_dim 32 / 64 / 96 with 2 heads, M2_TF_LAYER not 0)");
-    if (tfl_use(m, m->dec)) {
-        const m2_layer_w& L0 = m->dec[0];
-        TflFirst f;
-        f.dN = dT;
-        if (dT) {  // the first launch posts T for the host (m2_frames_wait)
-            m->fpost_seq = m->fpost_seq == INT_MAX ? 1 : m->fpost_seq + 1;
-            f.post = m->fpost_dev;
-            f.post_seq = m->fpost_seq;
-        }
-        if (enc) {  // the length regulator's expansion, built by the first launch into x
-            f.src = 2;
-            f.enc = enc;
-            f.cum = cum;
-            f.S = S;
-        } else {
-            f.src = 0;
-            f.x_in = x;
-        }
-        if ((rc = launch_tfl_first(f, B, T, H, m->cfg.num_heads, false, x, L0.n1_w, L0.n1_b, L0.qkv_p, wb.tfl[0],
-                                   tfl_queue(m), st, rows)))
-            return tfl_reset(m, st, rc);
-        bool projected = false;
-        if ((rc = run_tfl(m, m->dec, x, wb.x, wb, nullptr, B, T, st, m->dec_nw, m->dec_nb, m->mel_p, m->mel_b,
-                          m->cfg.mel_channels, out_mel, &projected, dT, rows)))
-            return rc;
-        if (projected) return M2_OK;
-        return final_projection(m, wb.x, B * T, out_mel, st);
-    }
-    bool qkv_ready = false;
-    if (enc) {
-        if (tf_first_fused(m, m->dec)) {
-            const m2_layer_w& L0 = m->dec[0];
-            if ((rc = launch_expand_ln_gemm(enc, cum, B, S, T, H, x, L0.n1_w, L0.n1_b, L0.qkv_p, 3 * H, wb.qkv, st)))
-                return rc;
-            qkv_ready = true;
-        } else if ((rc = launch_lr_expand(enc, cum, B, S, H, T, x, st))) {
-            return rc;
-        }
-    }
-    bool projected = false;
-    if ((rc = run_stack(m, m->dec, x, wb.x, wb, nullptr, B, T, st, m->dec_nw, m->dec_nb, m->mel_p, m->mel_b,
-                        m->cfg.mel_channels, out_mel, &projected, qkv_ready)))
-        return rc;
-    if (projected) return M2_OK;
-    return final_projection(m, m->dec.empty() ? x : wb.x, B * T, out_mel, st);
+    TfIo io;
+    io.enc = enc;
+    io.cum = cum;
+    io.S = S;
+    io.x0 = x;
+    io.dT = dT;
+    io.rows = rows;
+    io.x = wb.x;
+    io.out = out_mel;
+    const TfPlan p = plan_transformer(
+        tf_call(m, true, enc ? TfSrc::Expand : TfSrc::X, false, dT != nullptr, rows != nullptr, B, T), sw());
+    return run_tf_plan(m, p, io, wb, st);
 }
 }  // namespace
 
@@ -1142,10 +1093,10 @@ int32_t front_run(const m2_model* m, const int64_t* ids, const int64_t* lengths,
 // for the end fix-up (vocoder).  Otherwise M2_E_SHAPE: the caller runs the
 // utterances one by one.
 int32_t ragged_supported(const m2_model* m, bool decoder, bool vocoder, const char* what) {
-    if (decoder && !tfl_use(m, m->dec))
-        return fail(M2_E_SHAPE, (std::string(what) + ": per-utterance frame counts need the one-launch transformer "
-                                 "layers (hidden_dim 32 / 64 / 96 with 2 heads, split-f16 range, M2_TF_LAYER not 0)")
-                                    .c_str());
+    if (decoder) {  // the refusal a ragged decoder call would plan to, under the entry point's name
+        const TfError e = tf_call_error(tf_call(m, true, TfSrc::X, false, false, true, 1, 1), sw());
+        if (e.code) return fail(e.code, (std::string(what) + ": " + e.text).c_str());
+    }
     if (vocoder && !(m->fused && m->ragged_w))
         return fail(M2_E_SHAPE, (std::string(what) + ": per-utterance frame counts need the fused vocoder "
                                  "(unsupported (mel_channels, vocoder_channels) or M2_VOCODER_PERLAYER)").c_str());
@@ -1201,7 +1152,7 @@ int32_t vocoder_ragged(const m2_model* m, const float* mel, int32_t mel_layout, 
 // projection fused into the last one, and the fused (unchunked) vocoder.
 bool dev_back_ok(const m2_model* m, int32_t T_cap) {
     if (!sw().speculative) return false;  // M2_SPECULATIVE=0: host-side T only (A/B, tests)
-    return T_cap > 0 && tfl_use(m, m->dec) && tfl_proj_supported(m->cfg.hidden_dim, m->cfg.mel_channels) &&
+    return T_cap > 0 && !tf_call_error(tf_call(m, true, TfSrc::Expand, false, true, false, 1, T_cap), sw()).code &&
            m->fused && !(m->chunk_frames > 0 && T_cap > m->chunk_frames);
 }
 
@@ -1450,9 +1401,20 @@ int32_t m2_transformer_path(const m2_model* m) {
 
 int32_t m2_debug_transformer_form(const m2_model* m, int32_t stack) {
     M2_CHECK_ARG(m && (stack == 0 || stack == 1), "m2_debug_transformer_form: bad argument");
-    if (tfl_use(m, stack ? m->dec : m->enc)) return 3;  // text_encoder_layers / mel_decoder ask this first
-    if (!m->tfused) return 0;                           // run_layer's five linears
-    return tf_chain(m) ? 2 : 1;                         // run_stack
+    return tf_form(tf_call(m, stack != 0, TfSrc::X, false, false, false, 1, 1), sw());
+}
+
+int32_t m2_debug_transformer_plan(const m2_model* m, int32_t stack, int32_t B, int32_t N, int32_t masked,
+                                  int32_t source, int32_t device_T, int32_t ragged, char* out, size_t cap) {
+    M2_CHECK_ARG(m && (stack == 0 || stack == 1) && B >= 0 && N >= 0 && source >= 0 && source <= 2,
+                 "m2_debug_transformer_plan: bad argument");
+    // the calls the entry points make: the encoder embeds (source 0 plans the same layers on given rows)
+    // and may be masked; the decoder takes rows or the expansion, a device frame count or ragged rows
+    M2_CHECK_ARG(stack == 1 ? (!masked && source != 1) : (source != 2 && !device_T && !ragged),
+                 "m2_debug_transformer_plan: no entry point makes this call (encoder: source 0 | 1, masked; decoder: "
+                 "source 0 | 2, device_T, ragged)");
+    const TfCall c = tf_call(m, stack != 0, (TfSrc)source, masked != 0, device_T != 0, ragged != 0, B, N);
+    return plan_transformer(c, sw()).print(out, cap);
 }
 
 int32_t m2_profile_enable(m2_model* m, int32_t capacity) {

@@ -382,9 +382,7 @@ __global__ __launch_bounds__(64 * NW) void post_attn_kernel(const float* __restr
 
 }  // namespace tfx
 
-bool tf_fused_supported(int H, int N_out) {
-    return (H == 32 || H == 64 || H == 96) && N_out % 16 == 0;
-}
+static_assert(tfx::TR == kTfTileRows, "the plan's grid (transformer_plan.h) is in tiles of TR rows");
 
 // B-fragment packing for v_mfma_f32_16x16x4_f32: element (n-block nb, k-step
 // s, lane) = W[nb*16 + (lane&15)][4*s + (lane>>4)], layout [nb][s/4][lane][s%4].
@@ -423,26 +421,11 @@ bool pack_bfrag_split(const float* W, int N, int K, std::vector<float>* out) {
     return true;
 }
 
-// Waves per workgroup: 8 when the grid is short of two workgroups per CU
-// (small batches: every 32-row tile is then a serial chain of GEMM rounds, and
-// 8 waves halve the rounds: post_attn at stage2 B=8 S=100 13.8 -> 10.5 us,
-// tools/probe/tf_waves_ab.sh), else 4.  M2_TF_WAVES=4|8 forces one.  (An L2
-// warm-up of the layer's weights at kernel start measured 1 us slower: across
-// steps they stay L2-resident.)
-static int tf_waves(int R) {
-    const int forced = sw().tf_waves;
-    if (forced) return forced;
-    return cdiv(R, tfx::TR) < 2 * 256 ? 8 : 4;
-}
-
-// The widths launch_ln_gemm instantiates are those post_attn_kernel chains (tf_post_next_supported).
-bool tf_ln_gemm_supported(int K, int N) { return tf_post_next_supported(K, N); }
-
+// nw: waves per workgroup, 4 or 8 (tf_waves, transformer_plan.h).
 int32_t launch_ln_gemm(const float* x, const float* g, const float* b, const float* Wp, const float* bias, int act,
-                       int R, int K, int N, float* y, hipStream_t st) {
+                       int R, int K, int N, int nw, float* y, hipStream_t st) {
     if (R == 0) return M2_OK;
-    const int nw = tf_waves(R);
-    const dim3 grid(cdiv(R, tfx::TR)), blk(64 * nw);
+    const dim3 grid(tf_grid(R)), blk(64 * nw);
     const vx_u32x4* W = reinterpret_cast<const vx_u32x4*>(Wp);
 #define M2_LNG(KK, NN)                                                                                             \
     if (K == KK && N == NN) {                                                                                      \
@@ -471,10 +454,9 @@ int32_t launch_ln_gemm(const float* x, const float* g, const float* b, const flo
 
 // The first layer's LN1 -> QKV on rows it builds itself (SRC_EMBED / SRC_EXPAND).
 static int32_t launch_src_ln_gemm(int srcmode, const tfx::RowSrc& src, const float* g, const float* b,
-                                  const float* Wp, int R, int K, int N, float* y, hipStream_t st) {
+                                  const float* Wp, int R, int K, int N, int nw, float* y, hipStream_t st) {
     if (R == 0) return M2_OK;
-    const int nw = tf_waves(R);
-    const dim3 grid(cdiv(R, tfx::TR)), blk(64 * nw);
+    const dim3 grid(tf_grid(R)), blk(64 * nw);
     const vx_u32x4* W = reinterpret_cast<const vx_u32x4*>(Wp);
 #define M2_SLG(KK, NN, SS)                                                                                        \
     if (K == KK && N == NN && srcmode == SS) {                                                                    \
@@ -497,11 +479,9 @@ static int32_t launch_src_ln_gemm(int srcmode, const tfx::RowSrc& src, const flo
     return fail(M2_E_SHAPE, "ln_gemm: unsupported (K, N) for a fused row source");
 }
 
-bool tf_src_fused_supported(int H, int N) { return (H == 32 && N == 96) || (H == 64 && N == 192) || (H == 96 && N == 288); }
-
 int32_t launch_embed_ln_gemm(const int64_t* ids, const float* emb, const float* pe, int B, int S, int H, int vocab,
                              const int64_t* lengths, uint8_t* mask, float* x, const float* g, const float* b,
-                             const float* Wp, int N, float* y, hipStream_t st) {
+                             const float* Wp, int N, int nw, float* y, hipStream_t st) {
     tfx::RowSrc src;
     src.ids = ids;
     src.emb = emb;
@@ -512,26 +492,26 @@ int32_t launch_embed_ln_gemm(const int64_t* ids, const float* emb, const float* 
     src.mask = mask;
     src.S = S;
     src.xo = x;
-    return launch_src_ln_gemm(tfx::SRC_EMBED, src, g, b, Wp, B * S, H, N, y, st);
+    return launch_src_ln_gemm(tfx::SRC_EMBED, src, g, b, Wp, B * S, H, N, nw, y, st);
 }
 
 int32_t launch_expand_ln_gemm(const float* enc, const int32_t* cum, int B, int S, int T, int H, float* x,
-                              const float* g, const float* b, const float* Wp, int N, float* y, hipStream_t st) {
+                              const float* g, const float* b, const float* Wp, int N, int nw, float* y,
+                              hipStream_t st) {
     tfx::RowSrc src;
     src.enc = enc;
     src.cum = cum;
     src.S = S;
     src.T = T;
     src.xo = x;
-    return launch_src_ln_gemm(tfx::SRC_EXPAND, src, g, b, Wp, B * T, H, N, y, st);
+    return launch_src_ln_gemm(tfx::SRC_EXPAND, src, g, b, Wp, B * T, H, N, nw, y, st);
 }
 
 int32_t launch_post_attn(const float* att, const float* x, const float* Wo, const float* bo, const float* g2,
                          const float* b2n, const float* W1, const float* b1, const float* W2, const float* b2, int R,
-                         int H, float* y, hipStream_t st) {
+                         int H, int nw, float* y, hipStream_t st) {
     if (R == 0) return M2_OK;
-    const int nw = tf_waves(R);
-    const dim3 grid(cdiv(R, tfx::TR)), blk(64 * nw);
+    const dim3 grid(tf_grid(R)), blk(64 * nw);
     auto f4 = [](const float* p) { return reinterpret_cast<const vx_u32x4*>(p); };
 #define M2_PA(HH)                                                                                                   \
     case HH:                                                                                                        \
@@ -553,18 +533,12 @@ int32_t launch_post_attn(const float* att, const float* x, const float* Wo, cons
     return M2_OK;
 }
 
-bool tf_post_next_supported(int H, int NN) {
-    return (H == 32 && (NN == 96 || NN == 32 || NN == 64)) || (H == 64 && (NN == 192 || NN == 64 || NN == 80)) ||
-           (H == 96 && (NN == 288 || NN == 80 || NN == 96));
-}
-
 int32_t launch_post_attn_next(const float* att, const float* x, const float* Wo, const float* bo, const float* g2,
                               const float* b2n, const float* W1, const float* b1, const float* W2, const float* b2,
-                              int R, int H, float* y, const float* gn, const float* bn, const float* Wn,
+                              int R, int H, int nw, float* y, const float* gn, const float* bn, const float* Wn,
                               const float* bn2, int NN, float* z, hipStream_t st) {
     if (R == 0) return M2_OK;
-    const int nw = tf_waves(R);
-    const dim3 grid(cdiv(R, tfx::TR)), blk(64 * nw);
+    const dim3 grid(tf_grid(R)), blk(64 * nw);
     auto f4 = [](const float* p) { return reinterpret_cast<const vx_u32x4*>(p); };
 #define M2_PAN(HH, NNN)                                                                                              \
     if (H == HH && NN == NNN) {                                                                                      \

@@ -1,6 +1,7 @@
 // One-launch-per-layer transformer kernels (transformer_layer.hip).
 #pragma once
 #include "m2_common.h"
+#include "transformer_plan.h"
 
 namespace m2 {
 
@@ -29,14 +30,10 @@ struct TflQueue {
     unsigned seq = 0;
 };
 
-// True when the fused layer path covers (H, heads): heads == 2, H in {32, 64, 96}.
-bool tfl_supported(int H, int heads);
-// npad and the bytes of one TflBufs set for B utterances of N rows.
-int tfl_npad(int N);
+// The bytes of one TflBufs set for B utterances of N rows (npad = tfl_npad(N),
+// transformer_plan.h, where tfl_supported and tfl_proj_supported live too).
 size_t tfl_bytes(int B, int N, int H, int heads);
 void tfl_carve(unsigned char* base, int B, int N, int H, int heads, TflBufs* out);
-// Final-projection widths the last decoder layer can fuse (mel channels).
-bool tfl_proj_supported(int H, int NN);
 
 // The first layer's LN1 -> QKV on 16-row tiles of each utterance, rows built
 // by the launch itself (and stored to x_out, the residual input):
@@ -60,7 +57,8 @@ struct TflFirst {
     int32_t* post = nullptr;
     int32_t post_seq = 0;
 };
-int32_t launch_tfl_first(const TflFirst& f, int B, int N, int H, int heads, bool masked, float* x_out,
+// rb: 16-row tiles per workgroup (the plan's row, tfl_first_rb).
+int32_t launch_tfl_first(const TflFirst& f, int B, int N, int H, int heads, bool masked, int rb, float* x_out,
                          const float* g, const float* bln, const float* Wqkv, const TflBufs& out, TflQueue q,
                          hipStream_t st, const int32_t* rows = nullptr);
 
@@ -72,16 +70,14 @@ int32_t launch_tfl_first(const TflFirst& f, int B, int N, int H, int heads, bool
 // clamp(rows[b], 1, N) rows and keys - a ragged batch.  N stays the row stride
 // of x, z and the masks and sizes npad and the grid; rows past the bound are
 // zeros in the attention buffers and are not written to x_out / z.  Not
-// combinable with dN.
+// combinable with dN.  rb, qs2: 16-row tiles per workgroup and the attention
+// form (the plan's row: tfl_layer_rb, tfl_qs2).
 struct TflLayer {
     const float *Wo, *bo, *g2, *b2n, *W1, *b1, *W2, *b2;  // packed (pack_bfrag_split) / fp32
     const float *gn = nullptr, *bn = nullptr, *Wn = nullptr, *bn2 = nullptr;
-    // the layer's scores (log2 units) may leave the f16 range: the unmasked
-    // head_dim-48 default form (f16 softmax base) gives way to the f32-base one
-    bool wide_scores = false;
 };
-int32_t launch_tfl_layer(const TflLayer& w, int B, int N, int H, int heads, bool masked, const int64_t* lengths,
-                         const float* x_in, float* x_out, const TflBufs& in, int next, const TflBufs& out,
+int32_t launch_tfl_layer(const TflLayer& w, int B, int N, int H, int heads, bool masked, int rb, int qs2,
+                         const int64_t* lengths, const float* x_in, float* x_out, const TflBufs& in, int next, const TflBufs& out,
                          int NN, float* z, TflQueue q, hipStream_t st, const int32_t* dN = nullptr,
                          const int32_t* rows = nullptr);
 

@@ -1784,16 +1784,8 @@ struct FArgs {
 #ifndef FK_MINW  // A/B builds: waves per SIMD the first launch is compiled for
 #define FK_MINW 2
 #endif
-// Waves per first-launch workgroup: 64-row tiles (the very large grids) run
-// 4 waves, so two workgroups share a CU at 189 VGPRs and one tile's latency
-// chain (prefix sums -> search -> gather -> LN -> QKV -> stores) overlaps the
-// other's: configs[4]'s frame-expansion launch 210 -> 192 us; the small grids'
-// 16- and 32-row tiles keep 8 (4 there: B=8 6.3 -> 7.5 us,
-// profiles/r04/r04af_*).
-#ifndef FK_NW4  // A/B builds: waves of the 64-row-tile workgroups
-#define FK_NW4 4
-#endif
-constexpr int fk_nw(int rb) { return rb == 4 ? FK_NW4 : NW; }
+// Waves per first-launch workgroup: fk_nw(rb), with the tile rules in transformer_plan.h.
+static_assert(TQ == kTileRows && NW == kWaves, "the plan's tile rules (transformer_plan.h) use these");
 template <int H, int SRC, bool MASKED, int RB>
 __global__ __launch_bounds__(fk_nw(RB) * 64, FK_MINW) void first_kernel(FArgs a) {
     constexpr int HD = H / HEADS, H4 = H / 4, TR = 16 * RB, FNW = fk_nw(RB);
@@ -1895,16 +1887,6 @@ extern "C" int32_t m2_debug_stamps_tfl(void* host, size_t bytes) {
 #endif
 
 // ---------------------------------------------------------------------------
-bool tfl_supported(int H, int heads) { return heads == 2 && (H == 32 || H == 64 || H == 96); }
-
-bool tfl_proj_supported(int H, int NN) {
-    return (H == 32 && (NN == 32 || NN == 64)) || (H == 64 && (NN == 64 || NN == 80)) ||
-           (H == 96 && (NN == 80 || NN == 96));
-}
-
-// a multiple of 64 so that 16-, 32- and 64-row tiles all cover [0, npad) exactly
-int tfl_npad(int N) { return (N + 63) / 64 * 64; }
-
 namespace {
 void tfl_sizes(int B, int N, int H, int heads, size_t* qk, size_t* v) {
     const int HD = H / heads, npad = tfl_npad(N);
@@ -1926,54 +1908,13 @@ void tfl_carve(unsigned char* base, int B, int N, int H, int heads, TflBufs* out
 }
 
 namespace {
-// Rows per workgroup of the layer launches: 64 (query-split attention, K / V
-// staged in LDS) once the 64-row tiles alone fill the 256 CUs; else 16 while
-// one round of the CUs holds the 16-row grid, else 32.  M2_TFL_RB=1|2|4
-// forces one.  The first (LN1 -> QKV) launch has no attention: at most 32.
-int tfl_rb(int B, int N) {
-    if (sw().tfl_rb) return sw().tfl_rb;
-    const long tiles16 = (long)B * (tfl_npad(N) / tfl::TQ);
-    return tiles16 >= 4 * 256 ? 4 : (tiles16 > 256 ? 2 : 1);
-}
-// 64-row tiles: two query blocks per wave with the lean softmax
-// (attention_qsplit2<..., LEAN>) at head_dim 48 (stage2: B=128 T=2600 step
-// -1.5 %, B=16 T=2600 -1.9 %, B=64 T=500 -0.8 % against the plain two-block
-// form, which was itself -0.7 % at B=128 T=2600 against one block; the lean
-// one-block form +2.2 % at B=16 T=2600), the lean one-block form below
-// (stage1 B=32: -0.7 % against the plain one-block form; two blocks +0.3 to
-// +0.6 %; in-process A/Bs, profiles/r03/r03ab_*, r03ad_ab.txt, r03aj_ab.txt,
-// r03al_ab.txt).  Round 4: at head_dim 48 the wave-specialised form with
-// LDS-DMA staging (attention_qsplit_ws<..., DMA>; masked launches keep the
-// lean two-block form): against the ping-pong form (6), itself -0.9 % on the
-// long-form step against the lean two-block form (3): long-form step -1.5 %,
-// B=16 T=2600 -1.1 %, B=64 T=500 level (in-process A/Bs,
-// profiles/r04/r04j_*, r04l_*, r04m_*, r04n_*); at head_dim 32 it is slower
-// than the lean one-block form (stage1 B=32 +0.5 %, B=128 +1.4 %).  Measured
-// and not kept (removed in round 5): the software-pipelined form (5, level or
-// slower, r04d / r04e), the wave-specialised form with register staging (7,
-// between 6 and 9) and with its regions interleaved by group barriers (8,
-// +3 %; 10).  Round 6: the key-quarter form (12, attention_quarters) for
-// every unmasked layer - at head_dim 48 it replaces 9 (configs[4] step -4.2 %,
-// B=16 T=2600 -7.1 %, B=64 T=500 -2.6 %; 9 removed, history keeps it), at
-// head_dim 32 the lean one-block form (stage1 B=128 S=130 -3.2 %, B=32 S=520
-// -9.1 %; profiles/r06/r06ad_*, r06ah_*).  Masked layers, and layers whose
-// scores may leave the f16 range (12's base is an f16 pair), keep the
-// previous default: 3 at head_dim 48, 4 below.  M2_TFL_QS2=0|2|3|4|12 forces
-// a form (switch table, m2_common.h): 0 / 2 one / two query blocks, 3 / 4 the
-// same with the lean softmax, 12 the key-quarter form (unmasked layers).
-int tfl_qs2(int H) {
-    if (sw().tfl_qs2 >= 0) return sw().tfl_qs2;
-    return 12;
-}
-int tfl_ntile(int N, int rb) { return (tfl_npad(N) + tfl::TQ * rb - 1) / (tfl::TQ * rb); }
-dim3 tfl_grid(int B, int N, int rb) { return dim3(B * tfl_ntile(N, rb)); }
 float tfl_sl2(int H) {
     const float scale = (float)(1.0 / std::sqrt((double)(H / tfl::HEADS)));  // components.py:52, fp32 at the mul
     return scale * tfl::kLog2e;
 }
 }  // namespace
 
-int32_t launch_tfl_first(const TflFirst& f, int B, int N, int H, int heads, bool masked, float* x_out,
+int32_t launch_tfl_first(const TflFirst& f, int B, int N, int H, int heads, bool masked, int rb, float* x_out,
                          const float* g, const float* bln, const float* Wqkv, const TflBufs& out, TflQueue q,
                          hipStream_t st, const int32_t* rows) {
     M2_CHECK_SHAPE(tfl_supported(H, heads), "tfl: unsupported (hidden_dim, heads)");
@@ -1986,16 +1927,6 @@ int32_t launch_tfl_first(const TflFirst& f, int B, int N, int H, int heads, bool
     a.B = B;
     a.N = N;
     a.npad = tfl_npad(N);
-    // rows per workgroup: the layers' choice up to 32, 64 for grids of >= 8
-    // rounds of 16-row tiles (latency-bound rounds; with 8-wave workgroups
-    // 64-row tiles made stage2 B=64 1.4 % slower, profiles/r03/ab/r03x_ab.txt,
-    // with the 4-wave ones (fk_nw) 0.5-1.7 % faster, r04ag_s2_b64_first_rb);
-    // M2_TFL_FIRST_RB=1|2|4 forces one (switch table, m2_common.h)
-    int rb = tfl_rb(B, N) > 1 ? 2 : 1;
-    if ((long)B * (tfl_npad(N) / tfl::TQ) >= 8L * 256) rb = 4;
-    if (sw().tfl_first_rb) rb = sw().tfl_first_rb;
-    if (masked && sw().tfl_rb_masked) rb = sw().tfl_rb_masked;
-    if (!masked && sw().tfl_rb_unmasked) rb = sw().tfl_rb_unmasked;
     a.ntile = tfl_ntile(N, rb);
     a.qcnt = q.cnt;
     a.qseq = q.seq;
@@ -2023,7 +1954,7 @@ int32_t launch_tfl_first(const TflFirst& f, int B, int N, int H, int heads, bool
     a.q = out.q;
     a.k = out.k;
     a.v = out.v;
-    const dim3 grid = tfl_grid(B, N, rb), blk(tfl::fk_nw(rb) * 64);
+    const dim3 grid(tfl_grid(B, N, rb)), blk(tfl::fk_nw(rb) * 64);
 #define M2_TFF(HH, SS, MM)                                                                      \
     if (H == HH && f.src == SS && masked == MM) {                                               \
         if (rb == 4) hipLaunchKernelGGL((tfl::first_kernel<HH, SS, MM, 4>), grid, blk, 0, st, a);  \
@@ -2046,9 +1977,10 @@ int32_t launch_tfl_first(const TflFirst& f, int B, int N, int H, int heads, bool
     return fail(M2_E_SHAPE, "tfl first layer: unsupported (hidden_dim, row source, mask)");
 }
 
-int32_t launch_tfl_layer(const TflLayer& w, int B, int N, int H, int heads, bool masked, const int64_t* lengths,
-                         const float* x_in, float* x_out, const TflBufs& in, int next, const TflBufs& out, int NN,
-                         float* z, TflQueue q, hipStream_t st, const int32_t* dN, const int32_t* rows) {
+int32_t launch_tfl_layer(const TflLayer& w, int B, int N, int H, int heads, bool masked, int rb, int qs2,
+                         const int64_t* lengths, const float* x_in, float* x_out, const TflBufs& in, int next,
+                         const TflBufs& out, int NN, float* z, TflQueue q, hipStream_t st, const int32_t* dN,
+                         const int32_t* rows) {
     M2_CHECK_SHAPE(tfl_supported(H, heads), "tfl: unsupported (hidden_dim, heads)");
     M2_CHECK_ARG(!masked || lengths, "tfl: masked attention needs lengths");
     M2_CHECK_ARG(q.cnt, "tfl: no work-queue counters");
@@ -2064,9 +1996,6 @@ int32_t launch_tfl_layer(const TflLayer& w, int B, int N, int H, int heads, bool
     a.dN = dN;
     a.rows = rows;
     a.npad = tfl_npad(N);
-    const int rb = masked && sw().tfl_rb_masked     ? sw().tfl_rb_masked
-                   : !masked && sw().tfl_rb_unmasked ? sw().tfl_rb_unmasked
-                                                     : tfl_rb(B, N);
     a.ntile = tfl_ntile(N, rb);
     a.qcnt = q.cnt;
     a.qseq = q.seq;
@@ -2093,13 +2022,7 @@ int32_t launch_tfl_layer(const TflLayer& w, int B, int N, int H, int heads, bool
     a.nk = out.k;
     a.nv = out.v;
     a.z = z;
-    const dim3 grid = tfl_grid(B, N, rb), blk(tfl::NW * 64);
-    // form 12 is unmasked-only, and at head_dim 48 keeps the softmax base as
-    // an f16 pair: a masked launch, or a layer whose scores may leave the f16
-    // range, runs the previous default instead (the lean two-block form 3 at
-    // head_dim 48, the one-block form 4 below)
-    int qs2 = tfl_qs2(H);
-    if (qs2 == 12 && (masked || w.wide_scores)) qs2 = H / tfl::HEADS >= 48 ? 3 : 4;
+    const dim3 grid(tfl_grid(B, N, rb)), blk(tfl::NW * 64);
 #define M2_TFL(HH, MM, NX, NNN)                                                                 \
     if (H == HH && masked == MM && next == NX && (NX != 2 || NN == NNN)) {                      \
         if constexpr (!MM) {                                                                    \

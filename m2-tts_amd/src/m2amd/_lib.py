@@ -99,6 +99,8 @@ _SIGNATURES = {
     "m2_eval_mcd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "m2_transformer_path": (c_i32, [c_vp]),
     "m2_debug_transformer_form": (c_i32, [c_vp, c_i32]),
+    "m2_debug_transformer_plan": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.c_char_p,
+                                          c_size]),
     "m2_loss_column_count": (c_i32, [c_i32]),
     "m2_loss_column_name": (ctypes.c_char_p, [c_i32, c_i32]),
     "m2_conv1d_strided": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_i32, c_i32, c_i32, c_i32, c_vp,

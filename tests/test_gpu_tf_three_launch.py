@@ -1,7 +1,7 @@
 """GPU: the three-launch transformer layers (csrc/transformer_fused.hip:
 ln_gemm_kernel with its SRC_X / SRC_EMBED / SRC_EXPAND row sources,
-post_attn_kernel<H, NN, NW>, the drivers run_stack and run_layer of
-m2_runtime.hip) and the model shapes off the two stages: what every handle
+post_attn_kernel<H, NN, NW>, forms 0 to 2 of the launch plan that run_tf_plan
+of m2_runtime.hip executes) and the model shapes off the two stages: what every handle
 with num_heads != 2 runs, and what M2_TF_LAYER=0 selects.
 
 Reference: the CPU oracle (oracle/m2tts_oracle.py) in float64 (ref64).  The

@@ -13,6 +13,9 @@
 // The vocoder's launch plan (csrc/vocoder_launch.h) runs here too: plan_vocoder_launch against
 // the decision rules the launchers carried before it (old_* below), over a sweep of calls, switch
 // tables and workgroup-slot counts, with the plans' invariants and three pinned lines.
+// The transformer stacks' launch plan (csrc/transformer_plan.h) likewise: plan_transformer against the
+// rules the drivers and launchers carried before it (old_transformer), over a sweep of handles, calls
+// and switch tables, with the plans' invariants and three pinned lines (check_transformer_plan).
 // The training losses' plans (csrc/losses_plan.h) run here too: the discriminator
 // calls' sizes and workspace layout against the formulas they replaced, and the
 // backward kernels' launch plans against their limits, and the spectral backward's
@@ -33,6 +36,7 @@
 
 #include "losses_plan.h"
 #include "m2_model.h"
+#include "transformer_plan.h"
 #include "decoder_grad_plan.h"
 #include "encoder_grad_plan.h"
 #include "vocoder_grad_plan.h"
@@ -1044,9 +1048,295 @@ static void check_encoder_grad() {
     std::printf(" (%d plans, %d rows)\n", plans, rows_seen);
 }
 
+// ---------------------------------------------------------------------------
+// The transformer stacks' launch plan (csrc/transformer_plan.h) against the rules the drivers
+// and launchers carried before it: tfl_use / tf_chain / tf_first_fused / text_encoder_layers /
+// mel_decoder / run_tfl / run_stack / run_layer / final_projection of m2_runtime.hip, tfl_rb /
+// tfl_qs2 and the launchers' own overrides of transformer_layer.hip, tf_waves of
+// transformer_fused.hip.  Each old_* returns the launch sequence with its geometry.
+struct OldTfCall {
+    int H, heads, n, mel;  // mel 0: the encoder's call (no final projection)
+    bool tfused, att_f32, wide_last;
+    int src;  // 0 x, 1 embed, 2 expand
+    bool masked, devT, ragged;
+    int B, N;
+};
+struct OldTfRow {
+    const char* kind;
+    int layer, next, op, rb, qs2, waves, grid, thr;
+};
+struct OldTf {
+    int form = 0;
+    int32_t err = 0;
+    const char* msg = nullptr;
+    bool projected = false;
+    std::vector<OldTfRow> rows;
+};
+static bool old_tfl_supported(int H, int heads) { return heads == 2 && (H == 32 || H == 64 || H == 96); }
+static bool old_tfl_proj_supported(int H, int NN) {
+    return (H == 32 && (NN == 32 || NN == 64)) || (H == 64 && (NN == 64 || NN == 80)) || (H == 96 && (NN == 80 || NN == 96));
+}
+static bool old_post_next_supported(int H, int NN) {
+    return (H == 32 && (NN == 96 || NN == 32 || NN == 64)) || (H == 64 && (NN == 192 || NN == 64 || NN == 80)) ||
+           (H == 96 && (NN == 288 || NN == 80 || NN == 96));
+}
+static bool old_src_fused_supported(int H, int N) { return (H == 32 && N == 96) || (H == 64 && N == 192) || (H == 96 && N == 288); }
+static int old_npad(int N) { return (N + 63) / 64 * 64; }
+static int old_tfl_rb(int B, int N, const Switches& s) {
+    if (s.tfl_rb) return s.tfl_rb;
+    const long tiles16 = (long)B * (old_npad(N) / 16);
+    return tiles16 >= 4 * 256 ? 4 : (tiles16 > 256 ? 2 : 1);
+}
+static int old_ntile(int N, int rb) { return (old_npad(N) + 16 * rb - 1) / (16 * rb); }
+static int old_tf_waves(int R, const Switches& s) {
+    if (s.tf_waves) return s.tf_waves;
+    return (R + 31) / 32 < 2 * 256 ? 8 : 4;
+}
+static bool old_tfl_use(const OldTfCall& c, const Switches& s) {
+    return s.tf_layer && c.tfused && !c.att_f32 && c.n > 0 && old_tfl_supported(c.H, c.heads);
+}
+static bool old_tf_chain(const OldTfCall& c, const Switches& s) {
+    return s.tf_chain && c.tfused && old_post_next_supported(c.H, 3 * c.H);
+}
+static OldTf old_transformer(const OldTfCall& c, const Switches& s) {
+    OldTf o;
+    const int H = c.H, n = c.n, R = c.B * c.N;
+    o.form = old_tfl_use(c, s) ? 3 : (!c.tfused ? 0 : (old_tf_chain(c, s) ? 2 : 1));  // m2_debug_transformer_form
+    if (c.B == 0 || c.N == 0) return o;
+    if (c.devT && !(old_tfl_use(c, s) && old_tfl_proj_supported(H, c.mel))) {
+        o.err = M2_E_ARG, o.msg = "mel decoder: a device frame count needs the one-launch layers";
+        return o;
+    }
+    if (c.ragged && !old_tfl_use(c, s)) {
+        o.err = M2_E_SHAPE, o.msg = "mel decoder: per-utterance frame counts need the one-launch layers "
+                                    "(hidden_dim 32 / 64 / 96 with 2 heads, M2_TF_LAYER not 0)";
+        return o;
+    }
+    auto plain = [&](const char* kind, int layer, int op = 0) { o.rows.push_back({kind, layer, 0, op, 0, 0, 0, 0, 0}); };
+    auto gemm = [&](const char* kind, int layer, int next = 0) {  // launch_ln_gemm / launch_post_attn*: tf_waves, 32-row tiles
+        const int nw = old_tf_waves(R, s);
+        o.rows.push_back({kind, layer, next, 0, 0, 0, nw, (R + 31) / 32, 64 * nw});
+    };
+    auto final_projection = [&] {
+        if (c.mel == 0) return;  // text_encoder_layers ends with the layers
+        if (c.tfused && old_post_next_supported(H, c.mel)) gemm("final_ln_gemm", n);
+        else plain("final_linear", n);
+    };
+    if (old_tfl_use(c, s)) {
+        {  // launch_tfl_first
+            int rb = old_tfl_rb(c.B, c.N, s) > 1 ? 2 : 1;
+            if ((long)c.B * (old_npad(c.N) / 16) >= 8L * 256) rb = 4;
+            if (s.tfl_first_rb) rb = s.tfl_first_rb;
+            if (c.masked && s.tfl_rb_masked) rb = s.tfl_rb_masked;
+            if (!c.masked && s.tfl_rb_unmasked) rb = s.tfl_rb_unmasked;
+            o.rows.push_back({"tfl_first", 0, 0, 0, rb, 0, 0, c.B * old_ntile(c.N, rb), (rb == 4 ? 4 : 8) * 64});
+        }
+        for (int l = 0; l < n; ++l) {  // run_tfl, launch_tfl_layer
+            const int next = l + 1 < n ? 1 : (c.mel > 0 && old_tfl_proj_supported(H, c.mel) ? 2 : 0);
+            const int rb = c.masked && s.tfl_rb_masked ? s.tfl_rb_masked
+                           : !c.masked && s.tfl_rb_unmasked ? s.tfl_rb_unmasked : old_tfl_rb(c.B, c.N, s);
+            int qs2 = s.tfl_qs2 >= 0 ? s.tfl_qs2 : 12;
+            if (qs2 == 12 && (c.masked || (c.wide_last && l == n - 1))) qs2 = H / 2 >= 48 ? 3 : 4;
+            o.rows.push_back({"tfl_layer", l, next, 0, rb, qs2, 0, c.B * old_ntile(c.N, rb), 8 * 64});
+            if (next == 2) o.projected = true;
+        }
+        if (!o.projected) final_projection();
+        return o;
+    }
+    const bool chain = old_tf_chain(c, s);
+    const bool first_fused = chain && n > 0 && old_src_fused_supported(H, 3 * H);
+    bool qkv_ready = false;
+    if (c.src == 1) {
+        if (first_fused) gemm("embed_ln_gemm", 0), qkv_ready = true;
+        else plain("embed_pe", 0);
+    } else if (c.src == 2) {
+        if (first_fused) gemm("expand_ln_gemm", 0), qkv_ready = true;
+        else plain("lr_expand", 0);
+    }
+    if (!chain) {  // run_stack -> run_layer
+        for (int l = 0; l < n; ++l) {
+            if (c.tfused) {
+                gemm("ln_gemm", l);
+                plain("attention", l);
+                gemm("post_attn", l);
+            } else {
+                plain("linear", l, 0);
+                plain("attention", l);
+                for (int op = 1; op < 4; ++op) plain("linear", l, op);
+            }
+        }
+    } else if (n > 0) {
+        if (!qkv_ready) gemm("ln_gemm", 0);
+        for (int l = 0; l < n; ++l) {
+            plain("attention", l);
+            if (l + 1 < n) gemm("post_attn_next", l, 1);
+            else if (c.mel > 0 && old_post_next_supported(H, c.mel)) gemm("post_attn_next", l, 2), o.projected = true;
+            else gemm("post_attn", l);
+        }
+    }
+    if (!o.projected) final_projection();
+    return o;
+}
+
+// The old rules' sequence in the printed format of transformer_plan.h (the pinned lines come from here).
+static std::string old_tf_line(const OldTfCall& c, const OldTf& o) {
+    char b[256];
+    static const char* const src[] = {"x", "embed", "expand"};
+    std::snprintf(b, sizeof b, "%s form=%d H=%d heads=%d layers=%d B=%d N=%d src=%s masked=%d devT=%d ragged=%d projected=%d",
+                  c.mel ? "dec" : "enc", o.form, c.H, c.heads, c.n, c.B, c.N, src[c.src], (int)c.masked, (int)c.devT,
+                  (int)c.ragged, (int)o.projected);
+    std::string line = b;
+    if (o.err) line += std::string(" error=\"") + o.msg + "\"";
+    for (const OldTfRow& r : o.rows) {
+        const std::string k = r.kind;
+        if (k == "embed_pe" || k == "lr_expand" || k == "final_linear") std::snprintf(b, sizeof b, " %s", r.kind);
+        else if (k == "attention") std::snprintf(b, sizeof b, " %s%d", r.kind, r.layer);
+        else if (k == "linear") std::snprintf(b, sizeof b, " %s%d[op=%d]", r.kind, r.layer, r.op);
+        else if (k == "final_ln_gemm") std::snprintf(b, sizeof b, " %s[waves=%d grid=%d thr=%d]", r.kind, r.waves, r.grid, r.thr);
+        else if (k == "post_attn_next")
+            std::snprintf(b, sizeof b, " %s%d[next=%d waves=%d grid=%d thr=%d]", r.kind, r.layer, r.next, r.waves, r.grid, r.thr);
+        else if (k == "tfl_first") std::snprintf(b, sizeof b, " %s%d[rb=%d grid=%d thr=%d]", r.kind, r.layer, r.rb, r.grid, r.thr);
+        else if (k == "tfl_layer")
+            std::snprintf(b, sizeof b, " %s%d[next=%d rb=%d qs2=%d grid=%d thr=%d]", r.kind, r.layer, r.next, r.rb, r.qs2, r.grid, r.thr);
+        else std::snprintf(b, sizeof b, " %s%d[waves=%d grid=%d thr=%d]", r.kind, r.layer, r.waves, r.grid, r.thr);
+        line += b;
+    }
+    return line;
+}
+
+static long g_tf_plans = 0, g_tf_diff = 0, g_tf_inv = 0;
+
+static void check_tf_plan(const OldTfCall& oc, const Switches& s) {
+    TfCall c;
+    if (oc.n > 0 && oc.wide_last) c.set_wide(oc.n - 1);
+    c.decoder = oc.mel > 0;
+    c.H = oc.H, c.heads = oc.heads, c.layers = oc.n, c.proj = oc.mel;
+    c.tfused = oc.tfused, c.att_f32 = oc.att_f32;
+    c.src = (TfSrc)oc.src;
+    c.masked = oc.masked, c.device_T = oc.devT, c.ragged = oc.ragged;
+    c.B = oc.B, c.N = oc.N;
+    const TfPlan p = plan_transformer(c, s);
+    const OldTf o = old_transformer(oc, s);
+    ++g_tf_plans;
+    bool same = p.form == o.form && p.error.code == o.err && (p.error.text == nullptr) == (o.msg == nullptr) &&
+                (!o.msg || !std::strcmp(p.error.text, o.msg)) && p.projected == o.projected &&
+                p.rows.size() == o.rows.size();
+    for (size_t i = 0; same && i < o.rows.size(); ++i) {
+        const TfRow& r = p.rows[i];
+        const OldTfRow& q = o.rows[i];
+        same = !std::strcmp(kTfKindNames[(int)r.kind], q.kind) && r.layer == q.layer && r.next == q.next && r.op == q.op &&
+               r.rb == q.rb && r.qs2 == q.qs2 && r.waves == q.waves && r.grid == q.grid && r.threads == q.thr;
+    }
+    bool inv = true;
+    int endings = 0, fused_end = 0;
+    for (const TfRow& r : p.rows) {
+        const bool has_grid = r.waves > 0 || r.rb > 0;
+        inv = inv && (!has_grid || (r.grid >= 1 && r.threads >= 64 && r.threads % 64 == 0 && r.threads <= 1024));
+        inv = inv && (has_grid || (r.grid == 0 && r.threads == 0));
+        endings += r.kind == TfKind::FinalLnGemm || r.kind == TfKind::FinalLinear;
+        fused_end += r.next == 2;
+    }
+    const bool runs = oc.B > 0 && oc.N > 0 && !p.error.code;
+    // a form-3 plan: the first launch, one launch per layer, and an ending of its own exactly when a
+    // projection is asked for (the decoder) and the last layer did not run it
+    if (runs && p.form == 3) inv = inv && (int)p.rows.size() == 1 + oc.n + (oc.mel > 0 && !p.projected ? 1 : 0);
+    inv = inv && p.projected == (fused_end == 1) && fused_end <= 1;
+    if (runs) inv = inv && endings == (oc.mel > 0 && !p.projected ? 1 : 0);
+    else inv = inv && p.rows.empty() && !p.projected;
+    char line[2048];
+    const int len = p.print(line, sizeof line);
+    inv = inv && len > 0 && len < (int)sizeof line && (int)std::strlen(line) == len;
+    same = same && old_tf_line(oc, o) == line;
+    if ((!same || !inv) && g_tf_diff + g_tf_inv < 5)
+        std::printf("  %s%s| %s\n    old: %s\n", same ? "" : "DIFFERS ", inv ? "" : "INVARIANT ", line, old_tf_line(oc, o).c_str());
+    g_tf_diff += !same;
+    g_tf_inv += !inv;
+}
+
+static void expect_tf_line(const char* what, const OldTfCall& oc, const char* want) {
+    const std::string got = old_tf_line(oc, old_transformer(oc, Switches{}));
+    const bool ok = got == want;
+    std::printf("  %s: %s%s\n", what, got.c_str(), ok ? "" : " (UNEXPECTED)");
+    g_bad += !ok;
+    check_tf_plan(oc, Switches{});  // and the planner prints the same line
+}
+
+static void check_transformer_plan() {
+    std::vector<Switches> sws(1);
+    auto with = [&](auto set) {
+        Switches s;
+        set(s);
+        sws.push_back(s);
+    };
+    with([](Switches& s) { s.tf_layer = false; });
+    with([](Switches& s) { s.tf_chain = false; });
+    with([](Switches& s) { s.tf_layer = s.tf_chain = false; });
+    for (const int v : {4, 8}) with([v](Switches& s) { s.tf_waves = v; });
+    for (const int v : {1, 2, 4}) {
+        with([v](Switches& s) { s.tfl_rb = v; });
+        with([v](Switches& s) { s.tfl_first_rb = v; });
+        with([v](Switches& s) { s.tfl_rb_masked = v; });
+        with([v](Switches& s) { s.tfl_rb_unmasked = v; });
+    }
+    for (const int v : {0, 2, 3, 4, 12}) with([v](Switches& s) { s.tfl_qs2 = v; });
+    with([](Switches& s) { s.tfl_rb = 4, s.tfl_first_rb = 1, s.tfl_rb_masked = 2; });  // the overrides' order
+    // B x N on both sides of each threshold: 256 / 1024 sixteen-row tiles (16, 17, 64 x 256), 2048
+    // (128 x 256), 512 thirty-two-row tiles (127, 128 x 128); 0: the empty call
+    const int Bs[] = {0, 1, 2, 16, 17, 64, 127, 128}, Ns[] = {0, 1, 63, 64, 65, 128, 256, 500, 2600};
+    struct Mode {
+        bool devT, ragged;
+    };
+    const Mode modes[] = {{false, false}, {true, false}, {false, true}, {true, true}};
+    for (const int H : {32, 48, 64, 96, 128})
+        for (const int heads : {1, 2, 3, 4, 6})
+            for (const int mel : {0, 32, 40, 48, 64, 80, 96})
+                for (const int n : {0, 1, 2, 3})
+                    for (int flags = 0; flags < 8; ++flags) {
+                        const bool tfused = flags & 1, att_f32 = flags & 2, wide_last = flags & 4;
+                        // the geometry rules read (B, N, H, heads, masked, wide, switches) and not the
+                        // rest of the handle: every B x N on the fused two-layer handles; on every
+                        // handle (every layer count and form) the shapes on both sides of each tile
+                        // threshold, a small one and an empty one
+                        const bool all_shapes = n == 2 && tfused && !att_f32;
+                        for (const int B : Bs)
+                            for (const int N : Ns) {
+                                const bool threshold = (N == 256 && (B == 16 || B == 17 || B == 64 || B == 128)) ||
+                                                       (N == 128 && (B == 127 || B == 128));
+                                if (!all_shapes && !(threshold || (B == 2 && N == 65) || (B == 0 && N == 63))) continue;
+                                for (int src = 0; src < 3; ++src)
+                                    for (int masked = 0; masked < 2; ++masked)
+                                        for (const Mode& md : modes) {
+                                            // (a device T or ragged rows change the refusal and no geometry)
+                                            if ((md.devT || md.ragged) && !(B == 0 || B == 2 || B == 17 || (all_shapes && B == 128)))
+                                                continue;
+                                            const OldTfCall c{H, heads, n, mel, tfused, att_f32, wide_last, src, masked != 0,
+                                                              md.devT, md.ragged, B, N};
+                                            for (const Switches& s : sws) check_tf_plan(c, s);
+                                        }
+                            }
+                    }
+    std::printf("transformer plans: %ld plans over %zu switch tables, %ld differ from the old rules, %ld break an invariant\n",
+                g_tf_plans, sws.size(), g_tf_diff, g_tf_inv);
+    g_bad += (int)(g_tf_diff + g_tf_inv);
+    // three calls' lines, literally (default switches, no wide layer)
+    expect_tf_line("stage1 encoder B=32 S=100 masked", OldTfCall{64, 2, 2, 0, true, false, false, 1, true, false, false, 32, 100},
+                   "enc form=3 H=64 heads=2 layers=2 B=32 N=100 src=embed masked=1 devT=0 ragged=0 projected=0 "
+                   "tfl_first0[rb=1 grid=256 thr=512] tfl_layer0[next=1 rb=1 qs2=4 grid=256 thr=512] "
+                   "tfl_layer1[next=0 rb=1 qs2=4 grid=256 thr=512]");
+    expect_tf_line("stage1 decoder B=32 cap 500 devT", OldTfCall{64, 2, 2, 64, true, false, false, 2, false, true, false, 32, 500},
+                   "dec form=3 H=64 heads=2 layers=2 B=32 N=500 src=expand masked=0 devT=1 ragged=0 projected=1 "
+                   "tfl_first0[rb=2 grid=512 thr=512] tfl_layer0[next=1 rb=4 qs2=12 grid=256 thr=512] "
+                   "tfl_layer1[next=2 rb=4 qs2=12 grid=256 thr=512]");
+    expect_tf_line("stage2 decoder B=16 T=2600 ragged", OldTfCall{96, 2, 3, 80, true, false, false, 0, false, false, true, 16, 2600},
+                   "dec form=3 H=96 heads=2 layers=3 B=16 N=2600 src=x masked=0 devT=0 ragged=1 projected=1 "
+                   "tfl_first0[rb=4 grid=656 thr=256] tfl_layer0[next=1 rb=4 qs2=12 grid=656 thr=512] "
+                   "tfl_layer1[next=1 rb=4 qs2=12 grid=656 thr=512] tfl_layer2[next=2 rb=4 qs2=12 grid=656 thr=512]");
+}
+
 int main() {
     check_strips();
     check_launch_plans();
+    check_transformer_plan();
     check_disc_plans();
     check_geometries();
     check_spectral_bwd();
