@@ -901,6 +901,47 @@ int32_t m2_layer_norm_backward(const float* g_y, const float* x, const float* ga
 int32_t m2_length_regulator_backward(const float* d_reg, const int32_t* cum, int32_t B, int32_t S, int32_t H,
                                      int32_t T_out, float* d_enc, void* stream);
 
+/* ---- the duration predictor's training forward and backward ----------------
+ * DurationPredictor from its raw parameters, as the encoder above.  params: 10
+ * device pointers in parameters() order: (conv.weight [H,H,3], conv.bias [H],
+ * norm.weight [H], norm.bias [H]) of the two ConvBlocks, projection.weight
+ * [1,H,1], projection.bias [1].  bn: 8 vectors [H] in one array [8,H], block by
+ * block: alpha = gamma / sqrt(running_var + eps), beta' = beta - running_mean
+ * alpha (the eval-mode BatchNorm as the affine of m2_conv1d), running_mean,
+ * invstd = 1 / sqrt(running_var + eps).  The running statistics are constants:
+ * they get no gradient and nothing writes them; no dropout.  The dimension
+ * arguments are (H, B, S); enc is [B,S,H].  Supported: kernel size 3, H a
+ * multiple of 8 from 16 to 128, S <= 2^20, B S <= 2^24, B H S <= 2^30 (else M2_E_SHAPE; the
+ * _bytes queries return 0).  B = 0 or S = 0: nothing to do, M2_OK.
+ *
+ * m2_duration_train_forward: dur [B,S], bit-equal to the stand-alone module's
+ * forward (m2_conv1d with the affine and ReLU twice, the first reading enc
+ * transposed, then the k = 1 projection with softplus), the two blocks writing
+ * into the tape: y1, y2 [B,H,S], post-ReLU.  m2_duration_tape_map(index = 0, 1)
+ * names a map's offset (in floats) and its channel count.  The conv outputs u
+ * are not kept: the backward recomputes them with the same conv launch.
+ *
+ * m2_duration_backward: given d_dur [B,S]: d_enc [B,S,H] (or NULL) and grads
+ * (10 pointers, NULL skips, accumulate adds with one fp32 addition per
+ * element).  d gamma is formed per element from u, so it is right where gamma
+ * is 0 or negative.  No floating-point atomics: equal inputs give equal bits,
+ * and d_enc of an utterance does not depend on the rest of the batch.  A short
+ * workspace, and a short tape in m2_duration_train_forward, is M2_E_ARG;
+ * m2_duration_backward takes no tape size: the tape must be the one the forward
+ * of this shape filled (m2_duration_tape_bytes), which is the caller's to keep.
+ *
+ * m2_debug_duration_grad_plan: as m2_debug_decoder_grad_plan (the format is in
+ * csrc/duration_grad_plan.h). */
+size_t m2_duration_tape_bytes(int32_t H, int32_t B, int32_t S);
+int32_t m2_duration_tape_map(int32_t H, int32_t B, int32_t S, int32_t index, size_t* offset_floats, int32_t* width);
+int32_t m2_duration_train_forward(const float* const* params, const float* bn, int32_t H, const float* enc, int32_t B,
+                                  int32_t S, float* dur, void* tape, size_t tape_bytes, void* stream);
+size_t m2_duration_backward_workspace_bytes(int32_t H, int32_t B, int32_t S);
+int32_t m2_duration_backward(const float* const* params, const float* bn, int32_t H, const float* enc, int32_t B,
+                             int32_t S, const void* tape, const float* d_dur, float* d_enc, float* const* grads,
+                             int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream);
+int32_t m2_debug_duration_grad_plan(int32_t H, int32_t B, int32_t S, char* out, size_t cap);
+
 /* ---- measurement ----------------------------------------------------------
  * Kernel timing with HIP events recorded on the launch stream around each of
  * the fused vocoder's kernels (bench.py's roofline).  enable: allocate event

@@ -168,6 +168,13 @@ _SIGNATURES = {
     "m2_layer_norm_backward_workspace_bytes": (c_size, [c_i32, c_i32]),
     "m2_layer_norm_backward": (c_i32, [c_vp] * 4 + [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_size, c_vp]),
     "m2_length_regulator_backward": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    "m2_duration_tape_bytes": (c_size, [c_i32] * 3),
+    "m2_duration_tape_map": (c_i32, [c_i32] * 4 + [c_vp, c_vp]),
+    "m2_duration_train_forward": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp, c_size, c_vp]),
+    "m2_duration_backward_workspace_bytes": (c_size, [c_i32] * 3),
+    "m2_duration_backward": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_size,
+                                     c_vp]),
+    "m2_debug_duration_grad_plan": (c_i32, [c_i32] * 3 + [c_vp, c_size]),
     "m2_front_bytes": (c_size, [c_vp, c_i32, c_i32]),
     "m2_inference_workspace_bytes": (c_size, [c_vp, c_i32, c_i32, c_i32]),
     "m2_inference_front": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_vp, c_size, c_vp, c_size, c_vp, c_vp]),

@@ -868,6 +868,121 @@ def regulate_backward(d_reg: Tensor, cum: Tensor, S: int) -> Tensor:
     return d_enc
 
 
+DURATION_PARAMS = 10
+DURATION_TAPE_NAMES = ("y1", "y2")
+
+
+def batchnorm_eval_stats(weight: Tensor, bias: Tensor, mean: Tensor, var: Tensor, eps: float) -> Tensor:
+    """One block's four vectors of ``duration_train_forward``'s ``bn_stats`` as a [4, H] tensor: alpha and
+    beta' exactly as ``batchnorm_eval_affine`` returns them, the running mean, and invstd = 1 / sqrt(var + eps)."""
+    alpha, beta = batchnorm_eval_affine(weight.detach(), bias.detach(), mean, var, eps)
+    invstd = 1.0 / torch.sqrt(var + eps)
+    return torch.stack([alpha, beta, mean.to(torch.float32), invstd])
+
+
+def _duration_params(params, bn_stats):
+    """DurationPredictor's 10 parameters (parameters() order) as contiguous float32 device tensors, their
+    pointer array, bn_stats as one contiguous [8, H] tensor (eight [H] vectors, or two [4, H] blocks), and H."""
+    keep = [f32c(p.detach()) for p in params]
+    if len(keep) != DURATION_PARAMS:
+        raise ValueError(f"duration: (conv.weight, conv.bias, norm.weight, norm.bias) x 2, projection.weight, "
+                         f"projection.bias in parameters() order, got {len(keep)}")
+    require_device(*keep, what="duration parameter")
+    H = int(keep[0].shape[0])
+    shapes = [(H, H, 3), (H,), (H,), (H,)] * 2 + [(1, H, 1), (1,)]
+    for i, (t, want) in enumerate(zip(keep, shapes)):
+        if tuple(t.shape) != want:
+            raise ValueError(f"duration: parameter {i} must be {want} (kernel size 3), got {tuple(t.shape)}")
+    bn = bn_stats if isinstance(bn_stats, Tensor) else torch.cat([b.detach().reshape(-1, H) for b in bn_stats])
+    require_device(bn, what="duration bn_stats")
+    bn = f32c(bn.detach().reshape(-1, H))
+    if tuple(bn.shape) != (8, H):
+        raise ValueError(f"duration: bn_stats must be 8 vectors [{H}] (alpha, beta', mean, invstd per block), got "
+                         f"{tuple(bn.shape)}")
+    return keep, (ctypes.c_void_p * len(keep))(*[t.data_ptr() for t in keep]), bn, H
+
+
+def _duration_enc(enc: Tensor, H: int) -> Tensor:
+    require_device(enc, what="duration")
+    if enc.dim() != 3 or enc.shape[2] != H:
+        raise ValueError(f"duration: enc must be [B, S, {H}], got {tuple(enc.shape)}")
+    return f32c(enc.detach())
+
+
+def duration_supported(H: int) -> bool:
+    """Whether m2_duration_backward takes a DurationPredictor of this width (host arithmetic only)."""
+    return int(_lib.load().m2_duration_tape_bytes(H, 1, 1)) != 0
+
+
+def duration_train_forward(params, bn_stats, enc: Tensor):
+    """DurationPredictor's forward from its raw parameters and the eval-mode BatchNorm constants, keeping a
+    tape (m2_duration_train_forward): (dur [B,S], bit-equal to the stand-alone module's forward, and the tape,
+    a uint8 tensor that ``duration_tape_maps`` names and ``duration_backward`` reads).  ``bn_stats``: alpha,
+    beta', running mean and invstd of block 1, then of block 2 (``batchnorm_eval_stats`` per block)."""
+    keep, ptrs, bn, H = _duration_params(params, bn_stats)
+    enc = _duration_enc(enc, H)
+    B, S, _ = enc.shape
+    dev = enc.device
+    need = int(_lib.load().m2_duration_tape_bytes(H, B, S))
+    if need == 0:
+        raise M2Error(f"duration_train_forward: unsupported shape H = {H}, B={B} S={S}")
+    tape = torch.empty(need, dtype=torch.uint8, device=dev)
+    dur = torch.empty(B, S, device=dev, dtype=torch.float32)
+    _lib.call("m2_duration_train_forward", ptrs, _ptr(bn), H, _ptr(enc), B, S, _ptr(dur), _ptr(tape), tape.numel(),
+              stream_handle(dev))
+    return dur, tape
+
+
+def duration_tape_maps(tape: Tensor, H: int, B: int, S: int) -> dict:
+    """The maps of a tape as float32 views (m2_duration_tape_map): y1 and y2 [B,H,S], the two ConvBlocks'
+    outputs (post-ReLU)."""
+    lib = _lib.load()
+    flat = tape[:tape.numel() // 4 * 4].view(torch.float32)
+    off, width = ctypes.c_size_t(), ctypes.c_int32()
+    maps = {}
+    for i, name in enumerate(DURATION_TAPE_NAMES):
+        _lib.check(lib.m2_duration_tape_map(H, B, S, i, ctypes.byref(off), ctypes.byref(width)), "m2_duration_tape_map")
+        maps[name] = flat[off.value:off.value + B * S * width.value].view(B, width.value, S)
+    return maps
+
+
+def duration_backward(params, bn_stats, enc: Tensor, tape: Tensor, d_dur: Tensor, need_enc: bool = True, need=None,
+                      accumulate=False):
+    """The gradients of DurationPredictor given d_dur [B,S] (m2_duration_backward): (d_enc [B,S,H] or None,
+    the 10 gradients in parameters() order, None where ``need[i]`` is false).  ``accumulate``: a list of that
+    many tensors (or None entries) to add the gradients to instead of new tensors."""
+    keep, ptrs, bn, H = _duration_params(params, bn_stats)
+    enc = _duration_enc(enc, H)
+    B, S, _ = enc.shape
+    dev = enc.device
+    require_device(tape, d_dur, what="duration_backward")
+    d_dur = f32c(d_dur.detach().to(torch.float32))
+    if tuple(d_dur.shape) != (B, S):
+        raise ValueError(f"duration_backward: d_dur must be {(B, S)}, got {tuple(d_dur.shape)}")
+    lib = _lib.load()
+    tape_bytes = int(lib.m2_duration_tape_bytes(H, B, S))
+    if tape_bytes == 0:
+        raise M2Error(f"duration_backward: unsupported shape H = {H}, B={B} S={S}")
+    if tape.numel() < tape_bytes:
+        raise ValueError("duration_backward: the tape is not that of this shape")
+    onto = accumulate if accumulate else None
+    want = [True] * len(keep) if need is None else [bool(n) for n in need]
+    grads = []
+    for i, (p, w) in enumerate(zip(keep, want)):
+        if not w:
+            grads.append(None)
+        elif onto is not None and onto[i] is not None:
+            grads.append(onto[i])
+        else:
+            grads.append(torch.empty_like(p) if onto is None else torch.zeros_like(p))
+    gp = (ctypes.c_void_p * len(keep))(*[_ptr(g) for g in grads])
+    d_enc = torch.empty_like(enc) if need_enc else None
+    ws = torch.empty(max(int(lib.m2_duration_backward_workspace_bytes(H, B, S)), 1), dtype=torch.uint8, device=dev)
+    _lib.call("m2_duration_backward", ptrs, _ptr(bn), H, _ptr(enc), B, S, _ptr(tape), _ptr(d_dur), _ptr(d_enc), gp,
+              0 if onto is None else 1, _ptr(ws), ws.numel(), stream_handle(dev))
+    return d_enc, grads
+
+
 def embed_positional(ids: Tensor, emb: Tensor, pe: Tensor, scale: float) -> Tensor:
     """y[b,s,:] = emb[ids[b,s],:] * scale + pe[s,:]; ids outside [0, vocab) read a zero row."""
     require_device(ids, emb, pe, what="embedding")

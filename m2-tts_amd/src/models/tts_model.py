@@ -32,7 +32,7 @@ from m2amd import _lib, ops, runtime
 from m2amd.runtime import HandleCache, make_config
 
 from .components import (LightweightResBlock, PositionalEncoding, TransformerEncoderLayer, VariancePredictor,
-                         count_parameters, create_padding_mask, initialize_weights)
+                         _eval_only, count_parameters, create_padding_mask, initialize_weights)
 
 logger = logging.getLogger(__name__)
 Tensor = torch.Tensor
@@ -165,14 +165,73 @@ class TextEncoder(nn.Module):
         return ops.layer_norm(x, self.norm.weight, self.norm.bias), mask
 
 
+class _DurationGrad(torch.autograd.Function):
+    """DurationPredictor.forward with a graph: ops.duration_train_forward on the
+    module's own parameters and the eval-mode BatchNorm constants, and
+    ops.duration_backward on grad_output (once differentiable).  Arguments:
+    encoder_output, the constants [8, H] (ops.batchnorm_eval_stats per block),
+    then the 10 parameters in parameters() order."""
+
+    @staticmethod
+    def forward(ctx, enc, bn, *params):
+        dur, tape = ops.duration_train_forward(params, bn, enc)
+        ctx.save_for_backward(enc, bn, *params)
+        ctx.tape = tape
+        return dur
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        enc, bn, *params = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        d_enc, grads = ops.duration_backward(params, bn, enc, ctx.tape, grad_output, need_enc=need[0], need=need[2:])
+        return (d_enc, None, *grads)
+
+
 class DurationPredictor(nn.Module):
-    """softplus(VariancePredictor(enc^T)) -> [B, S] (reference tts_model.py:92-117)."""
+    """softplus(VariancePredictor(enc^T)) -> [B, S] (reference tts_model.py:92-117).
+
+    ``enable_backward()`` gives ``forward`` a graph: when gradients are enabled
+    and ``encoder_output`` or a parameter requires grad, the durations come
+    from the per-op path on the module's own parameters (inside an M2TTSModel
+    too: no handle, the stand-alone module's bits) and carry a ``grad_fn``
+    whose backward fills the 10 ``.grad`` and ``encoder_output.grad`` on the
+    GPU.  The gradient is that of the function this module computes: BatchNorm
+    with its running statistics as constants (the buffers get no gradient and
+    are not written), no dropout (models/components.py).  Off by default; with
+    it off, under ``no_grad`` or with nothing requiring grad, ``forward`` is
+    unchanged."""
+
+    backward_enabled = False
 
     def __init__(self, hidden_dim: int = 64, kernel_size: int = 3, dropout: float = 0.1):
         super().__init__()
         self.predictor = VariancePredictor(hidden_dim, kernel_size, dropout)
 
+    def enable_backward(self, enabled: bool = True) -> "DurationPredictor":
+        """Switch the graph of ``forward`` on or off (a plain attribute, no
+        state_dict entry).  Supported: kernel size 3, H a multiple of 8 from 16
+        to 128."""
+        if enabled:
+            conv = self.predictor.conv_layers[0].conv
+            k, h = int(conv.kernel_size[0]), int(conv.out_channels)
+            if k != 3 or h % 8 != 0 or not 16 <= h <= 128:
+                raise NotImplementedError(f"DurationPredictor.enable_backward: kernel size 3 and hidden_dim a multiple "
+                                          f"of 8 from 16 to 128; got kernel size {k}, hidden_dim {h}")
+        self.backward_enabled = bool(enabled)
+        return self
+
     def forward(self, encoder_output: Tensor) -> Tensor:
+        if self.backward_enabled and torch.is_grad_enabled():
+            params = list(self.parameters())
+            if encoder_output.requires_grad or any(p.requires_grad for p in params):
+                ops.require_device(encoder_output, *params, what="DurationPredictor")
+                stats = []
+                for blk in self.predictor.conv_layers:
+                    _eval_only(blk)
+                    n = blk.norm
+                    stats.append(ops.batchnorm_eval_stats(n.weight, n.bias, n.running_mean, n.running_var, n.eps))
+                return _DurationGrad.apply(encoder_output, torch.cat(stats), *params)
         hm = _owner_handle(self, "duration_predictor", encoder_output.device)
         if hm is not None:
             return hm.duration(encoder_output)
@@ -411,7 +470,20 @@ class SimpleVocoder(nn.Module):
 
 class M2TTSModel(nn.Module):
     """Text encoder -> duration predictor -> length regulator -> mel decoder ->
-    vocoder (reference tts_model.py:300-459)."""
+    vocoder (reference tts_model.py:300-459).
+
+    ``enable_backward()`` gives ``forward`` a graph: when gradients are enabled
+    and a parameter requires grad, ``forward`` composes the stage modules with
+    their switches on (no handle: an optimizer step changes every weight) and
+    returns the same six keys, ``mel_output`` and ``duration_pred`` carrying
+    ``grad_fn``s, so the reference's training step (a mel loss plus a duration
+    loss, ``backward()``, an optimizer step) runs on the GPU.  The length
+    regulator gives durations no gradient, as in the reference.  The vocoder's
+    switch stays the caller's (``model.vocoder.enable_backward()``).  Off by
+    default; with it off, under ``no_grad`` or with nothing requiring grad,
+    ``forward`` is unchanged."""
+
+    backward_enabled = False
 
     def __init__(self, vocab_size: int = 256, hidden_dim: int = 64, mel_channels: int = 64,
                  text_encoder_layers: int = 2, decoder_layers: int = 2, num_heads: int = 2, dropout: float = 0.1,
@@ -432,6 +504,24 @@ class M2TTSModel(nn.Module):
         total, trainable = count_parameters(self)
         logger.info(f"M2TTSModel: {total:,} parameters ({trainable:,} trainable), "
                     f"{total * 4 / (1024 * 1024):.1f} MB fp32")
+
+    def enable_backward(self, enabled: bool = True) -> "M2TTSModel":
+        """Switch the graph of ``forward`` on or off (a plain attribute, no
+        state_dict entry), together with the switches of ``text_encoder``,
+        ``duration_predictor``, ``length_regulator`` and ``decoder``.  A stage
+        that refuses its shape raises NotImplementedError, and then nothing is
+        switched.  The vocoder's switch is not touched."""
+        stages = (self.text_encoder, self.duration_predictor, self.length_regulator, self.decoder)
+        before = [st.backward_enabled for st in stages]
+        try:
+            for st in stages:
+                st.enable_backward(enabled)
+        except NotImplementedError:
+            for st, was in zip(stages, before):
+                st.backward_enabled = was
+            raise
+        self.backward_enabled = bool(enabled)
+        return self
 
     # -------------------------------------------------------------- handle
     def _eval_if_training(self):
@@ -519,6 +609,15 @@ class M2TTSModel(nn.Module):
                 max_target_length: Optional[int] = None) -> Dict[str, Optional[Tensor]]:
         """Reference tts_model.py:350-400: audio only when not training."""
         ops.require_device(phoneme_ids, what="M2TTSModel")
+        if self.backward_enabled and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            enc, mask = self.text_encoder(phoneme_ids, phoneme_lengths)
+            dur = self.duration_predictor(enc)
+            durations = target_durations if target_durations is not None else dur.detach()
+            reg = self.length_regulator(enc, durations, max_target_length)
+            mel = self.decoder(reg)
+            audio = None if self.training else self.vocoder(mel.transpose(1, 2))
+            return {"encoder_output": enc, "duration_pred": dur, "regulated_output": reg,
+                    "mel_output": mel, "audio_output": audio, "padding_mask": mask}
         with torch.no_grad():
             hm = self._hip(phoneme_ids.device)
             enc, mask = hm.text_encoder(phoneme_ids, phoneme_lengths)

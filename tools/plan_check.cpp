@@ -23,6 +23,7 @@
 // The decoder's gradient plan (csrc/decoder_grad_plan.h) is checked the same way (check_decoder_grad).
 // The text encoder's gradient plan (csrc/encoder_grad_plan.h) likewise (check_encoder_grad), with the
 // embedding's split over the positions.
+// The duration predictor's gradient plan (csrc/duration_grad_plan.h) likewise (check_duration_grad).
 // The vocoder's gradient plan (csrc/vocoder_grad_plan.h) runs here too: the tape and the backward's
 // workspace against a plain restatement of their formulas, the carved regions against each other,
 // and every launch row against the LDS and grid limits.
@@ -38,6 +39,7 @@
 #include "m2_model.h"
 #include "transformer_plan.h"
 #include "decoder_grad_plan.h"
+#include "duration_grad_plan.h"
 #include "encoder_grad_plan.h"
 #include "vocoder_grad_plan.h"
 #include "vocoder_launch.h"
@@ -1048,6 +1050,104 @@ static void check_encoder_grad() {
     std::printf(" (%d plans, %d rows)\n", plans, rows_seen);
 }
 
+// The duration predictor's gradient plan (csrc/duration_grad_plan.h) over the stage1 training shape and
+// the test cases.  Restated plainly: the tape is y1 and y2 [B, H, S]; the workspace is four maps of that
+// size (xt, u, gu, gy), the partials (the wider of the head's slots, one of 3 H + 1 floats per utterance
+// and 64-position chunk, and the conv weight gradient's split partials), one conv weight [H, H, 3] and one
+// bias [H]; eight steps, the first and last the transposes.  Sizes, overlaps and launch limits as
+// check_decoder_grad.
+static void check_duration_grad() {
+    int bad = 0, plans = 0, rows_seen = 0;
+    const int shapes[][3] = {{64, 32, 100}, {64, 2, 100}, {32, 1, 1},  {32, 3, 63}, {96, 2, 64},
+                             {128, 2, 65},  {64, 1, 130}, {16, 2, 7},  {24, 2, 33}};
+    for (const auto& sh : shapes) {
+        const dugrad::Dims d{sh[0], sh[1], sh[2]};
+        bad += !dugrad::dims_ok(d);
+        ++plans;
+        const size_t H = (size_t)d.H, B = (size_t)d.B, S = (size_t)d.S, n = B * H * S;
+        // the tape
+        const size_t second = (n * 4 + 255) / 256 * 256, tape = second + n * 4;
+        Sizer ts;
+        dugrad::carve_tape(ts, d, nullptr);
+        bad += ts.off != tape;
+        {
+            std::vector<char> mem(tape);
+            Carve tc(mem.data(), mem.size()), less(mem.data(), mem.size() - 1);
+            float *maps[dugrad::kMaps], *none[dugrad::kMaps];
+            dugrad::carve_tape(tc, d, maps);
+            dugrad::carve_tape(less, d, none);
+            bad += !tc.ok || less.ok;
+            if (tc.ok)
+                bad += reinterpret_cast<char*>(maps[0]) != mem.data() || reinterpret_cast<char*>(maps[1]) != mem.data() + second;
+        }
+        // the partials and the workspace
+        const size_t nslots = B * ((S + 63) / 64);
+        const size_t part = std::max(nslots * (3 * H + 1), loss::dw_plan(loss::ConvGeo{d.H, d.H, 3, 1, 1, 1}, d.B, d.S).part_floats);
+        bad += dugrad::part_floats(d) != part || dugrad::slots(d) != nslots || dugrad::slot_floats(d.H, false) != 2 * H;
+        const size_t floats[7] = {n, n, n, n, part, 3 * H * H, H};
+        size_t woff = 0;
+        for (const size_t f : floats) woff = (woff + 255) / 256 * 256 + f * 4;
+        Sizer ws;
+        dugrad::carve_backward(ws, d, nullptr);
+        bad += ws.off != woff;
+        {
+            std::vector<char> wm(woff);
+            Carve wc(wm.data(), wm.size()), wless(wm.data(), wm.size() - 1);
+            dugrad::Bufs b{}, nb{};
+            dugrad::carve_backward(wc, d, &b);
+            dugrad::carve_backward(wless, d, &nb);
+            bad += !wc.ok || wless.ok;
+            const char* p[8] = {reinterpret_cast<char*>(b.xt),   reinterpret_cast<char*>(b.u),    reinterpret_cast<char*>(b.gu),
+                                reinterpret_cast<char*>(b.gy),   reinterpret_cast<char*>(b.part), reinterpret_cast<char*>(b.wtmp),
+                                reinterpret_cast<char*>(b.btmp), wm.data() + wm.size()};
+            bad += p[0] != wm.data();
+            for (int i = 0; i < 6; ++i) bad += p[i + 1] < p[i] + floats[i] * 4;  // no overlap
+            bad += p[7] != p[6] + floats[6] * 4;
+        }
+        // the rows
+        const std::vector<dugrad::Step> plan = dugrad::plan_steps(d);
+        bad += plan.size() != 8 || plan.front().kind != dugrad::STEP_XT || plan.back().kind != dugrad::STEP_DT;
+        int finishes = 0, convs = 0;
+        for (const dugrad::Step& s : plan) {
+            std::vector<loss::LaunchRow> rows, rows_acc;
+            dugrad::step_rows(s, d, false, rows);
+            dugrad::step_rows(s, d, true, rows_acc);
+            bad += rows.empty() || rows_acc.size() != rows.size() + (s.kind == dugrad::STEP_CONV ? 2 : 0);
+            for (const loss::LaunchRow& r : rows_acc) {
+                ++rows_seen;
+                const bool db = std::strcmp(r.kernel, "conv_db_kernel") == 0;
+                bad += r.lds > (size_t)loss::kMaxLds || r.gx < 1 || r.gy < 1 || r.gz < 1 || r.gy > 65535 ||
+                       r.gz > 65535 || r.threads != (db ? loss::kDbThreads : 256);
+                finishes += std::strcmp(r.kernel, "dec_finish_kernel") == 0;
+                convs += std::strcmp(r.kernel, "conv_dx_mfma_kernel") == 0 || std::strcmp(r.kernel, "conv_dw_mfma_kernel") == 0;
+            }
+        }
+        bad += finishes != 10 || convs != 4;  // both convs take the exact-f32 MFMA for the data and the weight gradient
+        const loss::LaunchRow hd = dugrad::bn_row(d, true), b1 = dugrad::bn_row(d, false);
+        bad += hd.gx != (unsigned)((S + 63) / 64) || hd.gy != (unsigned)B || hd.lds != H * 64 * 4 || b1.lds != 0 ||
+               b1.gx != hd.gx;
+        const loss::LaunchRow xt = dugrad::tr_row(d.B, d.S, d.H), cf = dugrad::conv_fwd_row(d);
+        bad += xt.gx != (unsigned)((H + 31) / 32) || xt.gy != (unsigned)((S + 31) / 32) || xt.gz != (unsigned)B;
+        bad += cf.gx != (unsigned)((S + 1023) / 1024) || cf.gy != (unsigned)(H / 8) || cf.gz != (unsigned)B;
+        const std::string line = dugrad::print_plan(d);
+        char head[128];
+        std::snprintf(head, sizeof(head), "H=%d B=%d S=%d tape=%zu ws=%zu part=%zu u=recomputed xt:dur_transpose_kernel[grid=",
+                      d.H, d.B, d.S, tape + 256, woff + 256, part);
+        bad += line.compare(0, std::strlen(head), head) != 0 ||
+               line.find(" hd:dur_bn_bwd_kernel[grid=") == std::string::npos ||
+               line.find(" c1:conv_dw_mfma_kernel[grid=") == std::string::npos ||
+               line.find(" dt:dur_transpose_kernel[grid=") == std::string::npos;
+    }
+    bad += dugrad::dims_ok(dugrad::Dims{8, 1, 4}) || dugrad::dims_ok(dugrad::Dims{60, 1, 4}) ||
+           dugrad::dims_ok(dugrad::Dims{136, 1, 4}) || dugrad::dims_ok(dugrad::Dims{64, -1, 4}) ||
+           dugrad::dims_ok(dugrad::Dims{64, 1, (1 << 20) + 1});
+    bad += dugrad::dims_ok(dugrad::Dims{128, 16, 1 << 20});  // a map above 2^30 floats
+    bad += !dugrad::dims_ok(dugrad::Dims{16, 0, 0}) || !dugrad::dims_ok(dugrad::Dims{128, 8, 1 << 20});
+    std::printf("duration_grad:");
+    expect("plans_match", bad == 0 && plans == 9, true);
+    std::printf(" (%d plans, %d rows)\n", plans, rows_seen);
+}
+
 // ---------------------------------------------------------------------------
 // The transformer stacks' launch plan (csrc/transformer_plan.h) against the rules the drivers
 // and launchers carried before it: tfl_use / tf_chain / tf_first_fused / text_encoder_layers /
@@ -1343,6 +1443,7 @@ int main() {
     check_vocoder_grad();
     check_decoder_grad();
     check_encoder_grad();
+    check_duration_grad();
     const m2_config stage1{256, 64, 64, 2, 2, 2, 128, 1000}, stage2{256, 96, 80, 3, 3, 2, 256, 1000};
     for (const bool huge : {false, true}) {
         check(2 * huge, "stage1", stage1, huge);

@@ -42,7 +42,15 @@ encoder at 100 phonemes): --encoder-only prints m2_encoder_train_forward
 (encoder_train_forward_ms), m2_encoder_backward with every gradient
 (encoder_backward_ms, encoder_backward_over_forward) and
 m2_length_regulator_backward at --frames frames per utterance
-(regulator_adjoint_ms), alone.  Each
+(regulator_adjoint_ms), alone.  The duration predictor's training side
+(--hidden, --phonemes): --duration-only prints
+m2_duration_train_forward (duration_train_forward_ms) and m2_duration_backward
+with every gradient and d_enc (duration_backward_ms,
+duration_backward_over_forward), alone.  --model-step prints the stage-1
+training step of an M2TTSModel with enable_backward() in training mode, at
+--phonemes phonemes and --frames frames per utterance: forward with a graph
+(model_forward_graph_ms), then the same plus the reference's stage-1 loss
+(L1 mel + 0.1 x MSE duration) and backward() (model_step_ms), alone.  Each
 figure is the median of --iters timed calls after --warmup untimed ones.
 """
 import argparse
@@ -117,6 +125,56 @@ def encoder_lines(out, args, dev):
     out["regulator_adjoint_ms"] = timed(lambda: ops.regulate_backward(d_reg, cum, S), args.warmup, args.iters)
 
 
+def duration_lines(out, args, dev):
+    """The duration predictor's training forward and backward."""
+    from m2amd import ops
+    from models.tts_model import DurationPredictor
+    B, S, H = args.batch, args.phonemes, args.hidden
+    pred = DurationPredictor(H).to(dev).eval()
+    params = [p.detach() for p in pred.parameters()]
+    bn = torch.cat([ops.batchnorm_eval_stats(b.norm.weight, b.norm.bias, b.norm.running_mean, b.norm.running_var,
+                                             b.norm.eps) for b in pred.predictor.conv_layers])
+    enc = torch.randn(B, S, H, device=dev)
+    _, tape = ops.duration_train_forward(params, bn, enc)
+    d_dur = torch.randn(B, S, device=dev)
+    out["duration_train_forward_ms"] = timed(lambda: ops.duration_train_forward(params, bn, enc), args.warmup,
+                                             args.iters)
+    out["duration_backward_ms"] = timed(lambda: ops.duration_backward(params, bn, enc, tape, d_dur), args.warmup,
+                                        args.iters)
+    out["duration_backward_over_forward"] = out["duration_backward_ms"] / out["duration_train_forward_ms"]
+
+
+def model_step_lines(out, args, dev):
+    """M2TTSModel.forward with a graph, and the stage-1 step: the reference's loss (L1 mel + 0.1 x MSE
+    duration) and backward().  Every utterance fills its --frames frames."""
+    import warnings
+
+    import torch.nn.functional as F
+    from models.tts_model import M2TTSModel
+    B, S, T, H, M = args.batch, args.phonemes, args.frames, args.hidden, args.mels
+    model = M2TTSModel(args.vocab, H, M, args.enc_layers, args.dec_layers, args.heads).to(dev).train().enable_backward()
+    ids = torch.randint(0, args.vocab, (B, S), device=dev)
+    lengths = torch.randint(S // 2, S + 1, (B,), device=dev)
+    durations = torch.full((B, S), T // S, dtype=torch.int64, device=dev)
+    durations[:, :T % S] += 1
+    target = torch.randn(B, T, M, device=dev)
+
+    def forward():
+        return model(ids, lengths, target_durations=durations, max_target_length=T)
+
+    def step():
+        for p in model.parameters():
+            p.grad = None
+        o = forward()
+        (F.l1_loss(o["mel_output"], target) + 0.1 * F.mse_loss(o["duration_pred"], durations.float())).backward()
+
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)  # training mode computes the eval function, said once
+        out["model_forward_graph_ms"] = timed(forward, args.warmup, args.iters)
+        out["model_step_ms"] = timed(step, args.warmup, args.iters)
+    out["model_step_over_forward"] = out["model_step_ms"] / out["model_forward_graph_ms"]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
@@ -131,6 +189,8 @@ def main():
     ap.add_argument("--vocab", type=int, default=256)
     ap.add_argument("--enc-layers", type=int, default=2)
     ap.add_argument("--encoder-only", action="store_true")
+    ap.add_argument("--duration-only", action="store_true")
+    ap.add_argument("--model-step", action="store_true")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--iters", type=int, default=10)
     args = ap.parse_args()
@@ -148,6 +208,18 @@ def main():
         out = {"batch": args.batch, "phonemes": args.phonemes, "frames": args.frames, "vocab": args.vocab,
                "hidden": args.hidden, "enc_layers": args.enc_layers, "heads": args.heads, "iters": args.iters}
         encoder_lines(out, args, dev)
+        print(json.dumps(out))
+        return
+    if args.duration_only:
+        out = {"batch": args.batch, "phonemes": args.phonemes, "hidden": args.hidden, "iters": args.iters}
+        duration_lines(out, args, dev)
+        print(json.dumps(out))
+        return
+    if args.model_step:
+        out = {"batch": args.batch, "phonemes": args.phonemes, "frames": args.frames, "mels": args.mels,
+               "vocab": args.vocab, "hidden": args.hidden, "enc_layers": args.enc_layers, "dec_layers": args.dec_layers,
+               "heads": args.heads, "iters": args.iters}
+        model_step_lines(out, args, dev)
         print(json.dumps(out))
         return
     loss = CombinedTTSLoss().eval().to(dev)
